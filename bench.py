@@ -1,21 +1,26 @@
 #!/usr/bin/env python3
 """Benchmark of the AdaLog calibration hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 One *step* = one complete calibration (QuantCalibrator.batching_quant_calib: capture + every module's FPCS search) of
 BASELINE.json configs[1]: deit_small, W4A4 (configs/4bit.py), 32 synthetic 224x224 calibration images PER GPU
 (weak scaling: the global calibration set is 32*N images sharded by rank, scores all-reduced over RCCL).
 Inputs (images, random-init weights) are resident in HBM before the timed region.  Rank 0 prints ONE JSON line:
-  value      = calibration images per second, whole job  (= 32*N*K / wall, wall = max over ranks)
+  value      = calibration images per second, whole job  (= 32*N*K / wall, wall = max over ranks); ms_per_step = wall / K
   roofline   = the dominant scoring kernel (largest summed launch time; the library reports which kernel each launch used):
                algorithmic flops of its launches / their summed duration, measured live with events on the launch stream
                during the timed steps; config.scoring_kernels lists every kernel the same way
+A plain run does only that: set-up, W warm-up steps, the K timed steps, the dump, the line.  --full adds
+  config.other_schedule = the same K steps timed again on the other schedule (not with --no-rerun-all)
   hbm_kernels = the HBM-class kernels of the path (fake-quant, self-MSE scoring, quantile, packing) against 8 TB/s
   brecq      = BRECQ iterations per second on one block (bounded sample)
+  quant_forward = the calibrated model's quant_forward pass (graph replay, eager, raw FP32)
   cpu_baseline = the CPU oracle (a port of the reference's algorithm, oracle/) timed on the host cores on a bounded
                sample of the same workload and scaled to images/s with the work model of BASELINE.md section 2
+(the last four on one GPU only, and not with --no-cpu-baseline).
+--dump-outputs DIR writes what the last timed step computed (dump_outputs) so that two builds can be compared.
 """
 import argparse
 import copy
@@ -367,6 +372,26 @@ def quant_forward_rate(calibrated, images, dev, reps=5):
                     "listeners on every module), kept for callers that hook modules; packed weights cached; raw = the FP32 model (rocBLAS)"}
 
 
+DUMP_SAMPLE = 1 << 16         # elements written of a larger tensor by dump_outputs
+
+
+def dump_outputs(model, out_dir):
+    """What a caller of the timed path receives: the calibrated model's state_dict (every quantiser's scale, zero point, log
+    base and tables, and the weights / LayerNorm parameters that re-parameterisation rewrote), one <out_dir>/<key>.npy per
+    entry in its own shape, float32 (float64 for float64 and integer entries).  An entry of more than DUMP_SAMPLE elements
+    is written as DUMP_SAMPLE of its flattened elements, at sorted indices from a generator with a fixed seed (the same in
+    every run and build): ~14 MB in all for deit_small."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for key, t in model.state_dict().items():
+        t = t.detach().cpu()
+        if t.numel() > DUMP_SAMPLE:
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_SAMPLE].sort().values
+            t = t.reshape(-1)[idx]
+        dt = torch.float32 if t.dtype in (torch.float32, torch.float16, torch.bfloat16, torch.bool) else torch.float64
+        np.save(os.path.join(out_dir, key + ".npy"), t.to(dt).numpy())
+
+
 def _cpu_sample(threads, n_cand, min_seconds=0.0):
     """Seconds the oracle needs for one weight-scoring + one activation-scoring call of ``n_cand`` candidates each at
     deit_small attn.proj size (32 images x 197 tokens, 384 -> 384, W4A4) on ``threads`` host threads (thread-count probe, and
@@ -583,14 +608,20 @@ def main():
                     help="fixed calibration-set size sharded over the GPUs (strong scaling; BASELINE config 4 = 1024 over 8); "
                          "default: --images-per-gpu x N (weak scaling)")
     ap.add_argument("--depth", type=int, default=None, help="truncate the block count (debug only; invalidates the metric)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also time the other schedule, the HBM-class kernels, BRECQ, quant_forward and "
+                         "the CPU-oracle baseline (with its HIP cross-check)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the calibrated model of the last timed step to DIR/<state_dict key>.npy (see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip hbm_kernels, brecq, quant_forward and cpu_baseline")
     ap.add_argument("--schedule", choices=("reference", "product"), default="reference",
                     help="what the main timed region (`value`) runs.  reference: every search of every round, as reference "
                          "quant_layers/linear.py:536-541 / matmul.py:275-277 do -- no candidate work is skipped.  product: the "
                          "package's default, which does not re-run a search whose inputs are bit-identical to the previous round's "
-                         "nor the dead weight self-search (same calibrated model).  The other schedule is timed in a second region "
-                         "of the same run and reported under config.other_schedule")
-    ap.add_argument("--no-rerun-all", action="store_true", help="skip the second timed region")
+                         "nor the dead weight self-search (same calibrated model).  With --full the other schedule is timed in a "
+                         "second region of the same run and reported under config.other_schedule")
+    ap.add_argument("--no-rerun-all", action="store_true", help="with --full: skip the second timed region")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -682,10 +713,12 @@ def main():
     by = prof.stop()
     coll = parallel.collective_stats()
     round_stats = _search.round_stats() if args.schedule == "product" else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(models[args.warmup + args.steps - 1], args.dump_outputs)
     # second timed region: the same K steps on the OTHER schedule (both produce the same calibrated model, tests/calibrator_cases.py)
     wall_all = None
     other = "product" if args.schedule == "reference" else "reference"
-    if not args.no_rerun_all:
+    if args.full and not args.no_rerun_all:
         set_schedule(other)
         _search.reset_round_stats()
         more = [copy.deepcopy(base) for _ in range(args.steps)]
@@ -789,7 +822,7 @@ def main():
                                            "WRITE_SIZE, per launch); null for any other workload",
                          "launches": n, "avg_launch_ms": ms / max(n, 1)},
         }
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             result["hbm_kernels"] = hbm_kernels(ops, dev)
             try:
                 result["brecq"] = brecq_rate(args.model, args.bits, dev)

@@ -1,7 +1,8 @@
 #!/bin/bash
-# copies the summaries of tools/final_run.sh (gpurun_out/final, scratch) into profiles/ (tracked), named per round
+# copies the summaries of tools/final_run.sh OUT_DIR (untracked) into profiles/ (tracked), named per round:
+#   bash tools/collect_profiles.sh ROUND OUT_DIR
 r=${1:-r06}
-f=gpurun_out/final
+f=${2:?usage: bash tools/collect_profiles.sh ROUND OUT_DIR}
 cp $f/bench.json profiles/${r}_bench.json
 for m in deit_tiny vit_base swin_small swin_base w3 w6 swin_base_w3_128img; do [ -f $f/bench_$m.json ] && cp $f/bench_$m.json profiles/${r}_bench_$m.json; done
 grep -h '^{' $f/bench_gloo2.json | tail -1 > profiles/${r}_bench_gloo_2ranks_1gpu.json
