@@ -174,6 +174,7 @@ class AsymmetricallyBatchingQuantLinear(PTQSLBatchingQuantLinear):
         self.a_quantizer.scale.data.copy_(scale.view(self.a_quantizer.scale.shape))
         self.a_quantizer.zero_point.data.copy_((-amn / scale).view(self.a_quantizer.zero_point.shape))
         self.a_quantizer.inited = True
+        self.a_quantizer.forget_codes_fit()
 
     # ------------------------------------------------------------------ helpers
     def _tokens_per_image(self):
@@ -216,6 +217,7 @@ class AsymmetricallyBatchingQuantLinear(PTQSLBatchingQuantLinear):
         search.commit_param(self.a_quantizer.zero_point, zp)
         self.a_quantizer.inited = True
         self.a_quantizer._zp_on_grid = True
+        self.a_quantizer.forget_codes_fit()
 
     def _int_dt(self, rows, prefer_fp8=False, fixed=None):
         """Storage type of the integer operand pair of an output-based search over `rows` candidate rows.  fp8 needs every
@@ -508,7 +510,10 @@ class AsymmetricallyBatchingQuantLinear(PTQSLBatchingQuantLinear):
             return out if addend is None else addend + out
         be = backend.get()
         aq = self.a_quantizer
-        if not isinstance(self.w_quantizer, UniformQuantizer) or aq.n_bits > 7 or self.w_quantizer.n_bits > 7:
+        if (not isinstance(self.w_quantizer, UniformQuantizer) or aq.n_bits > 7 or self.w_quantizer.n_bits > 7
+                or not self.w_quantizer.codes_fit(-128, 127) or not aq.codes_fit(-128, 127)):
+            # (a zero point off the grid, as a min/max initialisation or a loaded checkpoint may leave it, gives codes q - rne(z)
+            # beyond int8, which the packed operands cannot hold: compose, as the searches do for such quantisers)
             out = super().quant_forward(x)
             return out if addend is None else addend + out
         lead = x.shape[:-1]
@@ -599,6 +604,7 @@ class AsymmetricallyChannelWiseBatchingQuantLinear(AsymmetricallyBatchingQuantLi
             self.a_quantizer.channel_wise = False
             self.a_quantizer.scale = nn.Parameter(t_scale.detach().clone())
             self.a_quantizer.zero_point = nn.Parameter(t_zp.detach().clone())
+            self.a_quantizer.forget_codes_fit()
             AsymmetricallyBatchingQuantLinear.hyperparameter_searching(self)
 
 
@@ -786,7 +792,8 @@ class PostGeluLogBasedBatchingQuantLinear(AsymmetricallyBatchingQuantLinear):
         """quant_forward takes the fused route (packer + bf16 MFMA product): the callers that hand over fc1's output with
         ``pre_gelu`` (utils/models.py: Mlp) ask first."""
         return (self.calibrated and isinstance(self.w_quantizer, UniformQuantizer) and not self.a_quantizer.training_mode
-                and not (torch.is_grad_enabled() and self.w_quantizer.training_mode) and getattr(backend.get(), "QF_EXTRAS", False))
+                and not (torch.is_grad_enabled() and self.w_quantizer.training_mode) and getattr(backend.get(), "QF_EXTRAS", False)
+                and self.w_quantizer.codes_fit(-256, 256))
 
     def quant_forward(self, x, addend=None, pre_gelu=False):
         """``pre_gelu``: x is fc1's output and the layer's input is GELU(x) -- applied in the packer's loader (one pass less over the
@@ -794,7 +801,8 @@ class PostGeluLogBasedBatchingQuantLinear(AsymmetricallyBatchingQuantLinear):
         assert self.calibrated, f"Module should be calibrated before run quant_forward for {self}"
         aq = self.a_quantizer
         if (torch.is_grad_enabled() and (self.w_quantizer.training_mode or aq.training_mode)) \
-                or not isinstance(self.w_quantizer, UniformQuantizer) or aq.training_mode:
+                or not isinstance(self.w_quantizer, UniformQuantizer) or aq.training_mode or not self.w_quantizer.codes_fit(-256, 256):
+            # (weight codes q - rne(z) beyond +-256 are not exact in the bf16 weight operand: compose)
             # (a BRECQ iteration: GELU inside the quantiser's kernels, the residual inside the product's reduction pass)
             return MinMaxQuantLinear.quant_forward(self, x, pre_gelu=pre_gelu, addend=addend)
         be = backend.get()

@@ -250,6 +250,14 @@ class AsymmetricallyBatchingQuantMatMul(PTQSLBatchingQuantMatMul):
     def _commit(self, quantizer, scale, zp):
         search.commit_param(quantizer.scale, scale)             # (no copy when the search's last kernel wrote them in place)
         search.commit_param(quantizer.zero_point, zp)
+        quantizer.forget_codes_fit()
+
+    def packed_codes_fit(self):
+        """quant_forward's packed operands hold every code q - rne(z) of the uniform input quantisers: int8 for q . k^T (A and
+        B), bf16 (exact to +-256) for the B operand of softmax . v.  Otherwise the product composes (fake-quant, fp32 product)."""
+        b_ok = self.B_quantizer.codes_fit(-256, 256) if isinstance(self, PostSoftmaxAsymmetricallyBatchingQuantMatMul) \
+            else self.B_quantizer.codes_fit(-128, 127)
+        return b_ok and (isinstance(self, PostSoftmaxAsymmetricallyBatchingQuantMatMul) or self.A_quantizer.codes_fit(-128, 127))
 
     def _fpcs(self, which, fpcs_width=16, steps=6, fixed=None, dt=I8, fixed_sa=None, sa_mul=1.0, checked=False):
         """matmul.py:243-262."""
@@ -304,7 +312,8 @@ class AsymmetricallyBatchingQuantMatMul(PTQSLBatchingQuantMatMul):
 
     def quant_forward(self, A, B, a_pre=False, b_pre=False):
         assert self.calibrated, f"Module should be calibrated before run quant_forward for {self}"
-        if a_pre or b_pre or self._training() or self.A_quantizer.n_bits > 7 or self.B_quantizer.n_bits > 7:
+        if (a_pre or b_pre or self._training() or self.A_quantizer.n_bits > 7 or self.B_quantizer.n_bits > 7
+                or not self.packed_codes_fit()):
             return super().quant_forward(A, B, a_pre, b_pre)
         be = backend.get()
         H = self._heads()
@@ -443,7 +452,7 @@ class PostSoftmaxAsymmetricallyBatchingQuantMatMul(AsymmetricallyBatchingQuantMa
 
     def quant_forward(self, A, B, a_pre=False, b_pre=False):
         assert self.calibrated, f"Module should be calibrated before run quant_forward for {self}"
-        if a_pre or b_pre or self._training() or self.A_quantizer.training_mode:
+        if a_pre or b_pre or self._training() or self.A_quantizer.training_mode or not self.packed_codes_fit():
             return MinMaxQuantMatMul.quant_forward(self, A, B, a_pre, b_pre)
         be = backend.get()
         H = self._heads()

@@ -66,6 +66,29 @@ class UniformQuantizer(nn.Module):
 
     def end_training(self):
         self.training_mode = False
+        self.forget_codes_fit()
+
+    def codes_fit(self, lo: int, hi: int) -> bool:
+        """Every integer code q - rne(z), q in [0, 2^bits - 1], lies in [lo, hi] for every zero point: the packed operands of
+        quant_forward store these codes (int8: [-128, 127]; bf16 exactly: [-256, 256]), and a code outside wraps or saturates
+        there.  One host read per change of the zero point: the answer is kept, keyed by the zero point tensor and its in-place
+        version, until forget_codes_fit() -- which the owning layers call wherever they write the zero point through ``.data``
+        (writes the version cannot see).  Called on every quant_forward: the hit path is a few attribute reads."""
+        if self.sym:
+            return True
+        z = self._parameters.get("zero_point")
+        if z is None:
+            z = self.zero_point
+        hit = self.__dict__.get("_codes_fit")
+        if hit is not None and hit[0] is z and hit[1] == z._version and hit[2] == lo and hit[3] == hi and hit[4] == self.n_bits:
+            return hit[5]
+        rz = torch.round(z.detach().float())
+        ok = bool(((rz <= -lo) & (rz >= (2 ** self.n_bits - 1) - hi)).all())
+        self.__dict__["_codes_fit"] = (z, z._version, lo, hi, self.n_bits, ok)
+        return ok
+
+    def forget_codes_fit(self):
+        self.__dict__.pop("_codes_fit", None)
 
     def forward(self, x):
         if self.n_bits == 32:

@@ -487,23 +487,7 @@ def test_fused_block_quant_forward_matches_the_module_route(bits):
     assert torch.equal(y2, y_fused)                                    # deterministic
 
 
-def _minmax_params(t, bits, per=None):
-    """(scale, zero_point) of an asymmetric uniform quantiser from the tensor's range; per: dims to KEEP (None = per tensor)."""
-    if per is None:
-        mn, mx = t.min(), t.max()
-    else:
-        red = [d for d in range(t.dim()) if d not in per]
-        mn, mx = t.amin(dim=red, keepdim=True), t.amax(dim=red, keepdim=True)
-    s = (mx - mn).clamp_min(1e-6) / (2 ** bits - 1)
-    return s, torch.round(-mn / s).clamp(0, 2 ** bits - 1)
-
-
-def _arm(q, s, z=None):
-    q.scale.data.copy_(s.reshape(q.scale.shape))
-    if z is not None:
-        q.zero_point.data.copy_(z.reshape(q.zero_point.shape))
-    q.inited = True
-    q._zp_on_grid = True
+from tests.qf_cases import arm as _arm, minmax_params as _minmax_params  # noqa: E402  (shared with tests/test_gpu_quant_forward.py)
 
 
 @pytest.mark.parametrize("bits", [4, 6])
