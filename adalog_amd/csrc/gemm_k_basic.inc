@@ -181,7 +181,7 @@ __device__ __forceinline__ int swz2(int row, int slot) { return row * BK2 + ((sl
 // Epilogue of the large-tile kernel, specialised at compile time so the unrolled body is branch-free:
 //   STORE: write out (quant_forward) / else: squared error against ref;  EDGE: tile touches the M or N boundary;
 //   ROWS: per-row scale and bias present.
-template <int DT, int TM, bool STORE, bool EDGE, bool ROWS, bool ADD = false>
+template <int DT, int TM, bool STORE, bool EDGE, bool ROWS, bool ADD = false, bool ROWMAP = false>
 __device__ __forceinline__ void epilogue2(const GemmArgs& p, typename Acc<DT>::type (&acc)[TM][2], int g, int gh, int m0,
                                           int n0, int wr, int wc, int frow, int fkg, float* red) {
     constexpr int BM2 = 64 * TM;
@@ -191,6 +191,13 @@ __device__ __forceinline__ void epilogue2(const GemmArgs& p, typename Acc<DT>::t
     float* outg = STORE ? p.out + ogo : nullptr;
     const float* addg = (STORE && ADD && p.addend) ? p.addend + ogo : nullptr;
     const int ldr = (int)p.ldr, rcs = (int)p.ref_cs, ldo = (int)p.ldo;
+    // ROWMAP: the row of out / addend that GEMM row `row` lands on (the row scatter of adalog_gemm_out_gen_rows)
+    [[maybe_unused]] auto orow = [&](int row) {
+        if constexpr (ROWMAP) {
+            if (p.o_rows) { const int im = row / p.row_period; return p.o_rows[row - im * p.row_period] + im * p.row_period; }
+        }
+        return row;
+    };
     float alpha[2], beta[2], cm[2], csum[2] = {0.0f, 0.0f};
     int rc0[2], colj[2];
 #pragma unroll
@@ -218,15 +225,17 @@ __device__ __forceinline__ void epilogue2(const GemmArgs& p, typename Acc<DT>::t
             for (int r = 0; r < 16; ++r) {
                 const int row = rb0 + (r & 3) + 8 * (r >> 2);
                 const bool rv = !EDGE || row < p.M;
+                const int ro = ROWMAP ? (rv ? orow(row) : 0) : row;
 #pragma unroll
                 for (int j = 0; j < 2; ++j)
-                    av[r][j] = (addg && rv && (!EDGE || cm[j] != 0.0f)) ? addg[row * ldo + colj[j]] : 0.0f;
+                    av[r][j] = (addg && rv && (!EDGE || cm[j] != 0.0f)) ? addg[ro * ldo + colj[j]] : 0.0f;
             }
         }
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int row = rb0 + (r & 3) + 8 * (r >> 2);
             if (!EDGE || row < p.M) {                   // edge tiles (rare) predicate whole rows; interior tiles have no branch
+                [[maybe_unused]] const int ro = ROWMAP ? orow(row) : row;
                 float rs = 1.0f, rbv = 0.0f;
                 if (ROWS) { rs = p.row_scale[row]; rbv = p.row_bias[row]; }
 #pragma unroll
@@ -237,7 +246,7 @@ __device__ __forceinline__ void epilogue2(const GemmArgs& p, typename Acc<DT>::t
                     if (STORE) {
                         if (!EDGE || cm[j] != 0.0f) {
                             if (ADD) { if (addg) o += av[r][j]; }
-                            outg[row * ldo + colj[j]] = o;
+                            outg[(ROWMAP ? ro : row) * ldo + colj[j]] = o;
                         }
                     } else {
                         const float e = refg[row * ldr + rc0[j]] - o;
@@ -344,9 +353,14 @@ __device__ __forceinline__ void epilogue_lds(const GemmArgs& p, typename Acc<DT>
 // packer's arithmetic (reciprocal multiply, IEEE quotient inside the tie zone, clamp, biased u8 conversion), so the int8 image in
 // LDS equals adalog_pack_uniform's bit for bit and the separate pack launch of the activation disappears (reference
 // quant_layers/linear.py:46-51: q_a(x) inside the layer's forward).  int8 only (DT == 0).
-template <int DT, int TM, bool STORE, bool GENA = false, bool ADD = false>
+//
+// ROWMAP (quant_forward of a Swin block, adalog_gemm_out_gen_rows): the generated A rows are gathered and the STORE epilogue's rows
+// scattered through the maps of GemmArgs (a_rows / o_rows, period row_period) -- roll + window partition in front of qkv, window
+// reverse + roll back + the residual add behind proj.
+template <int DT, int TM, bool STORE, bool GENA = false, bool ADD = false, bool ROWMAP = false>
 __global__ __launch_bounds__(512, 2) void k_gemm_cand(GemmArgs p) {
     static_assert(!ADD || STORE, "the epilogue extras belong to the STORE form");
+    static_assert(!ROWMAP || (GENA && STORE), "the row maps belong to the generated-A STORE form");
     static_assert(!GENA || (DT == 0 && TM <= 2), "the generated A operand: int8, at most two row blocks per thread");
     constexpr int BM2 = 64 * TM;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -398,7 +412,14 @@ __global__ __launch_bounds__(512, 2) void k_gemm_cand(GemmArgs p) {
     [[maybe_unused]] float g_s = 1.0f, g_inv = 1.0f, g_lo = 0.0f, g_hi = 0.0f;
     if constexpr (GENA) {
         const float* xb = p.gen_x + (int64_t)g * p.gen_sg + lslot * 16;
-        const int r0 = min(m0 + lrow, p.M - 1), r1 = min(m0 + lrow + 64, p.M - 1);
+        int r0 = min(m0 + lrow, p.M - 1), r1 = min(m0 + lrow + 64, p.M - 1);
+        if constexpr (ROWMAP) {
+            if (p.a_rows) {
+                const int i0 = r0 / p.row_period, i1 = r1 / p.row_period;
+                r0 = p.a_rows[r0 - i0 * p.row_period] + i0 * p.row_period;
+                r1 = p.a_rows[r1 - i1 * p.row_period] + i1 * p.row_period;
+            }
+        }
         xr0 = xb + (int64_t)r0 * p.gen_ldx;
         xr1 = xb + (int64_t)r1 * p.gen_ldx;
         g_s = p.gen_scale[gh * p.gen_sn];
@@ -506,11 +527,11 @@ __global__ __launch_bounds__(512, 2) void k_gemm_cand(GemmArgs p) {
             else epilogue_lds<DT, TM, false, false>(p, acc, g, gh, m0, n0, wr, wc, frow, fkg, red, stage);
         }
     } else if (edge) {
-        if (rows) epilogue2<DT, TM, STORE, true, true, ADD>(p, acc, g, gh, m0, n0, wr, wc, frow, fkg, red);
-        else epilogue2<DT, TM, STORE, true, false, ADD>(p, acc, g, gh, m0, n0, wr, wc, frow, fkg, red);
+        if (rows) epilogue2<DT, TM, STORE, true, true, ADD, ROWMAP>(p, acc, g, gh, m0, n0, wr, wc, frow, fkg, red);
+        else epilogue2<DT, TM, STORE, true, false, ADD, ROWMAP>(p, acc, g, gh, m0, n0, wr, wc, frow, fkg, red);
     } else {
-        if (rows) epilogue2<DT, TM, STORE, false, true, ADD>(p, acc, g, gh, m0, n0, wr, wc, frow, fkg, red);
-        else epilogue2<DT, TM, STORE, false, false, ADD>(p, acc, g, gh, m0, n0, wr, wc, frow, fkg, red);
+        if (rows) epilogue2<DT, TM, STORE, false, true, ADD, ROWMAP>(p, acc, g, gh, m0, n0, wr, wc, frow, fkg, red);
+        else epilogue2<DT, TM, STORE, false, false, ADD, ROWMAP>(p, acc, g, gh, m0, n0, wr, wc, frow, fkg, red);
     }
     if (!STORE && p.partial) {
         __syncthreads();

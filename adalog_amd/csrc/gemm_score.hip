@@ -698,11 +698,11 @@ extern "C" int adalog_gemm_out_gen(const float* x, int64_t ldx, int64_t sxg, int
     return adalog_gemm_out_gen_ex(x, ldx, sxg, K, a_scale, a_zp, a_pg, n_bits, B, sBg, M, N, Kp, G, gmod, sa, sa_g, sa_mul, sb, sb_g, sb_n,
                                   bias, bi_g, bi_n, nullptr, out, ldo, sOg, stream);
 }
-// ... + addend[g][m][n] (same strides as out): the residual stream added in the epilogue (x + proj(...) of a transformer block)
-extern "C" int adalog_gemm_out_gen_ex(const float* x, int64_t ldx, int64_t sxg, int K, const float* a_scale, const float* a_zp, int64_t a_pg,
-                                      int n_bits, const void* B, int64_t sBg, int M, int N, int64_t Kp, int G, int gmod, const float* sa,
-                                      int64_t sa_g, float sa_mul, const float* sb, int64_t sb_g, int64_t sb_n, const float* bias,
-                                      int64_t bi_g, int64_t bi_n, const float* addend, float* out, int64_t ldo, int64_t sOg, void* stream) {
+static int gemm_out_gen_impl(const float* x, int64_t ldx, int64_t sxg, int K, const float* a_scale, const float* a_zp, int64_t a_pg,
+                             int n_bits, const void* B, int64_t sBg, int M, int N, int64_t Kp, int G, int gmod, const float* sa,
+                             int64_t sa_g, float sa_mul, const float* sb, int64_t sb_g, int64_t sb_n, const float* bias,
+                             int64_t bi_g, int64_t bi_n, const float* addend, float* out, int64_t ldo, int64_t sOg, const int* a_rows,
+                             const int* o_rows, int64_t period, void* stream) {
     ADALOG_ARG_CHECK(x && a_scale && a_zp && B && sa && sb && out, "gemm_out_gen: null pointer");
     ADALOG_ARG_CHECK(M >= 1 && N >= 1 && G >= 1 && gmod >= 1 && G % gmod == 0 && K >= 16 && K % 16 == 0 && Kp >= K && Kp % BK2 == 0,
                      "gemm_out_gen: K must be a multiple of 16, Kp a multiple of 128 covering it");
@@ -720,6 +720,8 @@ extern "C" int adalog_gemm_out_gen_ex(const float* x, int64_t ldx, int64_t sxg, 
     p.order = 0; p.reduce_cols = 0;
     p.gen_x = x; p.gen_ldx = ldx; p.gen_sg = sxg; p.gen_K = K; p.gen_scale = a_scale; p.gen_zp = a_zp; p.gen_sn = a_pg;
     p.gen_qmax = (float)((1 << n_bits) - 1);
+    const bool rowmap = a_rows || o_rows;
+    p.a_rows = a_rows; p.o_rows = o_rows; p.row_period = (int)(rowmap ? period : 1);
     // 128-row tiles while they give every CU one, else 64-row tiles (attn.proj of deit_small: 50 x 2 -> 99 x 2 tiles)
     int tmv = pick_tm_out(M, (int64_t)cdiv(N, BN2) * G);
     if (tmv > 2) tmv = 2;
@@ -727,19 +729,45 @@ extern "C" int adalog_gemm_out_gen_ex(const float* x, int64_t ldx, int64_t sxg, 
     const int64_t tiles = (int64_t)p.MT * p.NT * G;
     ADALOG_ARG_CHECK(tiles < ((int64_t)1 << 31), "gemm_out_gen: grid too large");
     const size_t shm = (size_t)(64 * tmv + BN2) * BK2 + (512 + 256) * sizeof(float);
-#define LAUNCH_GENA(TMV, ADDV, LABEL)                                                                             \
+#define LAUNCH_GENA(TMV, ADDV, MAPV, LABEL)                                                                       \
     do {                                                                                                          \
         static unsigned long long attr_dev = 0;                                                                   \
-        { hipError_t ea__ = adalog_max_lds(reinterpret_cast<const void*>(&k_gemm_cand<0, TMV, true, true, ADDV>), (int)(72 * 1024), &attr_dev); \
+        { hipError_t ea__ = adalog_max_lds(reinterpret_cast<const void*>(&k_gemm_cand<0, TMV, true, true, ADDV, MAPV>), (int)(72 * 1024), &attr_dev); \
           if (ea__ != hipSuccess) { adalog_set_error("hipFuncSetAttribute", ea__); return (int)ea__; } }         \
         adalog_note_kernel(LABEL);                                                                                \
-        hipLaunchKernelGGL((k_gemm_cand<0, TMV, true, true, ADDV>), dim3((unsigned)tiles), dim3(512), shm, (hipStream_t)stream, p); \
+        hipLaunchKernelGGL((k_gemm_cand<0, TMV, true, true, ADDV, MAPV>), dim3((unsigned)tiles), dim3(512), shm, (hipStream_t)stream, p); \
     } while (0)
-    if (addend) { if (tmv == 2) LAUNCH_GENA(2, true, "k_gemm_cand_gen_ex"); else LAUNCH_GENA(1, true, "k_gemm_cand_gen_ex"); }
-    else { if (tmv == 2) LAUNCH_GENA(2, false, "k_gemm_cand_gen"); else LAUNCH_GENA(1, false, "k_gemm_cand_gen"); }
+    if (rowmap) {
+        if (addend) { if (tmv == 2) LAUNCH_GENA(2, true, true, "k_gemm_cand_gen_rows"); else LAUNCH_GENA(1, true, true, "k_gemm_cand_gen_rows"); }
+        else { if (tmv == 2) LAUNCH_GENA(2, false, true, "k_gemm_cand_gen_rows"); else LAUNCH_GENA(1, false, true, "k_gemm_cand_gen_rows"); }
+    } else if (addend) { if (tmv == 2) LAUNCH_GENA(2, true, false, "k_gemm_cand_gen_ex"); else LAUNCH_GENA(1, true, false, "k_gemm_cand_gen_ex"); }
+    else { if (tmv == 2) LAUNCH_GENA(2, false, false, "k_gemm_cand_gen"); else LAUNCH_GENA(1, false, false, "k_gemm_cand_gen"); }
 #undef LAUNCH_GENA
     ADALOG_LAUNCH_CHECK("adalog_gemm_out_gen");
     return 0;
+}
+
+// ... + addend[g][m][n] (same strides as out): the residual stream added in the epilogue (x + proj(...) of a transformer block)
+extern "C" int adalog_gemm_out_gen_ex(const float* x, int64_t ldx, int64_t sxg, int K, const float* a_scale, const float* a_zp, int64_t a_pg,
+                                      int n_bits, const void* B, int64_t sBg, int M, int N, int64_t Kp, int G, int gmod, const float* sa,
+                                      int64_t sa_g, float sa_mul, const float* sb, int64_t sb_g, int64_t sb_n, const float* bias,
+                                      int64_t bi_g, int64_t bi_n, const float* addend, float* out, int64_t ldo, int64_t sOg, void* stream) {
+    return gemm_out_gen_impl(x, ldx, sxg, K, a_scale, a_zp, a_pg, n_bits, B, sBg, M, N, Kp, G, gmod, sa, sa_g, sa_mul, sb, sb_g, sb_n, bias,
+                             bi_g, bi_n, addend, out, ldo, sOg, nullptr, nullptr, 1, stream);
+}
+
+// ... with the rows of one group (G = 1) remapped in periods of L rows (the tokens of one image): A row r is read from x row
+// a_rows[r % L] + (r / L) L, and out / addend row o_rows[r % L] + (r / L) L is written (either map may be null = identity; entries in
+// [0, L); o_rows a permutation, so that every output row is written once).  Swin: a_rows = the roll + window partition in front of
+// qkv, o_rows = the same map behind proj with the block input as addend.
+extern "C" int adalog_gemm_out_gen_rows(const float* x, int64_t ldx, int K, const float* a_scale, const float* a_zp, int n_bits,
+                                        const void* B, int M, int N, int64_t Kp, const float* sa, float sa_mul, const float* sb,
+                                        int64_t sb_n, const float* bias, int64_t bi_n, const float* addend, float* out, int64_t ldo,
+                                        const int* a_rows, const int* o_rows, int64_t period, void* stream) {
+    ADALOG_ARG_CHECK(period >= 1 && M % period == 0, "gemm_out_gen_rows: M must be a multiple of the period");
+    ADALOG_ARG_CHECK(ldo >= N && (int64_t)M * ldo < ((int64_t)1 << 31), "gemm_out_gen_rows: output exceeds 32-bit addressing");
+    return gemm_out_gen_impl(x, ldx, 0, K, a_scale, a_zp, 0, n_bits, B, 0, M, N, Kp, 1, 1, sa, 0, sa_mul, sb, 0, sb_n, bias, 0, bi_n, addend,
+                             out, ldo, 0, a_rows, o_rows, period, stream);
 }
 
 // Attention searches with uniform candidates (reference quant_layers/matmul.py:135-163 / 173-201), GEN form: scores of the

@@ -41,6 +41,10 @@ struct GemmArgs {
     const float* gen_sa;                                 // optional device scalar folded into the column factor (the fixed operand's scale)
     float gen_qmax, gen_tie;                             // 2^bits - 1; |frac| above which the IEEE quotient decides the bin
     long long* timeline;             // profiling only (tools/gemm_lab.hip): 8 cycle stamps per workgroup, else nullptr
+    // ROWMAP form of the large-tile kernel (adalog_gemm_out_gen_rows): row r of the generated A operand is read from row
+    // a_rows[r % row_period] + (r / row_period) * row_period of gen_x, and the STORE epilogue writes (and reads the addend of) row
+    // o_rows[r % row_period] + (r / row_period) * row_period; a null map is the identity
+    const int* a_rows; const int* o_rows; int row_period;
 };
 #if defined(GEMM_LAB_TIMELINE)   // tools/lab only: the stamp stores would otherwise cost waits in the production kernel
 #define TL_STAMP(i) do { if (p.timeline && threadIdx.x == 0) p.timeline[(size_t)lid * 8 + (i)] = (long long)__builtin_readcyclecounter(); } while (0)

@@ -629,13 +629,20 @@ __global__ __launch_bounds__(256) void k_pack_uniform_tab16(PackArgs a) {
 // ATen's softmax_warp_forward, operation for operation (element k = lane + 64 it; max; e = exp(x - max) summed per lane in `it`
 // order, then the xor butterfly 32, 16, .., 1; e / sum), so that the composed route (torch softmax, then the packer) and this
 // kernel quantise the same fp32 probabilities.
+//
+// BIAS (Swin's window attention, reference utils/wrap_net.py:35-52): no multiplier; instead the relative-position bias is gathered and
+// the shift mask added in front of the softmax, as the module route's separate ATen adds round them: e = s + table[index[r][c]][h],
+// then e = e + mask[w][r][c] -- rows [G = windows * H][S][S], h = g % H, w = (g / H) % nW.
 struct SoftmaxPackArgs {
     const float* x; int64_t rows; int S; float mul;      // scores [rows][S] (contiguous), multiplied by `mul` first
     const float* scale; const float* qv; const float* mant; int levels2;   // the AdaLog quantiser: device scalars (scale, q), 37 numerators
     unsigned short* out; int64_t Kp;                     // bf16 bits [rows][Kp], zero beyond S
+    const float* table; const int64_t* index;            // BIAS: relative_position_bias_table [*][H], relative_position_index [S][S]
+    const float* mask; int H, nW;                        // BIAS: shift mask [nW][S][S] or null
 };
 constexpr int SM_ROWS = 4;
-__global__ __launch_bounds__(256) void k_softmax_adalog_pack(SoftmaxPackArgs a) {
+template <bool BIAS>
+__global__ __launch_bounds__(256) void k_softmax_adalog_pack_t(SoftmaxPackArgs a) {
     __shared__ unsigned short s_lut[258];
     const int lw = a.levels2 + 2;
     const float qf = a.qv[0], sc = a.scale[0];
@@ -666,8 +673,25 @@ __global__ __launch_bounds__(256) void k_softmax_adalog_pack(SoftmaxPackArgs a) 
         const int64_t row = row0 + rr;
         if (row >= a.rows) return;
         float el[4];
+        if constexpr (BIAS) {
+            const int64_t g = row / a.S;
+            const int r = (int)(row - g * a.S), h = (int)(g % a.H);
+            const int64_t* ix = a.index + (int64_t)r * a.S;
+            const float* mk = a.mask ? a.mask + ((g / a.H) % a.nW * a.S + r) * a.S : nullptr;
 #pragma unroll
-        for (int it = 0; it < 4; ++it) el[it] = lane + 64 * it < a.S ? raw[rr][it] * a.mul : -__builtin_inff();
+            for (int it = 0; it < 4; ++it) {
+                const int k = lane + 64 * it;
+                float e = -__builtin_inff();
+                if (k < a.S) {
+                    e = raw[rr][it] + a.table[ix[k] * a.H + h];
+                    if (mk) e = e + mk[k];
+                }
+                el[it] = e;
+            }
+        } else {
+#pragma unroll
+            for (int it = 0; it < 4; ++it) el[it] = lane + 64 * it < a.S ? raw[rr][it] * a.mul : -__builtin_inff();
+        }
         float mx = el[0];
 #pragma unroll
         for (int it = 1; it < 4; ++it) mx = mx < el[it] ? el[it] : mx;
@@ -696,26 +720,33 @@ __global__ __launch_bounds__(256) void k_softmax_adalog_pack(SoftmaxPackArgs a) 
 }
 
 // quant_forward of an attention block (reference utils/wrap_net.py:19-31 + quant_layers/matmul.py:43-45): the qkv projection's output
-// [B][N][3][H][64] is split into heads, passed through the three per-head uniform input quantisers (q and k of q . k^T, v of
+// [B][N][3][H][D] is split into heads, passed through the three per-head uniform input quantisers (q and k of q . k^T, v of
 // softmax . v) and written as the packed operands of the two products in ONE pass -- no permuted fp32 copies of q / k / v, no three
-// packer launches:  qp, kp int8 [B*H][N][128] (64 codes q - z, 64 zero bytes), vp bf16 [B*H][64][Np] (v transposed: a row per
+// packer launches:  qp, kp int8 [B*H][N][128] (D codes q - z, 128 - D zero bytes), vp bf16 [B*H][D][Np] (v transposed: a row per
 // channel, a column per token, zero beyond N).  Codes as adalog_pack_uniform writes them: clamp(rne(x / s) + rne(z), 0, qmax) - rne(z).
+// D = 16 QD (QD = 1..4): a block takes 64 tokens of one (image, head), QD threads per token (16 channels each); the other threads of
+// the block only help with the transposed store of v.  QMUL (Swin, wrap_net.py:41): q is multiplied by q_mul first (fp32 product,
+// ATen's q * scale with the scale cast to fp32) -- the codes are those of the module route's pack of q * scale.
 struct AttnSplitArgs {
     const float* qkv; int B, N, H;
     const float* qs; const float* qz; const float* ks; const float* kz; const float* vs; const float* vz;    // [H] each (pg = 1) or [1] (pg = 0)
     int pg; float q_qmax, k_qmax, v_qmax;
     int8_t* qp; int8_t* kp; unsigned short* vp; int64_t Np;
+    float q_mul;
 };
+template <int QD, bool QMUL>
 __global__ __launch_bounds__(256) void k_attn_split_pack(AttnSplitArgs a) {
+    constexpr int D = 16 * QD;
     __shared__ unsigned short vt[64][72];                       // [channel][token of the tile], rows padded against bank conflicts
     const int h = blockIdx.y, b = blockIdx.z, n0 = blockIdx.x * 64;
-    const int t = threadIdx.x, row = t >> 2, qt = t & 3;       // token of the tile, 16-channel quarter
+    const int t = threadIdx.x, row = t / QD, qt = t % QD;      // token of the tile, 16-channel slice
+    const bool loader = t < 64 * QD;                           // (QD = 4: every thread)
     const int n = n0 + row;
-    const int HD = a.H * 64;
+    const int HD = a.H * D;
     const int64_t g = (int64_t)b * a.H + h;
     const int pi = a.pg ? h : 0;
-    const bool live = n < a.N;
-    const float* src = a.qkv + ((int64_t)b * a.N + (live ? n : 0)) * (3 * HD) + h * 64 + qt * 16;
+    const bool live = loader && n < a.N;
+    const float* src = a.qkv + ((int64_t)b * a.N + (live ? n : 0)) * (3 * HD) + h * D + qt * 16;
     auto load16 = [&](const float* p_, float (&x)[16]) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -728,11 +759,17 @@ __global__ __launch_bounds__(256) void k_attn_split_pack(AttnSplitArgs a) {
         for (int e = 0; e < 16; ++e) c[e] = fminf(fmaxf(rintf(x[e] / s) + z, 0.0f), qmax) - z;
     };
     float x[16], c[16];
-    // q and k: one 16-byte store of codes and one of padding per thread and operand
+    // q and k: one 16-byte store of codes and (128 - D) / 16 / QD of padding per thread and operand
     for (int which = 0; which < 2; ++which) {
         const float s = which ? a.ks[pi] : a.qs[pi], z = rintf(which ? a.kz[pi] : a.qz[pi]), qmax = which ? a.k_qmax : a.q_qmax;
         if (live) {
             load16(src + which * HD, x);
+            if constexpr (QMUL) {
+                if (which == 0) {
+#pragma unroll
+                    for (int e = 0; e < 16; ++e) x[e] = x[e] * a.q_mul;
+                }
+            }
             codes(x, s, z, qmax, c);
             uint4 o;
             unsigned* ow = reinterpret_cast<unsigned*>(&o);
@@ -743,22 +780,25 @@ __global__ __launch_bounds__(256) void k_attn_split_pack(AttnSplitArgs a) {
                 for (int e = 0; e < 4; ++e) pk |= ((unsigned)(int)c[4 * j + e] & 0xffu) << (8 * e);
                 ow[j] = pk;
             }
-            int8_t* dst = (which ? a.kp : a.qp) + (g * a.N + n) * 128 + qt * 16;
-            *reinterpret_cast<uint4*>(dst) = o;
-            *reinterpret_cast<uint4*>(dst + 64) = make_uint4(0, 0, 0, 0);
+            int8_t* dst = (which ? a.kp : a.qp) + (g * a.N + n) * 128;
+            *reinterpret_cast<uint4*>(dst + qt * 16) = o;
+#pragma unroll
+            for (int zc = QD + qt; zc < 8; zc += QD) *reinterpret_cast<uint4*>(dst + zc * 16) = make_uint4(0, 0, 0, 0);
         }
     }
     // v: quantise, transpose through LDS, rows of 64 tokens (128 bytes) out
     {
         const float s = a.vs[pi], z = rintf(a.vz[pi]);
         if (live) { load16(src + 2 * HD, x); codes(x, s, z, a.v_qmax, c); }
+        if (loader) {
 #pragma unroll
-        for (int e = 0; e < 16; ++e) vt[qt * 16 + e][row] = live ? (unsigned short)(__float_as_uint(c[e]) >> 16) : (unsigned short)0;   // small integers: exact in bf16
+            for (int e = 0; e < 16; ++e) vt[qt * 16 + e][row] = live ? (unsigned short)(__float_as_uint(c[e]) >> 16) : (unsigned short)0;   // small integers: exact in bf16
+        }
         __syncthreads();
         const int ch = t >> 2, tq = t & 3;                       // channel, 16-token quarter
-        if (n0 + tq * 16 < a.Np) {
+        if (ch < D && n0 + tq * 16 < a.Np) {
             const uint4 lo = *reinterpret_cast<const uint4*>(&vt[ch][tq * 16]), hi = *reinterpret_cast<const uint4*>(&vt[ch][tq * 16 + 8]);
-            unsigned short* dst = a.vp + (g * 64 + ch) * a.Np + n0 + tq * 16;
+            unsigned short* dst = a.vp + (g * D + ch) * a.Np + n0 + tq * 16;
             *reinterpret_cast<uint4*>(dst) = lo;
             *reinterpret_cast<uint4*>(dst + 8) = hi;
         }
@@ -986,29 +1026,77 @@ extern "C" int adalog_softmax_adalog_pack_bf16(const float* x, int64_t rows, int
     ADALOG_ARG_CHECK(x && scale && qv && mant37 && out && rows > 0, "softmax_adalog_pack: null pointer");
     ADALOG_ARG_CHECK(S >= 1 && S <= 256 && Kp >= S && Kp <= 256 && (Kp * 2) % 64 == 0, "softmax_adalog_pack: 1 <= S <= Kp <= 256, Kp a multiple of 32");
     ADALOG_ARG_CHECK(n_bits >= 2 && n_bits <= 7, "softmax_adalog_pack: n_bits must be in [2,7]");
-    SoftmaxPackArgs a{x, rows, S, mul, scale, qv, mant37, 1 << n_bits, reinterpret_cast<unsigned short*>(out), Kp};
+    SoftmaxPackArgs a{x, rows, S, mul, scale, qv, mant37, 1 << n_bits, reinterpret_cast<unsigned short*>(out), Kp, nullptr, nullptr, nullptr, 1, 1};
     adalog_note_kernel("k_softmax_adalog_pack");
-    hipLaunchKernelGGL(k_softmax_adalog_pack, dim3((unsigned)((rows + 4 * SM_ROWS - 1) / (4 * SM_ROWS))), dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(k_softmax_adalog_pack_t<false>, dim3((unsigned)((rows + 4 * SM_ROWS - 1) / (4 * SM_ROWS))), dim3(256), 0, (hipStream_t)stream, a);
     ADALOG_LAUNCH_CHECK("adalog_softmax_adalog_pack_bf16");
     return 0;
 }
 
-// The three operand packs of an attention block's quant_forward in one launch (k_attn_split_pack): qkv fp32 [B][N][3][H][64]
-// (contiguous, 16-byte aligned); (scale, zero point) of the three uniform quantisers per head (pg = 1: [H]) or per tensor (pg = 0);
-// qp, kp int8 [B*H][N][128]; vp bf16 [B*H][64][Np], Np a multiple of 64 covering N.  Head dimension 64 only.
+// Swin's window attention: ((x + relative-position bias) + shift mask).softmax(-1) through the same quantiser into the same operand
+// image.  x: fp32 [G][S][S] contiguous (G = windows * H); table fp32 [(2 Wh - 1)(2 Ww - 1)][H] contiguous; index int64 [S][S] (entries
+// index the table's rows); mask fp32 [nW][S][S] or null, window w = (g / H) % nW.  The table is read on every call (no cached bias).
+extern "C" int adalog_softmax_bias_adalog_pack_bf16(const float* x, int64_t G, int S, int H, const float* table, const int64_t* index,
+                                                    const float* mask, int nW, const float* scale, const float* qv, int n_bits,
+                                                    const float* mant37, void* out, int64_t Kp, void* stream) {
+    if (G == 0) return 0;
+    ADALOG_ARG_CHECK(x && table && index && scale && qv && mant37 && out && G > 0, "softmax_bias_adalog_pack: null pointer");
+    ADALOG_ARG_CHECK(S >= 1 && S <= 256 && Kp >= S && Kp <= 256 && (Kp * 2) % 64 == 0, "softmax_bias_adalog_pack: 1 <= S <= Kp <= 256, Kp a multiple of 32");
+    ADALOG_ARG_CHECK(H >= 1 && G % H == 0 && (!mask || nW >= 1), "softmax_bias_adalog_pack: G must be a multiple of H, nW >= 1 with a mask");
+    ADALOG_ARG_CHECK(n_bits >= 2 && n_bits <= 7, "softmax_bias_adalog_pack: n_bits must be in [2,7]");
+    const int64_t rows = G * S;
+    SoftmaxPackArgs a{x, rows, S, 1.0f, scale, qv, mant37, 1 << n_bits, reinterpret_cast<unsigned short*>(out), Kp, table, index, mask, H,
+                      mask ? nW : 1};
+    adalog_note_kernel("k_softmax_bias_adalog_pack");
+    hipLaunchKernelGGL(k_softmax_adalog_pack_t<true>, dim3((unsigned)((rows + 4 * SM_ROWS - 1) / (4 * SM_ROWS))), dim3(256), 0, (hipStream_t)stream, a);
+    ADALOG_LAUNCH_CHECK("adalog_softmax_bias_adalog_pack_bf16");
+    return 0;
+}
+
+// The three operand packs of an attention block's quant_forward in one launch per 65535 images (k_attn_split_pack): qkv fp32
+// [B][N][3][H][D] (contiguous, 16-byte aligned), D in {16, 32, 48, 64}; (scale, zero point) of the three uniform quantisers per head
+// (pg = 1: [H]) or per tensor (pg = 0); qp, kp int8 [B*H][N][128]; vp bf16 [B*H][D][Np], Np a multiple of 64 covering N.  q_mul != 1:
+// q is multiplied by it (fp32) before its quantiser.  Images beyond grid z's 65535 go in further launches (Swin: B = windows).
+extern "C" int adalog_attn_split_pack_ex(const float* qkv, int B, int N, int H, int D, float q_mul, const float* q_scale, const float* q_zp,
+                                         int q_bits, const float* k_scale, const float* k_zp, int k_bits, const float* v_scale,
+                                         const float* v_zp, int v_bits, int pg, void* qp, void* kp, void* vp, int64_t Np, void* stream) {
+    if (B == 0 || N == 0) return 0;
+    ADALOG_ARG_CHECK(qkv && q_scale && q_zp && k_scale && k_zp && v_scale && v_zp && qp && kp && vp, "attn_split_pack: null pointer");
+    ADALOG_ARG_CHECK(B >= 1 && N >= 1 && H >= 1 && H <= 65535 && Np >= N && Np % 64 == 0, "attn_split_pack: bad sizes (Np: a multiple of 64 covering N)");
+    ADALOG_ARG_CHECK(D >= 16 && D <= 64 && D % 16 == 0, "attn_split_pack: head dimension must be 16, 32, 48 or 64");
+    ADALOG_ARG_CHECK(q_bits >= 2 && q_bits <= 7 && k_bits >= 2 && k_bits <= 7 && v_bits >= 2 && v_bits <= 7, "attn_split_pack: n_bits must be in [2,7]");
+    ADALOG_ARG_CHECK(((((uintptr_t)qkv) | ((uintptr_t)qp) | ((uintptr_t)kp) | ((uintptr_t)vp)) & 15) == 0, "attn_split_pack: 16-byte aligned buffers");
+    const bool qmul = q_mul != 1.0f;
+    adalog_note_kernel("k_attn_split_pack");
+    for (int b0 = 0; b0 < B; b0 += 65535) {
+        const int nb = B - b0 < 65535 ? B - b0 : 65535;
+        const int64_t gb = (int64_t)b0 * H;
+        AttnSplitArgs a{qkv + (int64_t)b0 * N * 3 * H * D, nb, N, H, q_scale, q_zp, k_scale, k_zp, v_scale, v_zp, pg ? 1 : 0,
+                        (float)((1 << q_bits) - 1), (float)((1 << k_bits) - 1), (float)((1 << v_bits) - 1),
+                        reinterpret_cast<int8_t*>(qp) + gb * N * 128, reinterpret_cast<int8_t*>(kp) + gb * N * 128,
+                        reinterpret_cast<unsigned short*>(vp) + gb * D * Np, Np, q_mul};
+        const dim3 grid((unsigned)(Np / 64), (unsigned)H, (unsigned)nb);
+#define LAUNCH_SPLIT(QDV)                                                                                              \
+        do {                                                                                                          \
+            if (qmul) hipLaunchKernelGGL((k_attn_split_pack<QDV, true>), grid, dim3(256), 0, (hipStream_t)stream, a);  \
+            else hipLaunchKernelGGL((k_attn_split_pack<QDV, false>), grid, dim3(256), 0, (hipStream_t)stream, a);      \
+        } while (0)
+        switch (D / 16) {
+            case 1: LAUNCH_SPLIT(1); break;
+            case 2: LAUNCH_SPLIT(2); break;
+            case 3: LAUNCH_SPLIT(3); break;
+            default: LAUNCH_SPLIT(4); break;
+        }
+#undef LAUNCH_SPLIT
+        ADALOG_LAUNCH_CHECK("adalog_attn_split_pack");
+    }
+    return 0;
+}
+
+// Head dimension 64, no multiplier (the ViT / DeiT block).
 extern "C" int adalog_attn_split_pack(const float* qkv, int B, int N, int H, const float* q_scale, const float* q_zp, int q_bits,
                                       const float* k_scale, const float* k_zp, int k_bits, const float* v_scale, const float* v_zp,
                                       int v_bits, int pg, void* qp, void* kp, void* vp, int64_t Np, void* stream) {
-    if (B == 0 || N == 0) return 0;
-    ADALOG_ARG_CHECK(qkv && q_scale && q_zp && k_scale && k_zp && v_scale && v_zp && qp && kp && vp, "attn_split_pack: null pointer");
-    ADALOG_ARG_CHECK(B >= 1 && N >= 1 && H >= 1 && H <= 65535 && B <= 65535 && Np >= N && Np % 64 == 0, "attn_split_pack: bad sizes (Np: a multiple of 64 covering N)");
-    ADALOG_ARG_CHECK(q_bits >= 2 && q_bits <= 7 && k_bits >= 2 && k_bits <= 7 && v_bits >= 2 && v_bits <= 7, "attn_split_pack: n_bits must be in [2,7]");
-    ADALOG_ARG_CHECK(((((uintptr_t)qkv) | ((uintptr_t)qp) | ((uintptr_t)kp) | ((uintptr_t)vp)) & 15) == 0, "attn_split_pack: 16-byte aligned buffers");
-    AttnSplitArgs a{qkv, B, N, H, q_scale, q_zp, k_scale, k_zp, v_scale, v_zp, pg ? 1 : 0, (float)((1 << q_bits) - 1), (float)((1 << k_bits) - 1),
-                    (float)((1 << v_bits) - 1), reinterpret_cast<int8_t*>(qp), reinterpret_cast<int8_t*>(kp),
-                    reinterpret_cast<unsigned short*>(vp), Np};
-    adalog_note_kernel("k_attn_split_pack");
-    hipLaunchKernelGGL(k_attn_split_pack, dim3((unsigned)(Np / 64), (unsigned)H, (unsigned)B), dim3(256), 0, (hipStream_t)stream, a);
-    ADALOG_LAUNCH_CHECK("adalog_attn_split_pack");
-    return 0;
+    return adalog_attn_split_pack_ex(qkv, B, N, H, 64, 1.0f, q_scale, q_zp, q_bits, k_scale, k_zp, k_bits, v_scale, v_zp, v_bits, pg, qp, kp,
+                                     vp, Np, stream);
 }

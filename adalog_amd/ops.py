@@ -619,6 +619,91 @@ def attn_split_pack(qkv, H: int, q_par, k_par, v_par, per_head: bool):
     return qp, kp, vp
 
 
+# Capability flag of the Swin block's fused quant_forward (utils/models.py: SwinTransformerBlock), read like QF_EXTRAS: attn_split_pack_ex,
+# softmax_bias_adalog_pack, gemm_out_gen_rows.  The CPU specification backend of the tests does not have it.
+QF_SWIN = True
+
+
+def attn_split_pack_ex(qkv, H: int, q_par, k_par, v_par, per_head: bool, D: int = 64, q_mul: Optional[float] = None):
+    """attn_split_pack for head dimension D in {16, 32, 48, 64} (qkv fp32 [B, N, 3*H*D]): qp, kp int8 [1, B*H, N, 128] (D codes, then
+    zeros), vp bf16 [1, B*H, D, Np].  ``q_mul``: q is multiplied by float32(q_mul) before its quantiser -- Swin's q * scale, the product
+    ATen forms (adalog_attn_split_pack_ex).  Any number of images B."""
+    qkv = _f32c(qkv, "qkv")
+    B, N, C3 = qkv.shape
+    assert D in (16, 32, 48, 64) and C3 == 3 * H * D
+    Np = ((N + 63) // 64) * 64
+    qp = torch.empty((1, B * H, N, 128), dtype=torch.int8, device=qkv.device)
+    kp = torch.empty((1, B * H, N, 128), dtype=torch.int8, device=qkv.device)
+    vp = torch.empty((1, B * H, D, Np), dtype=torch.bfloat16, device=qkv.device)
+    par = []
+    for s_, z_, b_ in (q_par, k_par, v_par):
+        s_, z_ = _f32c(s_, "scale").reshape(-1), _f32c(z_, "zero_point").reshape(-1)
+        assert s_.numel() == z_.numel() == (H if per_head else 1)
+        par += [s_, z_, int(b_)]
+    rc = _lib.load().adalog_attn_split_pack_ex(qkv.data_ptr(), B, N, H, int(D), 1.0 if q_mul is None else float(q_mul),
+                                              par[0].data_ptr(), par[1].data_ptr(), par[2], par[3].data_ptr(), par[4].data_ptr(), par[5],
+                                              par[6].data_ptr(), par[7].data_ptr(), par[8], 1 if per_head else 0, qp.data_ptr(),
+                                              kp.data_ptr(), vp.data_ptr(), Np, _stream())
+    _lib.check(rc, "adalog_attn_split_pack_ex")
+    qp.k_valid = kp.k_valid = D
+    vp.k_valid = N
+    return qp, kp, vp
+
+
+def softmax_bias_adalog_pack(x3, H: int, table, index, mask, scale, qv, n_bits: int, mant37):
+    """((x3 + relative-position bias) + mask).softmax(-1) through the post-softmax AdaLog quantiser, as the packed bf16 operand
+    [1, G, S, Kp] of softmax . v (adalog_softmax_bias_adalog_pack_bf16).  x3: fp32 [G = windows * H, S, S] contiguous, S <= 256;
+    table: relative_position_bias_table [*, H]; index: relative_position_index [S, S] (int64); mask: [nW, S, S] or None."""
+    x3 = _f32c(x3, "scores")
+    G, R, S = x3.shape
+    assert R == S and G % H == 0
+    table = _f32c(table, "table")
+    assert table.dim() == 2 and table.shape[1] == H
+    assert index.dtype == torch.int64 and index.is_cuda and index.numel() == S * S
+    index = index.contiguous()
+    nW = 0
+    if mask is not None:
+        mask = _f32c(mask, "mask")
+        assert mask.dim() == 3 and mask.shape[1:] == (S, S)
+        nW = mask.shape[0]
+    Kp = pad_k(S, BF16)
+    out = torch.empty((1, G, S, Kp), dtype=torch.bfloat16, device=x3.device)
+    rc = _lib.load().adalog_softmax_bias_adalog_pack_bf16(x3.data_ptr(), G, S, int(H), table.data_ptr(), index.data_ptr(), _ptr(mask), nW,
+                                                         _ptr(_f32c(scale, "scale")), _ptr(_f32c(qv, "qv")), int(n_bits),
+                                                         _ptr(_f32c(mant37, "mant37")), out.data_ptr(), Kp, _stream())
+    _lib.check(rc, "adalog_softmax_bias_adalog_pack_bf16")
+    out.k_valid = S
+    return out
+
+
+def gemm_out_gen_rows(x2, a_scale, a_zp, n_bits: int, B, N: int, sa: Strided, sb: Strided, bias: Optional[Strided],
+                      a_rows=None, o_rows=None, period: int = 1, addend=None, sa_mul: float = 1.0):
+    """gemm_out_gen of one group (x2 fp32 [M, K], per-tensor quantiser) with rows remapped in periods of L = ``period`` rows
+    (adalog_gemm_out_gen_rows): GEMM row r reads x2 row a_rows[r % L] + (r // L) * L and lands on output row o_rows[r % L] + (r // L) * L,
+    where ``addend`` (fp32 [M, N], optional) is added -> fp32 [M, N].  Maps: int32 [L] device tensors holding a permutation of range(L),
+    or None (identity)."""
+    sa, sb = sa.checked(), sb.checked()
+    bias = None if bias is None else bias.checked()
+    M, K = x2.shape
+    Kp = B.shape[-1]
+    a_scale, a_zp = _f32c(a_scale, "a_scale").reshape(-1), _f32c(a_zp, "a_zp").reshape(-1)
+    assert a_scale.numel() == a_zp.numel() == 1 and sa.g == 0 and sb.g == 0 and (bias is None or bias.g == 0)
+    assert B.dtype == torch.int8 and B.is_contiguous() and B.shape[-2] == N
+    assert x2.dtype == torch.float32 and x2.is_cuda and x2.stride(1) == 1 and period >= 1 and M % period == 0
+    for m in (a_rows, o_rows):
+        assert m is None or (m.dtype == torch.int32 and m.is_cuda and m.is_contiguous() and m.numel() == period)
+    out = torch.empty((M, N), dtype=torch.float32, device=x2.device)
+    if addend is not None:
+        addend = _f32c(addend, "addend")
+        assert addend.numel() == M * N
+    rc = _lib.load().adalog_gemm_out_gen_rows(x2.data_ptr(), x2.stride(0), K, a_scale.data_ptr(), a_zp.data_ptr(), int(n_bits), B.data_ptr(),
+                                             M, N, Kp, sa.t.data_ptr(), float(sa_mul), sb.t.data_ptr(), sb.n,
+                                             None if bias is None else bias.t.data_ptr(), 0 if bias is None else bias.n, _ptr(addend),
+                                             out.data_ptr(), N, _ptr(a_rows), _ptr(o_rows), int(period), _stream())
+    _lib.check(rc, "adalog_gemm_out_gen_rows")
+    return out
+
+
 def log2_shift(x, shift: float):
     """log2(x + shift), correctly rounded, -inf where x + shift <= 0 (input of score_act_fused; once per layer)."""
     x = _f32c(x, "x")

@@ -534,6 +534,33 @@ class AsymmetricallyBatchingQuantLinear(PTQSLBatchingQuantLinear):
         out = out.view(*lead, self.out_features)
         return out if (addend is None or fused_add) else addend + out
 
+    def rows_ok(self, x):
+        """quant_forward_rows takes this layer and input: plain uniform int8 quantisers (per-tensor activation, <= 7 bits, codes that
+        fit), the generated-A GEMM for x's shape, and a backend with the row maps."""
+        aq, wq = self.a_quantizer, self.w_quantizer
+        if not (isinstance(wq, UniformQuantizer) and isinstance(aq, UniformQuantizer) and not aq.channel_wise and aq.scale.numel() == 1
+                and aq.n_bits <= 7 and wq.n_bits <= 7 and not aq.training_mode and not wq.training_mode
+                and wq.codes_fit(-128, 127) and aq.codes_fit(-128, 127)):
+            return False
+        be = backend.get()
+        return (getattr(be, "QF_SWIN", False) and x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
+                and be.gemm_out_gen_ok(x.reshape(1, -1, self.in_features), pad_k(self.in_features, I8), aq.n_bits))
+
+    def quant_forward_rows(self, x, a_rows=None, o_rows=None, period=1, addend=None):
+        """quant_forward (the GENA route: the same packed weight, scales and bias) of x [M, K] with its rows remapped in periods of
+        ``period`` rows (ops.gemm_out_gen_rows): output row o_rows[r % L] + (r // L) L = x row a_rows[r % L] + (r // L) L through the layer,
+        plus that row of ``addend``.  Swin's block (utils/models.py): the roll + window partition in front of qkv, and the window reverse +
+        roll back + residual add behind proj, in the two GEMMs' loader and epilogue.  Callers check rows_ok(x) first."""
+        be = backend.get()
+        aq = self.a_quantizer
+        x2 = x.reshape(-1, self.in_features)
+        wp = self._pack_w_cached()
+        sa_, sb_ = Strided(aq.scale.data.view(-1)), Strided(self.w_quantizer.scale.data.view(-1), n=1)
+        bias_ = None if self.bias is None else Strided(self.bias.data, n=1)
+        add_ = None if addend is None else addend.reshape(-1, self.out_features)
+        return be.gemm_out_gen_rows(x2, aq.scale.data, aq.zero_point.data, aq.n_bits, wp, self.out_features, sa_, sb_, bias_,
+                                    a_rows=a_rows, o_rows=o_rows, period=period, addend=add_)
+
 
 class AsymmetricallyChannelWiseBatchingQuantLinear(AsymmetricallyBatchingQuantLinear):
     def __init__(self, in_features: int, out_features: int, bias: bool = True, mode="raw", w_bit=8, a_bit=8,

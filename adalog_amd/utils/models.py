@@ -267,6 +267,17 @@ def window_reverse(windows, window_size, H, W):
     return x.permute(0, 1, 3, 2, 4, 5).contiguous().view(-1, H, W, C)
 
 
+def swin_token_rows(input_resolution, window_size, shift_size):
+    """P: int32 [L = H * W], the token of an image that row r of its windows holds -- window_partition(roll(x, -shift))[r] = x[P[r]]
+    for x [H * W] tokens.  P is a permutation; window_reverse followed by roll(+shift) is its inverse.  The fused quant_forward of a
+    Swin block gathers qkv's rows through it and scatters proj's rows back through it (SwinTransformerBlock._fused_attn_residual)."""
+    H, W = input_resolution
+    idx = torch.arange(H * W, dtype=torch.int32).view(1, H, W, 1)
+    if any(shift_size):
+        idx = torch.roll(idx, shifts=(-shift_size[0], -shift_size[1]), dims=(1, 2))
+    return window_partition(idx, window_size).reshape(-1).contiguous()
+
+
 def get_relative_position_index(win_h, win_w):
     coords = torch.stack(torch.meshgrid([torch.arange(win_h), torch.arange(win_w)], indexing="ij"))
     coords_flatten = torch.flatten(coords, 1)
@@ -305,6 +316,59 @@ class WindowAttention(nn.Module):
         bias = self.relative_position_bias_table[self.relative_position_index.view(-1)].view(
             self.window_area, self.window_area, -1)
         return bias.permute(2, 0, 1).contiguous().unsqueeze(0)
+
+    def _fused_quant_forward_ok(self, x):
+        """quant_forward of the window attention on the fused route (SwinTransformerBlock._fused_attn_residual): Attention's conditions
+        with head dimension a multiple of 16 up to 64, <= 256 tokens per window, and qkv / proj on the generated-A GEMM with row maps.
+        x: the tokens in front of qkv (any order)."""
+        from ..quant_layers.matmul import AsymmetricallyBatchingQuantMatMul, PostSoftmaxAsymmetricallyBatchingQuantMatMul
+        from ..quantizers.uniform import UniformQuantizer
+        m1, m2 = self.matmul1, self.matmul2
+        D, N = self.dim // self.num_heads, self.window_area
+        if not (QF_FUSED and not torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32 and D % 16 == 0 and D <= 64
+                and N <= 256 and isinstance(self.attn_drop, nn.Identity) and isinstance(self.proj_drop, nn.Identity)):
+            return False
+        be = _backend.get()
+        if not (getattr(be, "QF_SWIN", False) and be.softmax_adalog_pack_ok(N)):
+            return False
+        if not (type(m1) is AsymmetricallyBatchingQuantMatMul and type(m2) is PostSoftmaxAsymmetricallyBatchingQuantMatMul
+                and all(_plain_quant_forward(m) for m in (self.qkv, self.proj, m1, m2))
+                and all(hasattr(m, "rows_ok") and m.rows_ok(x) for m in (self.qkv, self.proj))):
+            return False
+        qs = (m1.A_quantizer, m1.B_quantizer, m2.B_quantizer)
+        return (all(isinstance(q, UniformQuantizer) and 2 <= q.n_bits <= 7 and not q.training_mode for q in qs)
+                and not m2.A_quantizer.training_mode and m1._heads() == m2._heads() and m2.A_quantizer.scale.numel() == 1
+                and m1.packed_codes_fit() and m2.packed_codes_fit())
+
+    def _fused_quant_forward(self, x2, rows, period, mask, residual):
+        """The window attention in quant_forward mode (reference utils/wrap_net.py:35-52, every product in quant_forward) as five
+        launches, each restating the module route's arithmetic: qkv with its rows gathered through ``rows`` (the roll + window partition);
+        split + q * scale + three input quantisers + operand packs; q . k^T (int8 MFMA, the module route's call); relative-position bias
+        + shift mask + softmax + AdaLog quantiser + pack; softmax . v (bf16 MFMA) written as [B_, N, H, D]; proj with its rows scattered
+        back through ``rows`` and ``residual`` added in its epilogue.  x2, residual: [images * period, C] in token order -> same."""
+        from ..ops import BF16, I8, Strided
+        be = _backend.get()
+        C, H, N = self.dim, self.num_heads, self.window_area
+        D = C // H
+        Bw = x2.shape[0] // N
+        m1, m2 = self.matmul1, self.matmul2
+        qkv = self.qkv.quant_forward_rows(x2, a_rows=rows, period=period)
+        hm = m1._heads()
+        pg = 1 if hm > 1 else 0
+        sA, zA = m1._q_params(m1.A_quantizer)
+        sB, zB = m1._q_params(m1.B_quantizer)
+        sV, zV = m2._q_params(m2.B_quantizer)
+        qp, kp, vp = be.attn_split_pack_ex(qkv.view(Bw, N, 3 * C), H, (sA, zA, m1.A_quantizer.n_bits), (sB, zB, m1.B_quantizer.n_bits),
+                                           (sV, zV, m2.B_quantizer.n_bits), hm > 1, D=D, q_mul=self.scale)
+        scores = be.gemm_out(I8, qp, kp, N, N, Bw * H, hm, Strided(sA, g=pg), Strided(sB, g=pg), None)
+        if m2._q_host is None:
+            m2._q_host = int(m2.A_quantizer.q.item())
+        qv = _search.const_tensor([float(m2._q_host)], x2.device)
+        a_scale = m2.A_quantizer.scale.data.view(-1)
+        ap = be.softmax_bias_adalog_pack(scores, H, self.relative_position_bias_table.data, self.relative_position_index, mask,
+                                         a_scale, qv, m2.A_quantizer.n_bits, m2._mant37(x2.device))
+        out = be.gemm_out(BF16, ap, vp, N, D, Bw * H, hm, Strided(a_scale), Strided(sV, g=pg), None, sa_mul=m2._ts32(), heads_last=H)
+        return self.proj.quant_forward_rows(out.view(Bw * N, C), o_rows=rows, period=period, addend=residual)
 
     def forward(self, x, mask=None):
         B_, N, C = x.shape
@@ -356,6 +420,24 @@ class SwinTransformerBlock(nn.Module):
         else:
             attn_mask = None
         self.register_buffer("attn_mask", attn_mask, persistent=False)
+        # the fused quant_forward's row map (swin_token_rows): not in the state_dict, on the device before any graph capture
+        self.register_buffer("token_rows", swin_token_rows(input_resolution, ws, ss), persistent=False)
+
+    def _fused_ok(self, x):
+        """quant_forward of the block on the fused route: the window attention's gate (WindowAttention._fused_quant_forward_ok), the
+        map this block was built for, no drop-path (the MLP half decides for itself, Mlp.forward)."""
+        return (x.dim() == 4 and tuple(x.shape[1:3]) == tuple(self.input_resolution) and x.is_contiguous()
+                and self.token_rows is not None and self.token_rows.device == x.device
+                and isinstance(self.drop_path1, nn.Identity) and isinstance(self.drop_path2, nn.Identity)
+                and self.attn._fused_quant_forward_ok(x))
+
+    def _fused_attn_residual(self, x):
+        """x + the attention branch (x [B, H, W, C]) on the fused route -> [B * H * W, C]: norm1, then qkv reading its rows through
+        the roll + window partition map, the attention core, and proj writing its rows back through the same map (window reverse +
+        roll back) with x added in its epilogue -- the roll, partition, reverse, roll-back and residual-add launches disappear."""
+        B, H, W, C = x.shape
+        x2 = x.view(-1, C)
+        return self.attn._fused_quant_forward(self.norm1(x).view(-1, C), self.token_rows, H * W, self.attn_mask, x2)
 
     def _attn(self, x):
         B, H, W, C = x.shape
@@ -369,6 +451,10 @@ class SwinTransformerBlock(nn.Module):
 
     def forward(self, x):
         B, H, W, C = x.shape
+        if self._fused_ok(x):
+            # 11 launches: norm1, qkv, split-pack, q.k^T, bias + mask + softmax-pack, softmax.v, proj (+ x), norm2, fc1, GELU-pack, fc2 (+ x)
+            x = self._fused_attn_residual(x).view(B, H * W, C)
+            return self.mlp(self.norm2(x), residual=x).view(B, H, W, C)
         x = x + self.drop_path1(self._attn(self.norm1(x)))
         x = x.reshape(B, -1, C)
         x = x + self.drop_path2(self.mlp(self.norm2(x)))

@@ -433,6 +433,26 @@ int adalog_softmax_adalog_pack_bf16(const float* x, int64_t rows, int S, float m
 int adalog_attn_split_pack(const float* qkv, int B, int N, int H, const float* q_scale, const float* q_zp, int q_bits,
                            const float* k_scale, const float* k_zp, int k_bits, const float* v_scale, const float* v_zp, int v_bits,
                            int pg, void* qp, void* kp, void* vp, int64_t Np, void* stream);
+/* ---- quant_forward of a Swin block (round 7): the window-attention counterparts of the three above
+ * adalog_attn_split_pack_ex: adalog_attn_split_pack for head dimension D in {16, 32, 48, 64} (qkv fp32 [B][N][3][H][D]; qp, kp int8
+ *   [B*H][N][128] with D codes then zeros; vp bf16 [B*H][D][Np]), q multiplied by q_mul (fp32) first when q_mul != 1 -- Swin's
+ *   q * scale (reference utils/wrap_net.py:41).  Any B: images beyond 65535 go in further launches.
+ * adalog_softmax_bias_adalog_pack_bf16: adalog_softmax_adalog_pack_bf16 of (x + bias) + mask instead of x * mul (wrap_net.py:43-49):
+ *   x fp32 [G][S][S] (G = windows * H), bias[g][r][c] = table[index[r * S + c] * H + g % H] (relative_position_bias_table fp32, read on
+ *   every call; relative_position_index int64 [S][S]), mask fp32 [nW][S][S] of window (g / H) % nW, or null.
+ * adalog_gemm_out_gen_rows: adalog_gemm_out_gen_ex (G = 1, per-tensor quantiser) with a row gather of the activation and a row scatter
+ *   of out and addend, in periods of L rows: A row r reads x row a_rows[r % L] + (r / L) L, out / addend row o_rows[r % L] + (r / L) L
+ *   takes GEMM row r (int32 maps of L entries in [0, L), null = identity; o_rows a permutation).  M a multiple of L. */
+int adalog_attn_split_pack_ex(const float* qkv, int B, int N, int H, int D, float q_mul, const float* q_scale, const float* q_zp, int q_bits,
+                              const float* k_scale, const float* k_zp, int k_bits, const float* v_scale, const float* v_zp, int v_bits,
+                              int pg, void* qp, void* kp, void* vp, int64_t Np, void* stream);
+int adalog_softmax_bias_adalog_pack_bf16(const float* x, int64_t G, int S, int H, const float* table, const int64_t* index,
+                                         const float* mask, int nW, const float* scale, const float* qv, int n_bits,
+                                         const float* mant37, void* out, int64_t Kp, void* stream);
+int adalog_gemm_out_gen_rows(const float* x, int64_t ldx, int K, const float* a_scale, const float* a_zp, int n_bits, const void* B,
+                             int M, int N, int64_t Kp, const float* sa, float sa_mul, const float* sb, int64_t sb_n, const float* bias,
+                             int64_t bi_n, const float* addend, float* out, int64_t ldo, const int* a_rows, const int* o_rows,
+                             int64_t period, void* stream);
 
 /* ---- stable LSD radix sort of fp32 keys, per segment (csrc/radix_sort.hip; hipCUB until round 5): what the sorted forms above and
  * adalog_gram_act_prepare sort with.  x [S][n] contiguous -> sorted [S][n] (ascending per segment; -0 before +0), perm (may be null)
