@@ -1,0 +1,243 @@
+// quant_forward of the attention core in ONE launch (reference utils/wrap_net.py:23-30 / :41-51 with both products in quant_forward,
+// quant_layers/matmul.py:43-45): q . k^T on the int8 MFMA, scale (or relative-position bias + shift mask), softmax, the post-softmax
+// AdaLog quantiser and softmax . v on the bf16 MFMA, from the packed operands of adalog_attn_split_pack(_ex) to the heads-last
+// output [B][N][H][D].  The scores and the quantised probabilities live in LDS only: what gemm_out(I8) -> softmax_(bias_)adalog_pack
+// -> gemm_out(BF16, heads_last) hand from launch to launch through HBM (deit_small, 32 images: 49 MB written and read per block).
+//
+// The result equals those three launches bit for bit, because every step is exact or restated in their order:
+//   scores   int8 MFMA, int32 accumulators (exact in any order; only the ceil(D / 32) K-steps that hold codes are issued), then the
+//            STORE epilogue of k_gemm_cand: s = (float)acc * (sq * 1 * sk); s += 0;
+//   softmax  k_softmax_adalog_pack_t's restatement of ATen's softmax_warp_forward and the quantiser, through the SAME device functions
+//            (softmax_adalog.h): a wavefront per row, element k on lane k % 64, slot k / 64;
+//   . v      v_mfma_f32_32x32x16_bf16, one accumulator chain per output element over the 16-element K chunks 0 .. Kp / 16 - 1 in
+//            ascending order with k_gemm_cand's fragment layout (lanes 0-31: elements 0-7 of the chunk, lanes 32-63: elements 8-15),
+//            then o = (float)acc * (a_scale * sa_mul * sv); o += 0.  No split-K.
+//
+// A workgroup (4 wavefronts) owns one group g = image (or window) * H + head and a tile of TM * 32 query rows:
+//   1. wavefront w forms the score columns [64 w, 64 w + 64) of the tile (operand fragments straight from global memory: a row of qp /
+//      kp is read once per workgroup and wavefront) and writes them as fp32 into the LDS tile [TM * 32][Kp + 4];
+//   2. the wavefronts take the tile's rows in turn: softmax + quantiser, the bf16 row written over the head of its own fp32 row (a
+//      row is in registers before its first bf16 value is stored; rows are Kp + 4 floats apart, so the 16-byte fragment reads of step
+//      3 fall on different banks);
+//   3. wavefront (i, j) multiplies row block i of the probabilities by the 32 channels j of v (fragments of vp from global memory,
+//      requested before step 2 so that they arrive under it) and stores its 32 x 32 piece of out.
+// LDS: TM * 32 * (Kp + 4) * 4 bytes + the 258-entry value table: <= 65.5 KiB for 64 rows x 256 keys, 33 KiB for 32 rows -- two to four
+// workgroups per CU next to <= 128 VGPRs.  The row tile is 32 rows unless 64-row tiles pad no more (N = 197: 7 x 32 = 224 against 256).
+#include "common.h"
+#include "softmax_adalog.h"
+
+namespace {
+
+typedef int v4i __attribute__((ext_vector_type(4)));
+typedef int v16i __attribute__((ext_vector_type(16)));
+typedef float v16f __attribute__((ext_vector_type(16)));
+typedef __bf16 v8bf __attribute__((ext_vector_type(8)));
+
+struct AttnCoreArgs {
+    const int8_t* qp; const int8_t* kp;                  // int8 [G][N][128]: D codes, then zeros
+    const unsigned short* vp;                            // bf16 bits [G][D][Kp]: v transposed, zero beyond N
+    int64_t G; int N, D, H, gmod, MT;                    // MT: row tiles per group
+    int Kp;                                              // keys padded to a multiple of 64 (rows of vp, rows of the probability operand)
+    const float* sq; const float* sk; const float* sv; int pg;   // scales of the q / k / v quantisers: element (g % gmod) * pg
+    float mul;                                           // plain form: scores * mul in front of the softmax
+    const float* a_scale; const float* qv; const float* mant; int levels2;   // post-softmax AdaLog quantiser (device scalars, 37 numerators)
+    float sa_mul;                                        // constant folded into a_scale in the second product's epilogue
+    const float* table; const int64_t* index;            // BIAS: relative_position_bias_table [*][H], relative_position_index [N][N]
+    const float* mask; int nW;                           // BIAS: shift mask [nW][N][N] or null
+    float* out;                                          // fp32 [G / H][N][H][D]
+    int64_t bid0;                                        // first (group, row tile) pair of this launch
+};
+
+template <int TM, bool BIAS>
+__global__ __launch_bounds__(256) void k_attn_core(AttnCoreArgs a) {
+    constexpr int BMR = 32 * TM;
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const int ld = a.Kp + 4;                                           // floats between the rows of the score tile
+    float* S = reinterpret_cast<float*>(smem);
+    unsigned short* s_lut = reinterpret_cast<unsigned short*>(smem + (size_t)BMR * ld * 4);
+
+    const int64_t bid = a.bid0 + blockIdx.x;
+    const int64_t g = bid / a.MT;
+    const int mt = (int)(bid - g * a.MT);
+    const int m0 = mt * BMR;
+    const int gh = (int)(g % a.gmod), h = (int)(g % a.H);
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int frow = lane & 31, fkg = lane >> 5;
+    const int N = a.N, D = a.D, Kp = a.Kp;
+
+    const float qf = a.qv[0], sc = a.a_scale[0];
+    adalog_value_lut_bf16(s_lut, a.levels2, qf, a.mant);
+
+    // ---- 1. scores: wavefront w takes key columns [64 w, 64 w + 64)
+    if (w * 64 < N) {
+        const int nks = (D + 31) >> 5;                                 // 32-byte K-steps that hold codes
+        const int8_t* qg = a.qp + g * (int64_t)N * 128 + fkg * 16;
+        const int8_t* kg = a.kp + g * (int64_t)N * 128 + fkg * 16;
+        v4i af[TM][2], bf[2][2];
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+            const int r = min(m0 + i * 32 + frow, N - 1);
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks)
+                af[i][ks] = ks < nks ? *reinterpret_cast<const v4i*>(qg + (int64_t)r * 128 + ks * 32) : v4i{0, 0, 0, 0};
+        }
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int c = min(w * 64 + j * 32 + frow, N - 1);
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks)
+                bf[j][ks] = ks < nks ? *reinterpret_cast<const v4i*>(kg + (int64_t)c * 128 + ks * 32) : v4i{0, 0, 0, 0};
+        }
+        const float alpha = a.sq[gh * a.pg] * 1.0f * a.sk[gh * a.pg];
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                v16i acc;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[r] = 0;
+                acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(af[i][0], bf[j][0], acc, 0, 0, 0);
+                if (nks > 1) acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(af[i][1], bf[j][1], acc, 0, 0, 0);
+                float* sp = S + (i * 32 + 4 * fkg) * ld + w * 64 + j * 32 + frow;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    float s = (float)acc[r] * alpha;
+                    s += 0.0f;
+                    sp[((r & 3) + 8 * (r >> 2)) * ld] = s;
+                }
+            }
+    }
+
+    // ---- 3 (requests): this wavefront's fragments of v, all K chunks
+    constexpr int NJ = 4 / TM;                                         // 32-channel blocks the wavefronts of a row block are spread over
+    const int pi = w / NJ, pj = w % NJ;
+    const bool pv_live = pj * 32 < D;                                  // (TM = 1: wavefronts 2, 3 have no channels)
+    const int nkv = Kp >> 4;
+    uint4 vf[16];
+    {
+        const int d = min(pj * 32 + frow, D - 1);
+        const unsigned short* vg = a.vp + (g * D + d) * (int64_t)Kp + fkg * 8;
+#pragma unroll
+        for (int ks = 0; ks < 16; ++ks)
+            vf[ks] = (pv_live && ks < nkv) ? *reinterpret_cast<const uint4*>(vg + ks * 16) : make_uint4(0, 0, 0, 0);
+    }
+    __syncthreads();
+
+    // ---- 2. softmax + quantiser, a wavefront per row; the bf16 row replaces the head of the fp32 row
+    {
+        const float inv_s = __builtin_amdgcn_rcpf(sc), rq37 = 37.0f / qf;
+        const int rows = min(BMR, N - m0);
+        const float* mk = nullptr;
+        if constexpr (BIAS) { if (a.mask) mk = a.mask + ((g / a.H) % a.nW) * (int64_t)N * N; }
+        for (int rl = w; rl < rows; rl += 4) {
+            float* srow = S + rl * ld;
+            float el[4];
+#pragma unroll
+            for (int it = 0; it < 4; ++it) {
+                const int k = lane + 64 * it;
+                float e = -__builtin_inff();
+                if (k < N) {
+                    const float s = srow[k];
+                    if constexpr (BIAS) {
+                        const int64_t rc = (int64_t)(m0 + rl) * N + k;
+                        e = s + a.table[a.index[rc] * a.H + h];
+                        if (mk) e = e + mk[rc];
+                    } else {
+                        e = s * a.mul;
+                    }
+                }
+                el[it] = e;
+            }
+            const float sum = softmax_warp_row(el);
+            unsigned short* prow = reinterpret_cast<unsigned short*>(srow);
+#pragma unroll
+            for (int it = 0; it < 4; ++it) {
+                const int k = lane + 64 * it;
+                if (k >= Kp) break;
+                prow[k] = k < N ? adalog_prob_bf16(el[it], sum, sc, inv_s, qf, rq37, a.levels2, s_lut) : (unsigned short)0;
+            }
+        }
+    }
+    __syncthreads();
+
+    // ---- 3. softmax . v: wavefront (pi, pj) -> rows [32 pi, 32 pi + 32) x channels [32 pj, 32 pj + 32)
+    if (pv_live && m0 + pi * 32 < N) {
+        v16f acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+        const uint8_t* pa = smem + (size_t)(pi * 32 + frow) * ld * 4 + fkg * 16;
+#pragma unroll
+        for (int ks = 0; ks < 16; ++ks) {
+            if (ks < nkv) {
+                const uint4 pf = *reinterpret_cast<const uint4*>(pa + ks * 32);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<const v8bf*>(&pf), *reinterpret_cast<const v8bf*>(&vf[ks]),
+                                                              acc, 0, 0, 0);
+            }
+        }
+        const float alpha = a.a_scale[0] * a.sa_mul * a.sv[gh * a.pg];
+        const int col = pj * 32 + frow;
+        float* og = a.out + ((g / a.H) * (int64_t)N * a.H + h) * D + col;
+        if (col < D) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = m0 + pi * 32 + 4 * fkg + (r & 3) + 8 * (r >> 2);
+                if (row < N) {
+                    float o = acc[r] * alpha;
+                    o += 0.0f;
+                    og[(int64_t)row * a.H * D] = o;
+                }
+            }
+        }
+    }
+}
+
+}  // namespace
+
+// the shapes adalog_attn_core takes: 1 <= N <= 256 keys (the bound of adalog_softmax_adalog_pack_bf16), head dimension 16, 32, 48 or 64
+extern "C" int adalog_attn_core_supported(int N, int D) {
+    return (N >= 1 && N <= 256 && (D == 16 || D == 32 || D == 48 || D == 64)) ? 1 : 0;
+}
+
+extern "C" int adalog_attn_core(const void* qp, const void* kp, const void* vp, int64_t G, int N, int D, int H, int gmod, int64_t Np,
+                                const float* q_scale, const float* k_scale, const float* v_scale, int pg, float mul,
+                                const float* a_scale, const float* qv, int n_bits, const float* mant37, float sa_mul,
+                                const float* table, const int64_t* index, const float* mask, int nW, float* out, void* stream) {
+    ADALOG_ARG_CHECK(qp && kp && vp && q_scale && k_scale && v_scale && a_scale && qv && mant37 && out, "attn_core: null pointer");
+    ADALOG_ARG_CHECK(D == 16 || D == 32 || D == 48 || D == 64, "attn_core: head dimension D must be 16, 32, 48 or 64");
+    ADALOG_ARG_CHECK(N >= 1 && N <= 256, "attn_core: 1 <= N <= 256 tokens per group");
+    ADALOG_ARG_CHECK(Np == (int64_t)((N + 63) / 64) * 64, "attn_core: Np (rows of vp) must be N rounded up to a multiple of 64");
+    ADALOG_ARG_CHECK(n_bits >= 2 && n_bits <= 7, "attn_core: n_bits must be in [2,7]");
+    ADALOG_ARG_CHECK(G >= 1 && H >= 1 && gmod >= 1 && G % H == 0 && G % gmod == 0 && (pg == 0 || pg == 1),
+                     "attn_core: G must be a multiple of H and of gmod, pg 0 or 1");
+    ADALOG_ARG_CHECK((table != nullptr) == (index != nullptr) && (!mask || (table && nW >= 1)),
+                     "attn_core: table and index go together; a mask needs them and nW >= 1");
+    ADALOG_ARG_CHECK(((uintptr_t)qp & 15) == 0 && ((uintptr_t)kp & 15) == 0 && ((uintptr_t)vp & 15) == 0,
+                     "attn_core: packed operands must be 16-byte aligned");
+    const int tm = ((N + 31) / 32) * 32 < ((N + 63) / 64) * 64 ? 1 : 2;     // 64-row tiles only when they pad no more than 32-row tiles
+    AttnCoreArgs a{};
+    a.qp = (const int8_t*)qp; a.kp = (const int8_t*)kp; a.vp = (const unsigned short*)vp;
+    a.G = G; a.N = N; a.D = D; a.H = H; a.gmod = gmod; a.MT = cdiv(N, 32 * tm); a.Kp = (int)Np;
+    a.sq = q_scale; a.sk = k_scale; a.sv = v_scale; a.pg = pg; a.mul = mul;
+    a.a_scale = a_scale; a.qv = qv; a.mant = mant37; a.levels2 = 1 << n_bits; a.sa_mul = sa_mul;
+    a.table = table; a.index = index; a.mask = mask; a.nW = nW; a.out = out;
+    const size_t shm = (size_t)32 * tm * (a.Kp + 4) * 4 + 264 * sizeof(unsigned short);
+    const int64_t total = G * a.MT, per_launch = (int64_t)1 << 30;          // flattened (group, row tile) grid, split far below the limit
+    hipStream_t st = (hipStream_t)stream;
+#define LAUNCH_ATTN_CORE(TMV, BIASV)                                                                              \
+    do {                                                                                                          \
+        static unsigned long long attr_dev = 0;                                                                   \
+        { hipError_t ea__ = adalog_max_lds(reinterpret_cast<const void*>(&k_attn_core<TMV, BIASV>), (int)(68 * 1024), &attr_dev); \
+          if (ea__ != hipSuccess) { adalog_set_error("hipFuncSetAttribute", ea__); return (int)ea__; } }          \
+        for (int64_t b0 = 0; b0 < total; b0 += per_launch) {                                                      \
+            a.bid0 = b0;                                                                                          \
+            const int64_t nb = total - b0 < per_launch ? total - b0 : per_launch;                                 \
+            hipLaunchKernelGGL((k_attn_core<TMV, BIASV>), dim3((unsigned)nb), dim3(256), shm, st, a);            \
+        }                                                                                                         \
+    } while (0)
+    adalog_note_kernel("k_attn_core");
+    if (table) { if (tm == 2) LAUNCH_ATTN_CORE(2, true); else LAUNCH_ATTN_CORE(1, true); }
+    else { if (tm == 2) LAUNCH_ATTN_CORE(2, false); else LAUNCH_ATTN_CORE(1, false); }
+#undef LAUNCH_ATTN_CORE
+    ADALOG_LAUNCH_CHECK("adalog_attn_core");
+    return 0;
+}

@@ -10,6 +10,7 @@
 // applied once per output in the GEMM epilogue.  Output layout: out[c][g][r][Kp], Kp = K rounded up to 64 bytes,
 // zero padded (zeros contribute nothing to the integer dot product).
 #include "common.h"
+#include "softmax_adalog.h"
 #include <hip/hip_bf16.h>
 #include <type_traits>
 #include <stdlib.h>
@@ -644,14 +645,8 @@ constexpr int SM_ROWS = 4;
 template <bool BIAS>
 __global__ __launch_bounds__(256) void k_softmax_adalog_pack_t(SoftmaxPackArgs a) {
     __shared__ unsigned short s_lut[258];
-    const int lw = a.levels2 + 2;
     const float qf = a.qv[0], sc = a.scale[0];
-    for (int k = threadIdx.x; k < lw; k += blockDim.x) {
-        const int kqv = k * (int)qf;
-        const int t = kqv / ADALOG_R, j = kqv - t * ADALOG_R;
-        const float v = (k >= a.levels2 || t > 100) ? 0.0f : ldexpf(a.mant[j], -t);
-        s_lut[k] = (unsigned short)(__float_as_uint(v) >> 16);
-    }
+    adalog_value_lut_bf16(s_lut, a.levels2, qf, a.mant);
     __syncthreads();
     const int lane = threadIdx.x & 63;
     const float inv_s = __builtin_amdgcn_rcpf(sc), rq37 = 37.0f / qf;
@@ -692,28 +687,14 @@ __global__ __launch_bounds__(256) void k_softmax_adalog_pack_t(SoftmaxPackArgs a
 #pragma unroll
             for (int it = 0; it < 4; ++it) el[it] = lane + 64 * it < a.S ? raw[rr][it] * a.mul : -__builtin_inff();
         }
-        float mx = el[0];
-#pragma unroll
-        for (int it = 1; it < 4; ++it) mx = mx < el[it] ? el[it] : mx;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { const float b = __shfl_xor(mx, o); mx = mx < b ? b : mx; }
-        float sum = 0.0f;
-#pragma unroll
-        for (int it = 0; it < 4; ++it) { el[it] = expf(el[it] - mx); sum += el[it]; }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) sum = sum + __shfl_xor(sum, o);
+        const float sum = softmax_warp_row(el);
         unsigned short* orow = a.out + row * a.Kp;
 #pragma unroll
         for (int it = 0; it < 4; ++it) {
             const int k = lane + 64 * it;
             if (k >= a.Kp) break;
             unsigned short hv = 0;
-            if (k < a.S) {
-                const float pr = el[it] / sum;
-                float kk = adalog_k_fast(pr, sc, inv_s, qf, rq37, true);
-                kk = (kk == kk) ? fminf(fmaxf(kk, 0.0f), (float)(a.levels2 + 1)) : (float)(a.levels2 + 1);
-                hv = s_lut[(int)kk];
-            }
+            if (k < a.S) hv = adalog_prob_bf16(el[it], sum, sc, inv_s, qf, rq37, a.levels2, s_lut);
             orow[k] = hv;
         }
     }

@@ -676,6 +676,55 @@ def softmax_bias_adalog_pack(x3, H: int, table, index, mask, scale, qv, n_bits: 
     return out
 
 
+# Capability flag of the one-launch attention core (utils/models.py: QF_ATTN_CORE), read like QF_EXTRAS: attn_core, attn_core_ok.  The
+# CPU specification backend of the tests does not have it: the layers then keep composing the three launches.
+QF_ATTN_CORE = True
+
+
+def attn_core_ok(N: int, D: int) -> bool:
+    """attn_core takes N tokens per group and head dimension D (the bound of softmax_adalog_pack_ok, D in {16, 32, 48, 64})"""
+    return softmax_adalog_pack_ok(N) and bool(_lib.load().adalog_attn_core_supported(int(N), int(D)))
+
+
+def attn_core(qp, kp, vp, N: int, D: int, H: int, gmod: int, sA, sB, sV, mul: float, a_scale, qv, n_bits: int, mant37,
+              sa_mul: float = 1.0, table=None, index=None, mask=None):
+    """The attention core of quant_forward in one launch (adalog_attn_core): from the packed operands of attn_split_pack(_ex) to
+    softmax . v as fp32 [B, N, H, D] (heads last), bit-identical to
+        gemm_out(I8, qp, kp) -> softmax_adalog_pack(., mul) / softmax_bias_adalog_pack(., table, index, mask) -> gemm_out(BF16, ., vp,
+        heads_last=H)
+    without the scores and the probability operand in memory.  sA, sB, sV: scales of the q / k / v quantisers, one per head (numel ==
+    gmod == H) or per tensor; a_scale, qv, mant37: the post-softmax AdaLog quantiser; sa_mul: folded into a_scale.  ``table`` and
+    ``index`` (Swin): relative_position_bias_table [*, H] and relative_position_index [N, N] in front of the softmax instead of
+    ``mul``, plus ``mask`` [nW, N, N] or None."""
+    G = qp.shape[1]
+    assert qp.dtype == torch.int8 and kp.dtype == torch.int8 and vp.dtype == torch.bfloat16
+    assert qp.is_cuda and qp.is_contiguous() and kp.is_contiguous() and vp.is_contiguous()
+    assert qp.shape[-2:] == (N, 128) and kp.shape == qp.shape and vp.shape[1] == G and vp.shape[2] == D and G % H == 0
+    Np = vp.shape[-1]
+    sA, sB, sV = (_f32c(t, "scale").reshape(-1) for t in (sA, sB, sV))
+    assert sA.numel() == sB.numel() == sV.numel() and sA.numel() in (1, gmod)
+    pg = 0 if sA.numel() == 1 else 1
+    nW = 0
+    if table is not None:
+        table = _f32c(table, "table")
+        assert table.dim() == 2 and table.shape[1] == H
+        assert index is not None and index.dtype == torch.int64 and index.is_cuda and index.numel() == N * N
+        index = index.contiguous()
+        if mask is not None:
+            mask = _f32c(mask, "mask")
+            assert mask.dim() == 3 and mask.shape[1:] == (N, N)
+            nW = mask.shape[0]
+    else:
+        assert index is None and mask is None
+    out = torch.empty((G // H, N, H, D), dtype=torch.float32, device=qp.device)
+    rc = _lib.load().adalog_attn_core(qp.data_ptr(), kp.data_ptr(), vp.data_ptr(), G, int(N), int(D), int(H), int(gmod), Np,
+                                      sA.data_ptr(), sB.data_ptr(), sV.data_ptr(), pg, float(mul), _ptr(_f32c(a_scale, "scale")),
+                                      _ptr(_f32c(qv, "qv")), int(n_bits), _ptr(_f32c(mant37, "mant37")), float(sa_mul), _ptr(table),
+                                      _ptr(index), _ptr(mask), nW, out.data_ptr(), _stream())
+    _lib.check(rc, "adalog_attn_core")
+    return out
+
+
 def gemm_out_gen_rows(x2, a_scale, a_zp, n_bits: int, B, N: int, sa: Strided, sb: Strided, bias: Optional[Strided],
                       a_rows=None, o_rows=None, period: int = 1, addend=None, sa_mul: float = 1.0):
     """gemm_out_gen of one group (x2 fp32 [M, K], per-tensor quantiser) with rows remapped in periods of L = ``period`` rows

@@ -28,6 +28,14 @@ from .. import train_mm
 
 # quant_forward of a ViT / DeiT block on the fused route (Attention._fused_quant_forward, Mlp.forward): 0 = module by module
 QF_FUSED = os.environ.get("ADALOG_QF_FUSED", "1") != "0"
+# ... with the attention core of the fused route (q . k^T, softmax + AdaLog quantiser, softmax . v) as ONE launch (ops.attn_core)
+# instead of three: 9 launches per block instead of 11, same bits.  Opt-in: 1 = on
+QF_ATTN_CORE = os.environ.get("ADALOG_QF_ATTN_CORE", "0") == "1"
+
+
+def _attn_core_on(be, N, D):
+    """the switch is on, the backend has the one-launch attention core and it takes this shape"""
+    return QF_ATTN_CORE and getattr(be, "QF_ATTN_CORE", False) and be.attn_core_ok(N, D)
 
 
 def _plain_quant_forward(m):
@@ -126,11 +134,15 @@ class Attention(nn.Module):
         sV, zV = m2._q_params(m2.B_quantizer)
         qp, kp, vp = be.attn_split_pack(qkv, H, (sA, zA, m1.A_quantizer.n_bits), (sB, zB, m1.B_quantizer.n_bits),
                                         (sV, zV, m2.B_quantizer.n_bits), hm > 1)
-        scores = be.gemm_out(I8, qp, kp, N, N, B * H, hm, Strided(sA, g=pg), Strided(sB, g=pg), None)
         if m2._q_host is None:
             m2._q_host = int(m2.A_quantizer.q.item())
         qv = _search.const_tensor([float(m2._q_host)], x.device)
         a_scale = m2.A_quantizer.scale.data.view(-1)
+        if _attn_core_on(be, N, self.head_dim):
+            out = be.attn_core(qp, kp, vp, N, self.head_dim, H, hm, sA, sB, sV, self.scale, a_scale, qv, m2.A_quantizer.n_bits,
+                               m2._mant37(x.device), m2._ts32())
+            return self.proj.quant_forward(out.view(B, N, C), addend=residual)
+        scores = be.gemm_out(I8, qp, kp, N, N, B * H, hm, Strided(sA, g=pg), Strided(sB, g=pg), None)
         ap = be.softmax_adalog_pack(scores, self.scale, a_scale, qv, m2.A_quantizer.n_bits, m2._mant37(x.device))
         out = be.gemm_out(BF16, ap, vp, N, self.head_dim, B * H, hm, Strided(a_scale), Strided(sV, g=pg), None, sa_mul=m2._ts32(),
                           heads_last=H)
@@ -360,11 +372,15 @@ class WindowAttention(nn.Module):
         sV, zV = m2._q_params(m2.B_quantizer)
         qp, kp, vp = be.attn_split_pack_ex(qkv.view(Bw, N, 3 * C), H, (sA, zA, m1.A_quantizer.n_bits), (sB, zB, m1.B_quantizer.n_bits),
                                            (sV, zV, m2.B_quantizer.n_bits), hm > 1, D=D, q_mul=self.scale)
-        scores = be.gemm_out(I8, qp, kp, N, N, Bw * H, hm, Strided(sA, g=pg), Strided(sB, g=pg), None)
         if m2._q_host is None:
             m2._q_host = int(m2.A_quantizer.q.item())
         qv = _search.const_tensor([float(m2._q_host)], x2.device)
         a_scale = m2.A_quantizer.scale.data.view(-1)
+        if _attn_core_on(be, N, D):
+            out = be.attn_core(qp, kp, vp, N, D, H, hm, sA, sB, sV, 1.0, a_scale, qv, m2.A_quantizer.n_bits, m2._mant37(x2.device),
+                               m2._ts32(), table=self.relative_position_bias_table.data, index=self.relative_position_index, mask=mask)
+            return self.proj.quant_forward_rows(out.view(Bw * N, C), o_rows=rows, period=period, addend=residual)
+        scores = be.gemm_out(I8, qp, kp, N, N, Bw * H, hm, Strided(sA, g=pg), Strided(sB, g=pg), None)
         ap = be.softmax_bias_adalog_pack(scores, H, self.relative_position_bias_table.data, self.relative_position_index, mask,
                                          a_scale, qv, m2.A_quantizer.n_bits, m2._mant37(x2.device))
         out = be.gemm_out(BF16, ap, vp, N, D, Bw * H, hm, Strided(a_scale), Strided(sV, g=pg), None, sa_mul=m2._ts32(), heads_last=H)

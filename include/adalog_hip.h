@@ -454,6 +454,26 @@ int adalog_gemm_out_gen_rows(const float* x, int64_t ldx, int K, const float* a_
                              int64_t bi_n, const float* addend, float* out, int64_t ldo, const int* a_rows, const int* o_rows,
                              int64_t period, void* stream);
 
+/* ---- quant_forward's attention core in one launch (csrc/attn_core.hip): q . k^T (int8 MFMA), scale or relative-position bias +
+ * shift mask, softmax, the post-softmax AdaLog quantiser and softmax . v (bf16 MFMA) from the packed operands of
+ * adalog_attn_split_pack(_ex); the scores and the quantised probabilities never reach memory.  Bit-identical to
+ *   adalog_gemm_score(int8, qp, kp -> out) ; adalog_softmax_(bias_)adalog_pack_bf16 ; adalog_gemm_out_ex(bf16, ., vp, out_gi = H)
+ * (reference utils/wrap_net.py:23-30 and :41-51 with both products in quant_forward, quant_layers/matmul.py:43-45).
+ * adalog_attn_core: qp, kp int8 [G][N][128] (D codes q - rne(z), then zeros); vp bf16 [G][D][Np] (v transposed, zero beyond N;
+ *   Np = N rounded up to a multiple of 64); G = images (or windows) * H groups, head of group g = g % H; 1 <= N <= 256;
+ *   D in {16, 32, 48, 64}.  q_scale / k_scale / v_scale: the three input quantisers' scales, element (g % gmod) * pg (pg = 1: one
+ *   per head, gmod = H; pg = 0: per tensor).  Plain form (table = index = mask = NULL): softmax(scores * mul).  Bias form: softmax of
+ *   (scores + table[index[r * N + c] * H + g % H]) + mask[(g / H) % nW][r][c] (relative_position_bias_table fp32 [*][H],
+ *   relative_position_index int64 [N][N], mask fp32 [nW][N][N] or NULL); mul is not used.  a_scale, qv: device scalars of the
+ *   post-softmax quantiser (scale, log base q as a float), n_bits in [2, 7], mant37: its 37 numerators; sa_mul: constant folded into
+ *   a_scale in the second product's epilogue.  out fp32 [G / H][N][H][D] (heads last).
+ * adalog_attn_core_supported: 1 when adalog_attn_core takes N tokens per group and head dimension D. */
+int adalog_attn_core_supported(int N, int D);
+int adalog_attn_core(const void* qp, const void* kp, const void* vp, int64_t G, int N, int D, int H, int gmod, int64_t Np,
+                     const float* q_scale, const float* k_scale, const float* v_scale, int pg, float mul, const float* a_scale,
+                     const float* qv, int n_bits, const float* mant37, float sa_mul, const float* table, const int64_t* index,
+                     const float* mask, int nW, float* out, void* stream);
+
 /* ---- stable LSD radix sort of fp32 keys, per segment (csrc/radix_sort.hip; hipCUB until round 5): what the sorted forms above and
  * adalog_gram_act_prepare sort with.  x [S][n] contiguous -> sorted [S][n] (ascending per segment; -0 before +0), perm (may be null)
  * [S][n]: perm[s][i] = index within segment s of its i-th smallest value, equal values in input order.  n <= 8192: one launch (a
