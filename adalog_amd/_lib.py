@@ -74,6 +74,9 @@ SIGNATURES = {
     "adalog_gemm_out_gen_rows": (i32, [p, i64, i32, p, p, i32, p, i32, i32, i64, p, f32, p, i64, p, i64, p, p, i64, p, p, i64, p]),
     "adalog_attn_core_supported": (i32, [i32, i32]),
     "adalog_attn_core": (i32, [p, p, p, i64, i32, i32, i32, i32, i64, p, p, p, i32, f32, p, p, i32, p, f32, p, p, p, i32, p, p]),
+    "adalog_softmax_adalog_pack_long_bf16": (i32, [p, i64, i32, f32, p, p, i32, p, p, i64, p]),
+    "adalog_attn_core_long_supported": (i32, [i32, i32]),
+    "adalog_attn_core_long": (i32, [p, p, p, i64, i32, i32, i32, i32, i64, p, p, p, i32, f32, p, p, i32, p, f32, p, p]),
     "adalog_gemm_out_gen": (i32, [p, i64, i64, i32, p, p, i64, i32, p, i64, i32, i32, i64, i32, i32, p, i64, f32, p, i64, i64, p, i64, i64,
                             p, i64, i64, p]),
     "adalog_sort_workspace_bytes": (i64, [i64, i64, i32]),

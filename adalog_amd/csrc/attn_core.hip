@@ -191,6 +191,159 @@ __global__ __launch_bounds__(256) void k_attn_core(AttnCoreArgs a) {
     }
 }
 
+// The plain form for rows of up to 1024 keys (a ViT / DeiT at 384 px: 577 tokens).  k_attn_core gives every wavefront one 64-column key
+// block and holds all of v's K chunks in registers, which ends at 256 keys; here a workgroup of LONG_WAVES wavefronts owns one group
+// and 32 query rows, and
+//   1. the wavefronts take the 64-column key blocks in turn (block kb goes to wavefront kb % LONG_WAVES; the next block's fragments of
+//      kp are requested before the current block's MFMAs) and write the fp32 score tile [32][Kp + 4] into LDS: 32 * 1028 * 4 =
+//      131 584 bytes at 1024 keys plus the value table, inside the 160 KiB of a CU;
+//   2. softmax + quantiser, a wavefront per row, NS = 4 / 8 / 16 slots per lane for rows of <= 256 / 512 / 1024 (softmax_adalog.h: the
+//      slot count ATen uses for the row's next power of two), the bf16 row over the head of its own fp32 row as above;
+//   3. wavefront j < ceil(D / 32) multiplies the 32 rows by the 32 channels j of v.  v's fragments come from global memory eight K
+//      chunks (128 keys) at a time, the next eight requested before the MFMAs of the current eight (the first eight before step 2).
+//      The chunks go in ascending order into ONE accumulator chain per output element, as in k_gemm_cand: no split-K, same bits.
+constexpr int LONG_WAVES = 8;
+template <int NS>
+__global__ __launch_bounds__(64 * LONG_WAVES) void k_attn_core_long(AttnCoreArgs a) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const int ld = a.Kp + 4;                                           // floats between the rows of the score tile
+    float* S = reinterpret_cast<float*>(smem);
+    unsigned short* s_lut = reinterpret_cast<unsigned short*>(smem + (size_t)32 * ld * 4);
+
+    const int64_t bid = a.bid0 + blockIdx.x;
+    const int64_t g = bid / a.MT;
+    const int m0 = (int)(bid - g * a.MT) * 32;
+    const int gh = (int)(g % a.gmod), h = (int)(g % a.H);
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int frow = lane & 31, fkg = lane >> 5;
+    const int N = a.N, D = a.D, Kp = a.Kp;
+
+    const float qf = a.qv[0], sc = a.a_scale[0];
+    adalog_value_lut_bf16(s_lut, a.levels2, qf, a.mant);
+
+    // ---- 1. scores: wavefront w takes the key blocks w, w + LONG_WAVES, ..
+    {
+        const int nks = (D + 31) >> 5;                                 // 32-byte K-steps that hold codes
+        const int nkb = (N + 63) >> 6;                                 // key blocks that hold keys
+        const int8_t* kg = a.kp + g * (int64_t)N * 128 + fkg * 16;
+        v4i af[2], bf[2][2];
+        {
+            const int8_t* qr = a.qp + (g * (int64_t)N + min(m0 + frow, N - 1)) * 128 + fkg * 16;
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) af[ks] = ks < nks ? *reinterpret_cast<const v4i*>(qr + ks * 32) : v4i{0, 0, 0, 0};
+        }
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int c = min(w * 64 + j * 32 + frow, N - 1);
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks)
+                bf[j][ks] = (w < nkb && ks < nks) ? *reinterpret_cast<const v4i*>(kg + (int64_t)c * 128 + ks * 32) : v4i{0, 0, 0, 0};
+        }
+        const float alpha = a.sq[gh * a.pg] * 1.0f * a.sk[gh * a.pg];
+        for (int kb = w; kb < nkb; kb += LONG_WAVES) {
+            v4i bn[2][2];
+            const bool more = kb + LONG_WAVES < nkb;
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int c = min((kb + LONG_WAVES) * 64 + j * 32 + frow, N - 1);
+#pragma unroll
+                for (int ks = 0; ks < 2; ++ks)
+                    bn[j][ks] = (more && ks < nks) ? *reinterpret_cast<const v4i*>(kg + (int64_t)c * 128 + ks * 32) : v4i{0, 0, 0, 0};
+            }
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                v16i acc;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[r] = 0;
+                acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(af[0], bf[j][0], acc, 0, 0, 0);
+                if (nks > 1) acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(af[1], bf[j][1], acc, 0, 0, 0);
+                float* sp = S + (4 * fkg) * ld + kb * 64 + j * 32 + frow;       // (columns < Kp: Kp = 64 nkb)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    float s = (float)acc[r] * alpha;
+                    s += 0.0f;
+                    sp[((r & 3) + 8 * (r >> 2)) * ld] = s;
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int ks = 0; ks < 2; ++ks) bf[j][ks] = bn[j][ks];
+        }
+    }
+
+    // ---- 3 (requests): the first eight K chunks of this wavefront's fragments of v
+    const bool pv_live = w * 32 < D;
+    const int nkv = Kp >> 4;
+    const unsigned short* vg = a.vp + (g * D + min(w * 32 + frow, D - 1)) * (int64_t)Kp + fkg * 8;
+    uint4 vf[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) vf[i] = (pv_live && i < nkv) ? *reinterpret_cast<const uint4*>(vg + i * 16) : make_uint4(0, 0, 0, 0);
+    __syncthreads();
+
+    // ---- 2. softmax + quantiser, a wavefront per row; the bf16 row replaces the head of the fp32 row
+    {
+        const float inv_s = __builtin_amdgcn_rcpf(sc), rq37 = 37.0f / qf;
+        const int rows = min(32, N - m0);
+        for (int rl = w; rl < rows; rl += LONG_WAVES) {
+            float* srow = S + rl * ld;
+            float el[NS];
+#pragma unroll
+            for (int it = 0; it < NS; ++it) {
+                const int k = lane + 64 * it;
+                el[it] = k < N ? srow[k] * a.mul : -__builtin_inff();
+            }
+            const float sum = softmax_warp_row(el);
+            unsigned short* prow = reinterpret_cast<unsigned short*>(srow);
+#pragma unroll
+            for (int it = 0; it < NS; ++it) {
+                const int k = lane + 64 * it;
+                if (k >= Kp) break;
+                prow[k] = k < N ? adalog_prob_bf16(el[it], sum, sc, inv_s, qf, rq37, a.levels2, s_lut) : (unsigned short)0;
+            }
+        }
+    }
+    __syncthreads();
+
+    // ---- 3. softmax . v: wavefront w -> the tile's 32 rows x channels [32 w, 32 w + 32)
+    if (pv_live) {
+        v16f acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+        const uint8_t* pa = smem + (size_t)frow * ld * 4 + fkg * 16;
+        for (int k0 = 0; k0 < nkv; k0 += 8) {
+            uint4 vn[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i)
+                vn[i] = k0 + 8 + i < nkv ? *reinterpret_cast<const uint4*>(vg + (k0 + 8 + i) * 16) : make_uint4(0, 0, 0, 0);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                if (k0 + i < nkv) {
+                    const uint4 pf = *reinterpret_cast<const uint4*>(pa + (k0 + i) * 32);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<const v8bf*>(&pf), *reinterpret_cast<const v8bf*>(&vf[i]),
+                                                                  acc, 0, 0, 0);
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < 8; ++i) vf[i] = vn[i];
+        }
+        const float alpha = a.a_scale[0] * a.sa_mul * a.sv[gh * a.pg];
+        const int col = w * 32 + frow;
+        float* og = a.out + ((g / a.H) * (int64_t)N * a.H + h) * D + col;
+        if (col < D) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = m0 + 4 * fkg + (r & 3) + 8 * (r >> 2);
+                if (row < N) {
+                    float o = acc[r] * alpha;
+                    o += 0.0f;
+                    og[(int64_t)row * a.H * D] = o;
+                }
+            }
+        }
+    }
+}
+
 }  // namespace
 
 // the shapes adalog_attn_core takes: 1 <= N <= 256 keys (the bound of adalog_softmax_adalog_pack_bf16), head dimension 16, 32, 48 or 64
@@ -239,5 +392,54 @@ extern "C" int adalog_attn_core(const void* qp, const void* kp, const void* vp, 
     else { if (tm == 2) LAUNCH_ATTN_CORE(2, false); else LAUNCH_ATTN_CORE(1, false); }
 #undef LAUNCH_ATTN_CORE
     ADALOG_LAUNCH_CHECK("adalog_attn_core");
+    return 0;
+}
+
+// the shapes adalog_attn_core_long takes: 1 <= N <= 1024 keys (as far as ATen's per-warp softmax goes), head dimension 16, 32, 48 or 64
+extern "C" int adalog_attn_core_long_supported(int N, int D) {
+    return (N >= 1 && N <= 1024 && (D == 16 || D == 32 || D == 48 || D == 64)) ? 1 : 0;
+}
+
+// The plain form (softmax(scores * mul): ViT / DeiT) of adalog_attn_core for up to 1024 tokens per group; same operands, same bits as
+// gemm_out(I8) -> adalog_softmax_adalog_pack(_long)_bf16 -> gemm_out(BF16, heads_last).  LDS per workgroup: 32 (Np + 4) 4 + 528 bytes.
+extern "C" int adalog_attn_core_long(const void* qp, const void* kp, const void* vp, int64_t G, int N, int D, int H, int gmod, int64_t Np,
+                                     const float* q_scale, const float* k_scale, const float* v_scale, int pg, float mul,
+                                     const float* a_scale, const float* qv, int n_bits, const float* mant37, float sa_mul, float* out,
+                                     void* stream) {
+    ADALOG_ARG_CHECK(qp && kp && vp && q_scale && k_scale && v_scale && a_scale && qv && mant37 && out, "attn_core_long: null pointer");
+    ADALOG_ARG_CHECK(D == 16 || D == 32 || D == 48 || D == 64, "attn_core_long: head dimension D must be 16, 32, 48 or 64");
+    ADALOG_ARG_CHECK(N >= 1 && N <= 1024, "attn_core_long: 1 <= N <= 1024 tokens per group");
+    ADALOG_ARG_CHECK(Np == (int64_t)((N + 63) / 64) * 64, "attn_core_long: Np (rows of vp) must be N rounded up to a multiple of 64");
+    ADALOG_ARG_CHECK(n_bits >= 2 && n_bits <= 7, "attn_core_long: n_bits must be in [2,7]");
+    ADALOG_ARG_CHECK(G >= 1 && H >= 1 && gmod >= 1 && G % H == 0 && G % gmod == 0 && (pg == 0 || pg == 1),
+                     "attn_core_long: G must be a multiple of H and of gmod, pg 0 or 1");
+    ADALOG_ARG_CHECK(((uintptr_t)qp & 15) == 0 && ((uintptr_t)kp & 15) == 0 && ((uintptr_t)vp & 15) == 0,
+                     "attn_core_long: packed operands must be 16-byte aligned");
+    AttnCoreArgs a{};
+    a.qp = (const int8_t*)qp; a.kp = (const int8_t*)kp; a.vp = (const unsigned short*)vp;
+    a.G = G; a.N = N; a.D = D; a.H = H; a.gmod = gmod; a.MT = cdiv(N, 32); a.Kp = (int)Np;
+    a.sq = q_scale; a.sk = k_scale; a.sv = v_scale; a.pg = pg; a.mul = mul;
+    a.a_scale = a_scale; a.qv = qv; a.mant = mant37; a.levels2 = 1 << n_bits; a.sa_mul = sa_mul;
+    a.out = out;
+    const size_t shm = (size_t)32 * (a.Kp + 4) * 4 + 264 * sizeof(unsigned short);
+    const int64_t total = G * a.MT, per_launch = (int64_t)1 << 30;
+    hipStream_t st = (hipStream_t)stream;
+#define LAUNCH_ATTN_CORE_LONG(NSV)                                                                                \
+    do {                                                                                                          \
+        static unsigned long long attr_dev = 0;                                                                   \
+        { hipError_t ea__ = adalog_max_lds(reinterpret_cast<const void*>(&k_attn_core_long<NSV>), (int)(136 * 1024), &attr_dev); \
+          if (ea__ != hipSuccess) { adalog_set_error("hipFuncSetAttribute", ea__); return (int)ea__; } }          \
+        for (int64_t b0 = 0; b0 < total; b0 += per_launch) {                                                      \
+            a.bid0 = b0;                                                                                          \
+            const int64_t nb = total - b0 < per_launch ? total - b0 : per_launch;                                 \
+            hipLaunchKernelGGL((k_attn_core_long<NSV>), dim3((unsigned)nb), dim3(64 * LONG_WAVES), shm, st, a);   \
+        }                                                                                                         \
+    } while (0)
+    adalog_note_kernel("k_attn_core_long");
+    if (N <= 256) LAUNCH_ATTN_CORE_LONG(4);
+    else if (N <= 512) LAUNCH_ATTN_CORE_LONG(8);
+    else LAUNCH_ATTN_CORE_LONG(16);
+#undef LAUNCH_ATTN_CORE_LONG
+    ADALOG_LAUNCH_CHECK("adalog_attn_core_long");
     return 0;
 }

@@ -642,7 +642,9 @@ struct SoftmaxPackArgs {
     const float* mask; int H, nW;                        // BIAS: shift mask [nW][S][S] or null
 };
 constexpr int SM_ROWS = 4;
-template <bool BIAS>
+// NS slots per lane (softmax_adalog.h: 4 for S <= 256, 8 for S <= 512, 16 for S <= 1024), ROWS rows per wavefront: the long-row forms take
+// fewer rows at a time so that the loads in flight stay at 16 per lane
+template <bool BIAS, int NS = 4, int ROWS = SM_ROWS>
 __global__ __launch_bounds__(256) void k_softmax_adalog_pack_t(SoftmaxPackArgs a) {
     __shared__ unsigned short s_lut[258];
     const float qf = a.qv[0], sc = a.scale[0];
@@ -650,31 +652,31 @@ __global__ __launch_bounds__(256) void k_softmax_adalog_pack_t(SoftmaxPackArgs a
     __syncthreads();
     const int lane = threadIdx.x & 63;
     const float inv_s = __builtin_amdgcn_rcpf(sc), rq37 = 37.0f / qf;
-    // a wavefront takes SM_ROWS consecutive rows (the table above is built once per 4 SM_ROWS rows); their loads are issued together
-    const int64_t row0 = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * SM_ROWS;
-    float raw[SM_ROWS][4];
+    // a wavefront takes ROWS consecutive rows (the table above is built once per 4 ROWS rows); their loads are issued together
+    const int64_t row0 = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * ROWS;
+    float raw[ROWS][NS];
 #pragma unroll
-    for (int rr = 0; rr < SM_ROWS; ++rr) {
+    for (int rr = 0; rr < ROWS; ++rr) {
         const bool rv = row0 + rr < a.rows;
         const float* xr = a.x + (rv ? row0 + rr : 0) * a.S;
 #pragma unroll
-        for (int it = 0; it < 4; ++it) {
+        for (int it = 0; it < NS; ++it) {
             const int k = lane + 64 * it;
             raw[rr][it] = (rv && k < a.S) ? xr[k] : 0.0f;
         }
     }
 #pragma unroll
-    for (int rr = 0; rr < SM_ROWS; ++rr) {
+    for (int rr = 0; rr < ROWS; ++rr) {
         const int64_t row = row0 + rr;
         if (row >= a.rows) return;
-        float el[4];
+        float el[NS];
         if constexpr (BIAS) {
             const int64_t g = row / a.S;
             const int r = (int)(row - g * a.S), h = (int)(g % a.H);
             const int64_t* ix = a.index + (int64_t)r * a.S;
             const float* mk = a.mask ? a.mask + ((g / a.H) % a.nW * a.S + r) * a.S : nullptr;
 #pragma unroll
-            for (int it = 0; it < 4; ++it) {
+            for (int it = 0; it < NS; ++it) {
                 const int k = lane + 64 * it;
                 float e = -__builtin_inff();
                 if (k < a.S) {
@@ -685,17 +687,20 @@ __global__ __launch_bounds__(256) void k_softmax_adalog_pack_t(SoftmaxPackArgs a
             }
         } else {
 #pragma unroll
-            for (int it = 0; it < 4; ++it) el[it] = lane + 64 * it < a.S ? raw[rr][it] * a.mul : -__builtin_inff();
+            for (int it = 0; it < NS; ++it) el[it] = lane + 64 * it < a.S ? raw[rr][it] * a.mul : -__builtin_inff();
         }
         const float sum = softmax_warp_row(el);
         unsigned short* orow = a.out + row * a.Kp;
 #pragma unroll
-        for (int it = 0; it < 4; ++it) {
+        for (int it = 0; it < NS; ++it) {
             const int k = lane + 64 * it;
             if (k >= a.Kp) break;
             unsigned short hv = 0;
             if (k < a.S) hv = adalog_prob_bf16(el[it], sum, sc, inv_s, qf, rq37, a.levels2, s_lut);
             orow[k] = hv;
+        }
+        if constexpr (NS > 4) {                                        // a Kp past the slots of this form: zero columns
+            for (int64_t k = lane + 64 * NS; k < a.Kp; k += 64) orow[k] = 0;
         }
     }
 }
@@ -1011,6 +1016,26 @@ extern "C" int adalog_softmax_adalog_pack_bf16(const float* x, int64_t rows, int
     adalog_note_kernel("k_softmax_adalog_pack");
     hipLaunchKernelGGL(k_softmax_adalog_pack_t<false>, dim3((unsigned)((rows + 4 * SM_ROWS - 1) / (4 * SM_ROWS))), dim3(256), 0, (hipStream_t)stream, a);
     ADALOG_LAUNCH_CHECK("adalog_softmax_adalog_pack_bf16");
+    return 0;
+}
+
+// The same for rows of 257 <= S <= 1024 scores (a ViT / DeiT at 384 px: 577 tokens): 8 slots per lane up to 512, 16 up to 1024, which is
+// as far as ATen's per-warp softmax -- the arithmetic this kernel restates -- goes.  Kp: a multiple of 32 elements covering S, <= 1024.
+extern "C" int adalog_softmax_adalog_pack_long_bf16(const float* x, int64_t rows, int S, float mul, const float* scale, const float* qv,
+                                                    int n_bits, const float* mant37, void* out, int64_t Kp, void* stream) {
+    ADALOG_ARG_CHECK(x && scale && qv && mant37 && out, "softmax_adalog_pack_long: null pointer");
+    ADALOG_ARG_CHECK(S >= 257 && S <= 1024 && Kp >= S && Kp <= 1024 && (Kp * 2) % 64 == 0,
+                     "softmax_adalog_pack_long: 257 <= S <= Kp <= 1024, Kp a multiple of 32");
+    ADALOG_ARG_CHECK(n_bits >= 2 && n_bits <= 7, "softmax_adalog_pack_long: n_bits must be in [2,7]");
+    ADALOG_ARG_CHECK(rows >= 0 && rows <= (int64_t)0x7fffffff, "softmax_adalog_pack_long: 0 <= rows < 2^31");
+    if (rows == 0) return 0;
+    SoftmaxPackArgs a{x, rows, S, mul, scale, qv, mant37, 1 << n_bits, reinterpret_cast<unsigned short*>(out), Kp, nullptr, nullptr, nullptr, 1, 1};
+    adalog_note_kernel("k_softmax_adalog_pack_long");
+    if (S <= 512)
+        hipLaunchKernelGGL((k_softmax_adalog_pack_t<false, 8, 2>), dim3((unsigned)((rows + 7) / 8)), dim3(256), 0, (hipStream_t)stream, a);
+    else
+        hipLaunchKernelGGL((k_softmax_adalog_pack_t<false, 16, 1>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a);
+    ADALOG_LAUNCH_CHECK("adalog_softmax_adalog_pack_long_bf16");
     return 0;
 }
 

@@ -1,5 +1,6 @@
 // The row arithmetic of quant_forward's softmax + post-softmax AdaLog quantiser, shared by the kernels that restate it:
-// k_softmax_adalog_pack_t (operand.hip: scores from HBM, packed operand to HBM) and k_attn_core (attn_core.hip: both stay on the chip).
+// k_softmax_adalog_pack_t (operand.hip: scores from HBM, packed operand to HBM) and k_attn_core / k_attn_core_long (attn_core.hip:
+// both stay on the chip).
 // One definition, so that the two routes quantise the same fp32 probabilities bit for bit.
 #pragma once
 #include "common.h"
@@ -19,15 +20,20 @@ __device__ __forceinline__ void adalog_value_lut_bf16(unsigned short* s_lut, int
 // ATen's softmax_warp_forward over one row held by a wavefront, operation for operation: element k = lane + 64 it in el[it]
 // (-inf where k is past the row); max over `it`, then the xor butterfly 32, 16, .., 1; el[it] = exp(el[it] - max) summed per lane in
 // `it` order, then the same butterfly.  Returns the sum; the probabilities are el[it] / sum.
-__device__ __forceinline__ float softmax_warp_row(float (&el)[4]) {
+// NS slots per lane: 4 (rows of <= 256), 8 (<= 512) or 16 (<= 1024) -- ATen's WARP_ITERATIONS for the row's next power of two.  ATen keeps
+// this per-warp form up to 1024 elements per row; past that it switches to a block-wide softmax with another summation order, so
+// 1024 is where the restatement ends.  A row shorter than 64 (NS - 1) + 1 only adds exact zeros (exp(-inf)) to the ATen order.
+template <int NS>
+__device__ __forceinline__ float softmax_warp_row(float (&el)[NS]) {
+    static_assert(NS == 4 || NS == 8 || NS == 16, "softmax_warp_row: 4, 8 or 16 slots per lane");
     float mx = el[0];
 #pragma unroll
-    for (int it = 1; it < 4; ++it) mx = mx < el[it] ? el[it] : mx;
+    for (int it = 1; it < NS; ++it) mx = mx < el[it] ? el[it] : mx;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) { const float b = __shfl_xor(mx, o); mx = mx < b ? b : mx; }
     float sum = 0.0f;
 #pragma unroll
-    for (int it = 0; it < 4; ++it) { el[it] = expf(el[it] - mx); sum += el[it]; }
+    for (int it = 0; it < NS; ++it) { el[it] = expf(el[it] - mx); sum += el[it]; }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) sum = sum + __shfl_xor(sum, o);
     return sum;

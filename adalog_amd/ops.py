@@ -725,6 +725,58 @@ def attn_core(qp, kp, vp, N: int, D: int, H: int, gmod: int, sA, sB, sV, mul: fl
     return out
 
 
+# Capability flag of the long-row fused route (utils/models.py: QF_LONG), read like QF_EXTRAS: softmax_adalog_pack_long(_ok),
+# attn_core_long(_ok) -- 257 to 1024 tokens per attention group.  The CPU specification backend of the tests does not have it.
+QF_LONG = True
+
+
+def softmax_adalog_pack_long_ok(S: int) -> bool:
+    """rows of 257 .. 1024 scores: as far as ATen's per-warp softmax, whose arithmetic the kernel restates, goes"""
+    return 256 < S <= 1024 and pad_k(S, BF16) <= 1024
+
+
+def softmax_adalog_pack_long(x3, mul: float, scale, qv, n_bits: int, mant37):
+    """softmax_adalog_pack for rows of 257 <= S <= 1024 scores (adalog_softmax_adalog_pack_long_bf16): x3 fp32 [G, R, S] contiguous ->
+    the packed bf16 operand [1, G, R, Kp] of softmax . v, the same bits as pack_adalog of (x3 * mul).softmax(-1)."""
+    x3 = _f32c(x3, "scores")
+    G, R, S = x3.shape
+    Kp = pad_k(S, BF16)
+    out = torch.empty((1, G, R, Kp), dtype=torch.bfloat16, device=x3.device)
+    rc = _lib.load().adalog_softmax_adalog_pack_long_bf16(x3.data_ptr(), G * R, S, float(mul), _ptr(_f32c(scale, "scale")),
+                                                         _ptr(_f32c(qv, "qv")), int(n_bits), _ptr(_f32c(mant37, "mant37")),
+                                                         out.data_ptr(), Kp, _stream())
+    _lib.check(rc, "adalog_softmax_adalog_pack_long_bf16")
+    out.k_valid = S
+    return out
+
+
+def attn_core_long_ok(N: int, D: int) -> bool:
+    """attn_core_long takes N tokens per group (<= 1024) and head dimension D (16, 32, 48 or 64)"""
+    return bool(_lib.load().adalog_attn_core_long_supported(int(N), int(D)))
+
+
+def attn_core_long(qp, kp, vp, N: int, D: int, H: int, gmod: int, sA, sB, sV, mul: float, a_scale, qv, n_bits: int, mant37,
+                   sa_mul: float = 1.0):
+    """The plain form of attn_core for up to 1024 tokens per group (adalog_attn_core_long): fp32 [B, N, H, D], bit-identical to
+        gemm_out(I8, qp, kp) -> softmax_adalog_pack(_long)(., mul) -> gemm_out(BF16, ., vp, heads_last=H)
+    with the 32-row score tile in LDS.  Arguments as attn_core's (no table, index or mask: ViT / DeiT only)."""
+    G = qp.shape[1]
+    assert qp.dtype == torch.int8 and kp.dtype == torch.int8 and vp.dtype == torch.bfloat16
+    assert qp.is_cuda and qp.is_contiguous() and kp.is_contiguous() and vp.is_contiguous()
+    assert qp.shape[-2:] == (N, 128) and kp.shape == qp.shape and vp.shape[1] == G and vp.shape[2] == D and G % H == 0
+    Np = vp.shape[-1]
+    sA, sB, sV = (_f32c(t, "scale").reshape(-1) for t in (sA, sB, sV))
+    assert sA.numel() == sB.numel() == sV.numel() and sA.numel() in (1, gmod)
+    pg = 0 if sA.numel() == 1 else 1
+    out = torch.empty((G // H, N, H, D), dtype=torch.float32, device=qp.device)
+    rc = _lib.load().adalog_attn_core_long(qp.data_ptr(), kp.data_ptr(), vp.data_ptr(), G, int(N), int(D), int(H), int(gmod), Np,
+                                           sA.data_ptr(), sB.data_ptr(), sV.data_ptr(), pg, float(mul), _ptr(_f32c(a_scale, "scale")),
+                                           _ptr(_f32c(qv, "qv")), int(n_bits), _ptr(_f32c(mant37, "mant37")), float(sa_mul),
+                                           out.data_ptr(), _stream())
+    _lib.check(rc, "adalog_attn_core_long")
+    return out
+
+
 def gemm_out_gen_rows(x2, a_scale, a_zp, n_bits: int, B, N: int, sa: Strided, sb: Strided, bias: Optional[Strided],
                       a_rows=None, o_rows=None, period: int = 1, addend=None, sa_mul: float = 1.0):
     """gemm_out_gen of one group (x2 fp32 [M, K], per-tensor quantiser) with rows remapped in periods of L = ``period`` rows

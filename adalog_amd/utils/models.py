@@ -31,6 +31,10 @@ QF_FUSED = os.environ.get("ADALOG_QF_FUSED", "1") != "0"
 # ... with the attention core of the fused route (q . k^T, softmax + AdaLog quantiser, softmax . v) as ONE launch (ops.attn_core)
 # instead of three: 9 launches per block instead of 11, same bits.  Opt-in: 1 = on
 QF_ATTN_CORE = os.environ.get("ADALOG_QF_ATTN_CORE", "0") == "1"
+# ... for ViT / DeiT sequences of 257 to 1024 tokens per image (384 px: 577) and head dimensions 16, 32 and 48 as well: the same 11
+# (with QF_ATTN_CORE: 9) launches through the long-row softmax pack / attention core (ops.softmax_adalog_pack_long, ops.attn_core_long),
+# same bits.  Off: such a block takes the module route, as it always has.  Opt-in: 1 = on
+QF_LONG = os.environ.get("ADALOG_QF_LONG", "0") == "1"
 
 
 def _attn_core_on(be, N, D):
@@ -100,12 +104,13 @@ class Attention(nn.Module):
 
     def _fused_quant_forward_ok(self, x):
         """quant_forward of the whole block on the fused route (below): every quantised module of the block is in plain
-        quant_forward mode with the input quantisers the packers implement, head dimension 64, <= 256 tokens."""
+        quant_forward mode with the input quantisers the packers implement, head dimension 64, <= 256 tokens -- with QF_LONG, head
+        dimension 16, 32, 48 or 64 and up to 1024 tokens."""
         from ..quant_layers.matmul import AsymmetricallyBatchingQuantMatMul, PostSoftmaxAsymmetricallyBatchingQuantMatMul
         from ..quantizers.uniform import UniformQuantizer
         m1, m2 = self.matmul1, self.matmul2
-        if not (QF_FUSED and not torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32 and self.head_dim == 64
-                and x.shape[1] <= 256 and isinstance(self.q_norm, nn.Identity) and isinstance(self.k_norm, nn.Identity)
+        if not (QF_FUSED and not torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32
+                and self._fused_shape_ok(x.shape[1]) and isinstance(self.q_norm, nn.Identity) and isinstance(self.k_norm, nn.Identity)
                 and isinstance(self.attn_drop, nn.Identity) and isinstance(self.proj_drop, nn.Identity)):
             return False
         if not (type(m1) is AsymmetricallyBatchingQuantMatMul and type(m2) is PostSoftmaxAsymmetricallyBatchingQuantMatMul
@@ -115,6 +120,16 @@ class Attention(nn.Module):
         return (all(isinstance(q, UniformQuantizer) and 2 <= q.n_bits <= 7 and not q.training_mode for q in qs)
                 and not m2.A_quantizer.training_mode and m1._heads() == m2._heads() and m2.A_quantizer.scale.numel() == 1
                 and getattr(_backend.get(), "QF_EXTRAS", False) and m1.packed_codes_fit() and m2.packed_codes_fit())
+
+    def _fused_shape_ok(self, tokens):
+        """head dimension 64 and <= 256 tokens; with QF_LONG on and a backend that has the long-row kernels, head dimension 16, 32, 48
+        or 64 and every token count up to 1024 that its softmax packers take"""
+        if self.head_dim == 64 and tokens <= 256:
+            return True
+        if not (QF_LONG and self.head_dim in (16, 32, 48, 64)):
+            return False
+        be = _backend.get()
+        return getattr(be, "QF_LONG", False) and (tokens <= 256 or be.softmax_adalog_pack_long_ok(tokens))
 
     def _fused_quant_forward(self, x, residual):
         """The attention block in quant_forward mode (reference utils/wrap_net.py:19-32 with every product in quant_forward,
@@ -132,18 +147,29 @@ class Attention(nn.Module):
         sA, zA = m1._q_params(m1.A_quantizer)
         sB, zB = m1._q_params(m1.B_quantizer)
         sV, zV = m2._q_params(m2.B_quantizer)
-        qp, kp, vp = be.attn_split_pack(qkv, H, (sA, zA, m1.A_quantizer.n_bits), (sB, zB, m1.B_quantizer.n_bits),
-                                        (sV, zV, m2.B_quantizer.n_bits), hm > 1)
+        long_rows = N > 256                                              # (only behind QF_LONG: _fused_shape_ok)
+        if self.head_dim == 64:
+            qp, kp, vp = be.attn_split_pack(qkv, H, (sA, zA, m1.A_quantizer.n_bits), (sB, zB, m1.B_quantizer.n_bits),
+                                            (sV, zV, m2.B_quantizer.n_bits), hm > 1)
+        else:                                                            # (QF_LONG) the scale stays behind the product: no q_mul
+            qp, kp, vp = be.attn_split_pack_ex(qkv, H, (sA, zA, m1.A_quantizer.n_bits), (sB, zB, m1.B_quantizer.n_bits),
+                                               (sV, zV, m2.B_quantizer.n_bits), hm > 1, D=self.head_dim)
         if m2._q_host is None:
             m2._q_host = int(m2.A_quantizer.q.item())
         qv = _search.const_tensor([float(m2._q_host)], x.device)
         a_scale = m2.A_quantizer.scale.data.view(-1)
-        if _attn_core_on(be, N, self.head_dim):
+        if long_rows:
+            if QF_ATTN_CORE and getattr(be, "QF_ATTN_CORE", False) and be.attn_core_long_ok(N, self.head_dim):
+                out = be.attn_core_long(qp, kp, vp, N, self.head_dim, H, hm, sA, sB, sV, self.scale, a_scale, qv,
+                                        m2.A_quantizer.n_bits, m2._mant37(x.device), m2._ts32())
+                return self.proj.quant_forward(out.view(B, N, C), addend=residual)
+        elif _attn_core_on(be, N, self.head_dim):
             out = be.attn_core(qp, kp, vp, N, self.head_dim, H, hm, sA, sB, sV, self.scale, a_scale, qv, m2.A_quantizer.n_bits,
                                m2._mant37(x.device), m2._ts32())
             return self.proj.quant_forward(out.view(B, N, C), addend=residual)
         scores = be.gemm_out(I8, qp, kp, N, N, B * H, hm, Strided(sA, g=pg), Strided(sB, g=pg), None)
-        ap = be.softmax_adalog_pack(scores, self.scale, a_scale, qv, m2.A_quantizer.n_bits, m2._mant37(x.device))
+        soft = be.softmax_adalog_pack_long if long_rows else be.softmax_adalog_pack
+        ap = soft(scores, self.scale, a_scale, qv, m2.A_quantizer.n_bits, m2._mant37(x.device))
         out = be.gemm_out(BF16, ap, vp, N, self.head_dim, B * H, hm, Strided(a_scale), Strided(sV, g=pg), None, sa_mul=m2._ts32(),
                           heads_last=H)
         return self.proj.quant_forward(out.view(B, N, C), addend=residual)

@@ -474,6 +474,23 @@ int adalog_attn_core(const void* qp, const void* kp, const void* vp, int64_t G, 
                      const float* qv, int n_bits, const float* mant37, float sa_mul, const float* table, const int64_t* index,
                      const float* mask, int nW, float* out, void* stream);
 
+/* ---- the same two steps for rows of up to 1024 tokens (a ViT / DeiT at 384 px: 577), behind ADALOG_QF_LONG=1 in the models.  1024 is
+ * where ATen's per-warp softmax -- the arithmetic these kernels restate, 8 slots per lane up to 512 elements and 16 up to 1024 -- ends.
+ * adalog_softmax_adalog_pack_long_bf16: adalog_softmax_adalog_pack_bf16 for 257 <= S <= Kp <= 1024 (Kp a multiple of 32); same bits as
+ *   torch's softmax of x * mul followed by adalog_pack_adalog_bf16.
+ * adalog_attn_core_long: the plain form of adalog_attn_core (softmax(scores * mul); no bias, no mask) for 1 <= N <= 1024, D in {16, 32,
+ *   48, 64}; every other argument as there.  A workgroup owns one group and 32 query rows; its fp32 score tile [32][Np + 4] lives in
+ *   LDS (at most 132 112 bytes with the value table); v's K chunks stream in ascending order into one accumulator chain per output
+ *   element, so the result equals adalog_gemm_score(int8) ; adalog_softmax_adalog_pack(_long)_bf16 ; adalog_gemm_out_ex(bf16, out_gi =
+ *   H) bit for bit.
+ * adalog_attn_core_long_supported: 1 when adalog_attn_core_long takes N tokens per group and head dimension D. */
+int adalog_softmax_adalog_pack_long_bf16(const float* x, int64_t rows, int S, float mul, const float* scale, const float* qv, int n_bits,
+                                         const float* mant37, void* out, int64_t Kp, void* stream);
+int adalog_attn_core_long_supported(int N, int D);
+int adalog_attn_core_long(const void* qp, const void* kp, const void* vp, int64_t G, int N, int D, int H, int gmod, int64_t Np,
+                          const float* q_scale, const float* k_scale, const float* v_scale, int pg, float mul, const float* a_scale,
+                          const float* qv, int n_bits, const float* mant37, float sa_mul, float* out, void* stream);
+
 /* ---- stable LSD radix sort of fp32 keys, per segment (csrc/radix_sort.hip; hipCUB until round 5): what the sorted forms above and
  * adalog_gram_act_prepare sort with.  x [S][n] contiguous -> sorted [S][n] (ascending per segment; -0 before +0), perm (may be null)
  * [S][n]: perm[s][i] = index within segment s of its i-th smallest value, equal values in input order.  n <= 8192: one launch (a
