@@ -128,6 +128,7 @@ SIGNATURES = {
                               p, i64, p]),
     "adalog_gemm_score_avq_ok": (i32, [i32, i32, i32, i32, i32, i64, i64, i32]),
     "adalog_gemm_mixed_ok": (i32, [i32, i32, i32, i32, i32, i64]),
+    "adalog_gemm_mixed_ktrim": (i32, [i32, i32, i32, i32, i32, i64]),
     "adalog_rec_loss": (i32, [p, p, i64, f32, p, p, p]),
     "adalog_rec_loss_backward": (i32, [p, p, i64, f32, p, p, p]),
     "adalog_brecq_init": (i32, []),

@@ -644,6 +644,224 @@ __global__ __launch_bounds__(512, 2) void k_gemm_grpk8(GemmArgs p) {
 }
 
 
+// Trimmed-K form of k_gemm_grpk8 (K <= 208: the 197 keys of a 224 x 224 ViT): rows of 13 sixteen-element slots instead of four
+// 64-element K-steps -- fp8 candidate columns of Kb = 208 bytes, bf16 rows of KbA = 416 bytes -- so neither the packer, the
+// L2 -> LDS path nor the matrix pipe touches the 48 all-zero K positions 208..255, and the MFMAs that only multiply zeros go.
+//   * NKS MFMAs per 32 x 32 block, MFMA i with the operands of k_gemm_grpk8's MFMA i (kt = i / 4, m = i % 4), in the same
+//     order: for K half fkg it covers K = 32 (i >> 1) + 16 fkg + 8 (i & 1) + 0..7.  MFMAs 0..11 cover K < 192; MFMA 12 covers
+//     192..199 (fkg 0) and 208..215 (fkg 1: past the row, zeros in registers); MFMA 13 covers 200..207 and 216..223 (zeros).
+//     So NKS = 13 holds every non-zero product of K <= 200 and NKS = 14 of K <= 208; the MFMAs left out multiply zeros by
+//     zeros in k_gemm_grpk8 (an accumulator keeps its value; at most a zero changes sign, which d * d erases), and the
+//     scores are bit-identical.  Epilogue, per-lane fp32 sums, wave order and the wg_acc layout are k_gemm_grpk8's.
+//   * a 32-column block is one contiguous 6 656-byte run and a stage of SB = 4 blocks 26 624 bytes = 26 linear LDS-DMA requests
+//     (64 lanes x 16 bytes); the LDS image equals the memory image.  The column stride is 13 slots -- odd, so the 32 columns
+//     of a ds_read_b128 spread over the banks without a swizzle.  Lane (column, fkg) reads slots 2 pr + fkg, pr = 0..6
+//     (slot 13 does not exist: zero).
+//   * consumer w issues requests 3 w .. 3 w + 2, the loader wave requests 21..25.
+template <int NJ, int NKS>
+__global__ __launch_bounds__(512, 2) void k_gemm_grpk8t(GemmArgs p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    constexpr int NSL = 13, CBY = NSL * 16;                    // 16-byte slots / bytes of a column
+    constexpr int NPR = (NKS + 1) / 2;                         // slot pairs (fkg 0 | fkg 1) = fragment reads per block and lane
+    constexpr int NSG = 3, SB = 4, SBYTES = SB * 32 * CBY;     // ring stages, blocks per stage, bytes per stage
+    constexpr int RQ = SBYTES / 1024, CQ = 3, LQ = RQ - 7 * CQ; // requests per stage / per consumer / of the loader
+    constexpr int STG = NJ / SB > 0 ? NJ / SB : 1;             // stages per reference column
+    constexpr int P = NJ * 32;
+    static_assert(NKS == 13 || NKS == 14, "13 slots: MFMAs 12 and 13 are the last that can hold data");
+    static_assert(SBYTES % 1024 == 0 && RQ == 26 && LQ == 5, "a stage is 26 whole requests: 7 x 3 + 5 for the loader");
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    uint8_t* ring = lds;                                                        // [NSG][128 columns][208 bytes]
+    float* red = reinterpret_cast<float*>(lds + NSG * SBYTES);                  // [7 waves][P]
+    double* accl = reinterpret_cast<double*>(lds + NSG * SBYTES + 7 * P * 4);   // [gmod][256]
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int frow = lane & 31, fkg = lane >> 5;
+    const int KbA = (int)p.KbA;
+    const int NB = p.N >> 5;
+    const int CB = p.slab_R, NCH = p.slab_U;
+    const int items = p.G * NCH;
+    const int n_eff = p.N / P;
+    for (int i = tid; i < p.gmod * 256; i += 512) accl[i] = 0.0;
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+
+    int li = blockIdx.x, lst = 0, slot = 0, ahead = 0;
+    auto stages_of = [&](int item) { const int c = item % NCH; return (min(CB, NB - c * CB) + SB - 1) / SB; };
+    auto issue = [&]() {
+        const int g = li / NCH, c = li - g * NCH;
+        const int col0 = (c * CB + lst * SB) * 32;
+        const int64_t left = (int64_t)(p.N - col0) * CBY;      // bytes of the group from this stage on: past them a request reads zeros
+        const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc((void*)(p.B + (int64_t)g * p.sBg + (int64_t)col0 * CBY), 0,
+                                                                            (int)(left < 0 ? 0 : min(left, (int64_t)0x7ffffffe)), 0x00020000);
+        uint8_t* st = ring + slot * SBYTES;
+        // request r: bytes 1024 r .. + 1023 of the stage (the whole offset in the VGPR: it is what the range check sees)
+        if (w == 7) {
+#pragma unroll
+            for (int r = 7 * CQ; r < RQ; ++r) STREAM_DMA(rb, st + r * 1024, r * 1024 + lane * 16, 0);
+        } else {
+#pragma unroll
+            for (int i = 0; i < CQ; ++i) {
+                const int r = w * CQ + i;
+                STREAM_DMA(rb, st + r * 1024, r * 1024 + lane * 16, 0);
+            }
+        }
+        slot = slot == NSG - 1 ? 0 : slot + 1;
+        if (++lst == stages_of(li)) { lst = 0; li += gridDim.x; }
+        ++ahead;
+    };
+    if (li < items) issue();
+    if (li < items) issue();
+
+    if (w == 7) {
+        for (int item = blockIdx.x; item < items; item += gridDim.x) {
+            const int ns = stages_of(item);
+            for (int t = 0; t < ns; ++t) {
+                if (ahead >= 2) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(LQ) : "memory");   // the following stage's LQ may be in flight
+                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                asm volatile("s_barrier" ::: "memory");
+                --ahead;
+                if (li < items) issue();
+            }
+            asm volatile("s_barrier" ::: "memory");
+        }
+    } else {
+        const int row0 = w * 32;
+        const bool rowblock_live = row0 < p.M;
+        int st = 0;
+        for (int item = blockIdx.x; item < items; item += gridDim.x) {
+            const int g = item / NCH, c = item - g * NCH, gh = g % p.gmod;
+            const int blk0 = c * CB, nblk = min(CB, NB - blk0), ns = (nblk + SB - 1) / SB;
+            uint4 af[NKS];
+            {
+                const bool ok = row0 + frow < p.M;
+                const uint8_t* ar = p.A + (int64_t)g * p.sAg + (int64_t)min(row0 + frow, p.M - 1) * KbA;
+#pragma unroll
+                for (int i = 0; i < NKS; ++i) {
+                    const bool past = (i >> 1) == 6 && fkg == 1;              // K 208..: past the row
+                    af[i] = *reinterpret_cast<const uint4*>(ar + (past ? 0 : (i >> 1) * 64 + fkg * 32) + (i & 1) * 16);
+                    if (!ok || past) af[i] = make_uint4(0, 0, 0, 0);
+                }
+            }
+            float nal[NJ];
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) {
+                const int ci = j * 32 + frow;
+                nal[j] = -(p.sa[ci * p.sa_c + gh * p.sa_g] * p.sa_mul * p.sb[ci * p.sb_c + gh * p.sb_g]);
+            }
+            const uint32_t ref_bytes = (uint32_t)(((int64_t)(n_eff - 1) * p.ref_cs + p.M) * 4);
+            const __amdgpu_buffer_rsrc_t rrg = __builtin_amdgcn_make_buffer_rsrc((void*)(p.ref + (int64_t)g * p.sRg), 0, (int)ref_bytes, 0x00020000);
+            const bool full_rows = row0 + 32 <= p.M;
+            int roff[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) roff[q] = min(row0 + 8 * q + 4 * fkg, p.M - 4) * 4;
+            v2f cs2[NJ];
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) cs2[j] = (v2f){0.0f, 0.0f};
+            auto run = [&](auto full_tag) {
+                constexpr bool FULL = decltype(full_tag)::value;
+                auto load_ref = [&](int n, float4 (&r)[4]) {
+                    const int coff = n < n_eff ? n * (int)p.ref_cs * 4 : 0x7ffffff0;
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const v4u uu = __builtin_amdgcn_raw_buffer_load_b128(rrg, roff[q], coff, 0);
+                        r[q] = make_float4(__uint_as_float(uu.x), __uint_as_float(uu.y), __uint_as_float(uu.z), __uint_as_float(uu.w));
+                    }
+                };
+                auto fix_ref = [&](float4 (&r)[4]) {
+                    if (FULL) return;
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const int rr = row0 + 8 * q + 4 * fkg;
+                        const float4 u = r[q];
+                        const int sh = rr * 4 - roff[q];
+                        const float e0 = sh == 0 ? u.x : sh == 4 ? u.y : sh == 8 ? u.z : u.w;
+                        const float e1 = sh == 0 ? u.y : sh == 4 ? u.z : u.w;
+                        const float e2 = sh == 0 ? u.z : u.w;
+                        r[q] = make_float4(rr < p.M ? e0 : 0.f, rr + 1 < p.M ? e1 : 0.f, rr + 2 < p.M ? e2 : 0.f, rr + 3 < p.M ? u.w : 0.f);
+                    }
+                };
+                int n = blk0 / NJ;
+                float4 rc[4], rn[4];                           // current / next reference column
+                load_ref(n, rc);
+                load_ref(n + 1, rn);
+                fix_ref(rc);
+                const int foff = frow * CBY + fkg * 16;        // this lane's slot 0 / 1 of column frow
+                for (int tg = 0; tg < ns; tg += STG) {
+#pragma unroll
+                    for (int s = 0; s < STG; ++s) {
+                        // behind this wave's CQ requests of the stage: the next stage's CQ and the reference loads of the two stages in
+                        // between (a stage is 4 blocks: at least 16 / 8 / 4 loads for NJ = 2 / 4 / 8)
+                        constexpr int BEHIND = CQ + (NJ == 2 ? 16 : NJ == 4 ? 8 : 4);
+                        static_assert(BEHIND == (NJ == 2 ? 19 : NJ == 4 ? 11 : 7) && BEHIND < 64, "counted vmcnt of the consumers");
+                        if ((tg == 0 && s == 0) || ahead < 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                        else asm volatile("s_waitcnt vmcnt(%0)" :: "n"(BEHIND) : "memory");
+                        asm volatile("s_barrier" ::: "memory");
+                        --ahead;
+                        if (li < items) issue();
+                        const uint8_t* cur = ring + st * SBYTES;
+#pragma unroll
+                        for (int b = 0; b < SB; ++b) {
+                            const int j = (s * SB + b) % NJ;
+                            v16f acc;
+#pragma unroll
+                            for (int pr = 0; pr < NPR; ++pr) {
+                                // the last pair's fkg 1 slot would be slot 13: read slot 12 (in range) and drop it
+                                uint4 bq = lds_frag(cur, b * (32 * CBY) + foff + (pr == 6 ? 12 * 16 - fkg * 16 : pr * 32));
+                                if (pr == 6 && fkg == 1) bq = make_uint4(0, 0, 0, 0);
+                                uint4 lo, hi;
+                                fp8x16_bf16(bq, lo, hi);
+                                if (pr == 0) acc = mma0<1>(af[0], lo); else mma<1>(af[2 * pr], lo, acc);
+                                if (2 * pr + 1 < NKS) mma<1>(af[2 * pr + 1], hi, acc);
+                            }
+                            const v2f na = {nal[j], nal[j]};
+#pragma unroll
+                            for (int q = 0; q < 4; ++q) {
+                                const v2f tA = {acc[q * 4 + 0], acc[q * 4 + 1]}, tB = {acc[q * 4 + 2], acc[q * 4 + 3]};
+                                const v2f rA = {rc[q].x, rc[q].y}, rB = {rc[q].z, rc[q].w};
+                                const v2f dA = tA * na + rA, dB = tB * na + rB;
+                                cs2[j] += dA * dA; cs2[j] += dB * dB;
+                            }
+                            if (j == NJ - 1) {                 // next block starts the next reference column
+                                ++n;
+#pragma unroll
+                                for (int q = 0; q < 4; ++q) rc[q] = rn[q];
+                                fix_ref(rc);
+                                load_ref(n + 1, rn);
+                            }
+                        }
+                        st = st == NSG - 1 ? 0 : st + 1;
+                    }
+                }
+            };
+            if (!rowblock_live) {
+                for (int t = 0; t < ns; ++t) {
+                    asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
+                    --ahead;
+                    if (li < items) issue();
+                    st = st == NSG - 1 ? 0 : st + 1;
+                }
+            } else if (full_rows) run(std::true_type{});
+            else run(std::false_type{});
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) {
+                float cs = cs2[j].x + cs2[j].y;
+                cs += __shfl_xor(cs, 32);
+                if (fkg == 0) red[w * P + j * 32 + frow] = cs;
+            }
+            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+            if (tid < P) {
+                double v = 0.0;
+                const int nw = min(7, (p.M + 31) / 32);
+                for (int ww = 0; ww < nw; ++ww) v += (double)red[ww * P + tid];
+                accl[gh * 256 + tid] += v;
+            }
+        }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    for (int i = tid; i < p.gmod * 256; i += 512) p.wg_acc[(int64_t)blockIdx.x * p.gmod * 256 + i] = accl[i];
+#endif
+}
+
+
 // GEN forms of the window / wave-private group kernels (round 4; uniform attention candidates, reference matmul.py:135-201): the
 // candidate operand of a q.k^T search is P quantisations of the same [rows][K] fp32 tensor -- 1.1 GB packed and read back per
 // launch for swin stage 0, where the window kernel is bound by exactly that stream.  Here a lane builds its MFMA operand fragment

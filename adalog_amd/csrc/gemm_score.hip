@@ -203,6 +203,12 @@ static bool grpk8_ok(int M, int N, int G, int gmod, int ref_div, int64_t k_valid
            (int64_t)(N / ref_div) * ref_cs * 4 < ((int64_t)1 << 31);
 }
 
+// ... and of the trimmed-K form of the mixed kernel (k_gemm_grpk8t): rows of 208 elements, K = 193..208
+static bool grpk8t_ok(int M, int N, int G, int gmod, int ref_div, int64_t k_valid, const float* bias, const float* row_scale,
+                      int64_t sb_n, int64_t ref_cs) {
+    return k_valid <= 208 && grpk8_ok(M, N, G, gmod, ref_div, k_valid, bias, row_scale, sb_n, ref_cs);
+}
+
 // ... mixed operands, window family: K <= 64 elements (one 64-byte fp8 K-step against 128-byte bf16 rows), at most 64 rows.
 static bool winb_ok(int M, int N, int G, int gmod, int ref_div, int64_t k_valid, const float* bias, const float* row_scale, int64_t sb_n,
                     int64_t ref_cs, int wgs) {
@@ -264,6 +270,13 @@ extern "C" int adalog_gemm_mixed_ok(int M, int N, int G, int gmod, int ref_div, 
     if (!(L.stream && L.acc)) return 0;
     if (k_valid <= 64) return winb_ok(M, N, G, gmod, ref_div, k_valid, nullptr, nullptr, 0, M, L.wgs) ? 1 : 0;
     return grpk8_ok(M, N, G, gmod, ref_div, k_valid, nullptr, nullptr, 0, M) ? 1 : 0;
+}
+
+// Row length (elements) of the trimmed-K form of the mixed 197-token family, or 0 when the shape is not taken by it (then Kp = 256 as
+// adalog_gemm_mixed_ok describes): both operands may be packed with rows of 208 elements (13 sixteen-element slots) for K = 193..208.
+extern "C" int adalog_gemm_mixed_ktrim(int M, int N, int G, int gmod, int ref_div, int64_t k_valid) {
+    if (k_valid <= 64 || k_valid > 208 || !adalog_gemm_mixed_ok(M, N, G, gmod, ref_div, k_valid)) return 0;
+    return grpk8t_ok(M, N, G, gmod, ref_div, k_valid, nullptr, nullptr, 0, M) ? 208 : 0;
 }
 
 // GEN form of the attention searches (adalog_gemm_score_gen): the candidate operand B is not read but generated in the kernel
@@ -335,9 +348,10 @@ static int gemm_score_impl(int dtype, const void* A, const void* B, int64_t sAc,
     if (dtype == 4) {
         // mixed operands: one kernel, one shape family (adalog_gemm_mixed_ok)
         const bool window = k_valid > 0 && k_valid <= 64;
-        ADALOG_ARG_CHECK(Kp == (window ? 64 : 256) && k_valid > 0 && C == 1 && partial && ref && !out && ldr == 1 && reduce_cols == 1 &&
+        const bool ktrim = !window && Kp == 208 && grpk8t_ok(M, N, G, gmod, ref_div, k_valid, bias, row_scale, sb_n, ref_cs);
+        ADALOG_ARG_CHECK((Kp == (window ? 64 : 256) || ktrim) && k_valid > 0 && C == 1 && partial && ref && !out && ldr == 1 && reduce_cols == 1 &&
                          adalog_gemm_mixed_ok(M, N, G, gmod, ref_div, k_valid),
-                         "gemm_score: bf16 x fp8 operands are taken for the shapes adalog_gemm_mixed_ok accepts only (Kp = 64 or 256, C = 1, transposed reference)");
+                         "gemm_score: bf16 x fp8 operands are taken for the shapes adalog_gemm_mixed_ok accepts only (Kp = 64 or 256, or 208 where adalog_gemm_mixed_ktrim says so; C = 1, transposed reference)");
         const Layout L = layout_of(M, N, C, G, gmod, ref_div, reduce_cols, true, k_valid * 2, Kp * 2, true, 1);
         ADALOG_ARG_CHECK(window ? winb_ok(M, N, G, gmod, ref_div, k_valid, bias, row_scale, sb_n, ref_cs, L.wgs)
                                 : grpk8_ok(M, N, G, gmod, ref_div, k_valid, bias, row_scale, sb_n, ref_cs),
@@ -374,6 +388,24 @@ static int gemm_score_impl(int dtype, const void* A, const void* B, int64_t sAc,
         const int nch0 = cdiv((int64_t)3 * L.wgs, G);
         const int CB = cdiv(cdiv(NB, nch0 < 1 ? 1 : nch0), 8) * 8;
         p.slab_R = CB; p.slab_U = cdiv(NB, CB);
+        if (ktrim) {
+            // rows of 13 sixteen-element slots: 13 MFMAs per block hold every non-zero product of K <= 200, 14 of K <= 208
+            const size_t shm_t = (size_t)3 * 4 * 32 * 208 + (size_t)7 * ref_div * 4 + (size_t)gmod * 256 * 8;   // 3 stages of 4 blocks x 208 bytes
+#define LAUNCH_GRPK8T(NJV, NKSV)                                                                                  \
+            do {                                                                                                  \
+                static unsigned long long attr_dev = 0; \
+                { hipError_t ea__ = adalog_max_lds(reinterpret_cast<const void*>(&k_gemm_grpk8t<NJV, NKSV>), (int)(160 * 1024), &attr_dev); \
+                  if (ea__ != hipSuccess) { adalog_set_error("hipFuncSetAttribute", ea__); return (int)ea__; } } \
+                adalog_note_kernel(NKSV == 13 ? "k_gemm_grpk8t<13,bf16xfp8>" : "k_gemm_grpk8t<14,bf16xfp8>");     \
+                hipLaunchKernelGGL((k_gemm_grpk8t<NJV, NKSV>), dim3((unsigned)L.wgs), dim3(512), shm_t, st, p);   \
+            } while (0)
+#define LAUNCH_GRPK8T_NJ(NKSV) do { if (ref_div == 64) LAUNCH_GRPK8T(2, NKSV); else if (ref_div == 128) LAUNCH_GRPK8T(4, NKSV); else LAUNCH_GRPK8T(8, NKSV); } while (0)
+            if (k_valid <= 200) LAUNCH_GRPK8T_NJ(13); else LAUNCH_GRPK8T_NJ(14);
+#undef LAUNCH_GRPK8T_NJ
+#undef LAUNCH_GRPK8T
+            ADALOG_LAUNCH_CHECK("adalog_gemm_score (bf16 x fp8, trimmed K)");
+            return 0;
+        }
         const size_t shm = (size_t)3 * 4 * 4 * 32 * BK3 + (size_t)7 * ref_div * 4 + (size_t)gmod * 256 * 8;   // 3 stages of 4 K-steps x 4 blocks
 #define LAUNCH_GRPK8(NJV)                                                                                         \
         do {                                                                                                      \

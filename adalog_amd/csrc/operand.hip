@@ -892,8 +892,11 @@ extern "C" int adalog_pack_uniform(const float* x, int64_t G, int64_t R, int64_t
     {
         const int64_t row_bytes = Kp * ((out_dtype == 0 || out_dtype == 3) ? 1 : out_dtype == 1 ? 2 : 4);
         // 32-byte rows: int8 / fp8 operands of K <= 32 for the window kernel only (adalog_gemm_score checks its side)
-        ADALOG_ARG_CHECK(Kp >= K && (row_bytes % 64 == 0 || (row_bytes == 32 && (out_dtype == 0 || out_dtype == 3))),
-                         "pack_uniform: Kp must cover K and be a multiple of 64 bytes (128 for anything but the search kernels)");
+        // rows of 16-byte slots, fp8 only: the candidate columns of the trimmed-K mixed kernel (adalog_gemm_mixed_ktrim: 208 bytes).  Every
+        // pack kernel works on 4- or 16-element pieces of a row, so any such length packs; adalog_gemm_score checks what it can read
+        ADALOG_ARG_CHECK(Kp >= K && (row_bytes % 64 == 0 || (row_bytes == 32 && (out_dtype == 0 || out_dtype == 3)) ||
+                                     (row_bytes % 16 == 0 && out_dtype == 3)),
+                         "pack_uniform: Kp must cover K and be a multiple of 64 bytes (128 for anything but the search kernels; fp8: of 16 bytes)");
     }
     ADALOG_ARG_CHECK(n_bits >= 2 && n_bits <= 7, "pack_uniform: n_bits must be in [2,7] (q - z must fit int8)");
     hipStream_t st = (hipStream_t)stream;
@@ -935,7 +938,8 @@ extern "C" int adalog_pack_adalog_bf16_pre(const float* x, int64_t G, int64_t R,
     ADALOG_ARG_CHECK(pre == 0 || (pre == 1 && pg == 0 && sxk == 1 && !getenv("ADALOG_PACK_GENERIC")), "pack_adalog: the GELU prologue needs a per-tensor scale and unit K stride");
     ADALOG_ARG_CHECK(x && scale && qv && mant37 && out, "pack_adalog: null pointer");
     ADALOG_ARG_CHECK(G >= 1 && R >= 1 && K >= 1 && C >= 1 && C <= 65535 && gmod >= 1, "pack_adalog: bad sizes");
-    ADALOG_ARG_CHECK(Kp >= K && (Kp * 2) % 64 == 0, "pack_adalog: Kp must cover K and be a multiple of 32 elements");
+    // (rows of 16 elements: the fixed bf16 operand of the trimmed-K mixed kernel, adalog_gemm_mixed_ktrim)
+    ADALOG_ARG_CHECK(Kp >= K && (Kp * 2) % 32 == 0, "pack_adalog: Kp must cover K and be a multiple of 16 elements");
     ADALOG_ARG_CHECK(n_bits >= 2 && n_bits <= 7, "pack_adalog: n_bits must be in [2,7] (numerators must fit bf16)");
     PackArgs a{};
     a.x = x; a.G = G; a.R = R; a.K = K; a.sxg = sxg; a.sxr = sxr; a.sxk = sxk;

@@ -393,8 +393,27 @@ def gemm_score(dtype: int, A, B, M: int, N: int, C: int, G: int, gmod: int, ref,
 
 def gemm_mixed_ok(M: int, N: int, G: int, gmod: int, ref_div: int, k_valid: int) -> bool:
     """True when gemm_score(BF16_FP8, ...) takes this shape (C = 1, candidates innermost, transposed reference, column axis
-    summed): A bf16 [.., M, Kp], B fp8 [.., N * ref_div, Kp] with Kp = 64 (K <= 64: windows) or 256 (K = 193..256)."""
+    summed): A bf16 [.., M, Kp], B fp8 [.., N * ref_div, Kp] with Kp = 64 (K <= 64: windows) or 256 (K = 193..256; or the shorter rows
+    of gemm_mixed_ktrim)."""
     return bool(_lib.load().adalog_gemm_mixed_ok(int(M), int(N) * int(ref_div), int(G), int(gmod), int(ref_div), int(k_valid)))
+
+
+def gemm_mixed_ktrim(M: int, N: int, G: int, gmod: int, ref_div: int, k_valid: int) -> int:
+    """Row length (elements) of the trimmed-K form of gemm_score(BF16_FP8, ...) for this shape, or 0 when it has none: 208 for the
+    197-token family with K = 193..208.  Both operands are then packed with rows of that length -- ``k_align=16`` bytes for the fp8
+    candidates, ``k_align=32`` for the bf16 rows (``pad_k`` gives 208 for either) -- instead of 256; the scores are the same bit for bit."""
+    return int(_lib.load().adalog_gemm_mixed_ktrim(int(M), int(N) * int(ref_div), int(G), int(gmod), int(ref_div), int(k_valid)))
+
+
+def mixed_k_align(K: int, ktrim_kp: int = 0):
+    """(k_align of the fp8 candidate columns, k_align of the bf16 rows), in bytes, of the mixed softmax.v weight search: rows of 64
+    elements for windows (K <= 64), of 256 for 197-token groups -- or of ``ktrim_kp`` elements (what gemm_mixed_ktrim returned, or
+    the row length of an operand already packed) when ``pad_k`` of K at a 16-element granularity gives exactly that length."""
+    if K <= 64:
+        return 64, 128
+    if ktrim_kp and pad_k(K, FP8, 16) == ktrim_kp and pad_k(K, BF16, 32) == ktrim_kp:
+        return 16, 32
+    return 256, 512
 
 
 def gemm_win_ok(dtype: int, M: int, N: int, G: int, gmod: int, ref_div: int, k_valid: int) -> bool:

@@ -14,6 +14,7 @@ import torch.nn as nn
 
 from .. import backend, search, train_mm
 from ..ops import BF16, BF16_FP8, FP8, I8, Strided, pad_k  # noqa: F401
+from ..ops import mixed_k_align as ops_mixed_k_align
 from ..quantizers.logarithm import AdaLogQuantizer
 from ..quantizers.uniform import UniformQuantizer
 
@@ -26,6 +27,7 @@ GEN_MM = os.environ.get('ADALOG_GEN_MM', 'all')
 # the log-base search of softmax.v with its 128 AdaLog quantisations generated inside the kernel (adalog_gemm_score_avq); 0 = packed
 GEN_AVQ = os.environ.get('ADALOG_GEN_AVQ', '1') != '0'
 MIXED_B_SEARCH = os.environ.get('ADALOG_MIXED_B', '1') != '0'     # softmax.v weight search: fp8 candidates against the bf16 probabilities
+AV_KTRIM = os.environ.get('ADALOG_AV_KTRIM', '1') != '0'         # ... with rows of 208 instead of 256 elements where the kernel takes them (ops.gemm_mixed_ktrim)
 
 
 class MinMaxQuantMatMul(nn.Module):
@@ -179,6 +181,17 @@ class AsymmetricallyBatchingQuantMatMul(PTQSLBatchingQuantMatMul):
         whole = self._cand_chunk(G * max(S, Sp) * pad_k(K, BF16 if esz == 2 else I8, 64) * esz) >= self.eq_n
         return 64 if whole else 128
 
+    def _mixed_kalign(self):
+        """(k_align of the fp8 candidates, k_align of the fixed bf16 rows) of the mixed B search: ops.mixed_k_align, with the trimmed
+        rows (208 elements for 197 keys) unless ADALOG_AV_KTRIM=0 or the kernel has no trimmed form for the shape."""
+        be = backend.get()
+        G, S, K, Sp = self._dims()
+        kp = 0
+        # (the stand-in backend of the host-logic tests has one GEMM path and no trimmed form: 256-element rows there)
+        if AV_KTRIM and K > 64 and hasattr(be, "gemm_mixed_ktrim"):
+            kp = be.gemm_mixed_ktrim(S, Sp, G, self._heads(), self.eq_n, K)
+        return ops_mixed_k_align(K, kp)
+
     def _pack_fixed(self, which, dt=I8):
         be = backend.get()
         H = self._heads()
@@ -206,10 +219,12 @@ class AsymmetricallyBatchingQuantMatMul(PTQSLBatchingQuantMatMul):
         src = self._a3(A) if which == "A" else self._bt3_packable(B)
         bits = self.A_quantizer.n_bits if which == "A" else self.B_quantizer.n_bits
         rows = S if which == "A" else Sp
-        mixed = dt == BF16_FP8                     # fixed operand bf16 [.., 256], candidates fp8 [.., 256] (ops.gemm_mixed_ok)
+        mixed = dt == BF16_FP8                     # fixed operand bf16 [.., Kp], candidates fp8 [.., Kp]: Kp = 64, 256 or 208 (ops.gemm_mixed_ok / _ktrim)
         cdt = FP8 if mixed else dt                 # what the candidates are packed as
         esz = 2 if dt == BF16 else 1
-        al = (64 if K <= 64 else 256) if mixed else self._kalign(dt)      # fp8 rows of the two mixed shape families
+        # mixed: the candidates' rows are as long as those of the fixed operand the caller packed (gemm_score needs one Kp): the trimmed
+        # 208 when it was packed with _mixed_kalign, 256 / 64 otherwise
+        al = ops_mixed_k_align(K, fixed.shape[-1])[0] if mixed else self._kalign(dt)
         chunk = self._cand_chunk(G * rows * pad_k(K, cdt, al) * esz)
         if mixed and chunk < P:
             raise RuntimeError("the mixed softmax.v search scores all candidates in one launch")
@@ -439,7 +454,7 @@ class PostSoftmaxAsymmetricallyBatchingQuantMatMul(AsymmetricallyBatchingQuantMa
             qv = search.const_tensor([float(self._q_host)], dev)
             K = A.shape[-1]
             ap = self._pack_A_adalog(self._a3(A), qv, self.A_quantizer.scale.data.view(-1), 1, True,
-                                     k_align=(128 if K <= 64 else 512) if mixed else self._kalign())
+                                     k_align=self._mixed_kalign()[1] if mixed else self._kalign())
             self._fpcs("B", steps=self.steps, fixed=ap, dt=BF16_FP8 if mixed else BF16,
                        fixed_sa=Strided(self.A_quantizer.scale.data.view(-1)), sa_mul=self._ts32(), checked=True)
         self.calibrated = True

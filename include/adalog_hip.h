@@ -107,6 +107,11 @@ int adalog_pack_split3_bf16(const float* x, int64_t G, int64_t R, int64_t K, int
  *   streaming form (weight search of the post-GELU layer, reference linear.py:355-392; Kp = any multiple of 64).  The kernels convert
  *   the fp8 fragments with v_cvt_scalef32_pk_bf16_fp8, so the streamed candidate operand has half the bytes of a bf16 one. */
 int adalog_gemm_mixed_ok(int M, int N, int G, int gmod, int ref_div, int64_t k_valid);
+/* adalog_gemm_mixed_ktrim: for a shape of the 197-token family above, the shorter row length adalog_gemm_score (dtype 4) also takes
+ *   -- Kp = 208 elements (13 sixteen-element slots, K = 193..208) for BOTH operands, packed with that Kp by adalog_pack_uniform
+ *   (fp8) and adalog_pack_adalog_bf16 -- or 0 when there is none.  Same scores, bit for bit, as with Kp = 256: the launch leaves
+ *   out only K positions that are zero padding in both operands. */
+int adalog_gemm_mixed_ktrim(int M, int N, int G, int gmod, int ref_div, int64_t k_valid);
 int adalog_gemm_score(int dtype, const void* A, const void* B, int64_t sAc, int64_t sAg, int64_t sBc, int64_t sBg, int M,
                       int N, int64_t Kp, int64_t k_valid, int C, int G, int gmod, const float* ref, int64_t ldr, int64_t sRg, int64_t ref_cs,
                       int ref_div, const float* sa, int64_t sa_c, int64_t sa_g, float sa_mul, const float* sb, int64_t sb_c,
