@@ -8,7 +8,10 @@ torch.float64 arithmetic, on whatever device the inputs live on.  Three layers:
   * the quant_forward of the six layer classes, from a layer's parameters;
   * a ViT block split into stages, each fed its recorded fp32 input (teacher forcing): qkv; attention core (split, q / k / v
     quantisers, q . k^T, * scale, softmax, post-softmax AdaLog, . v); proj + residual; fc1; GELU -> shifted AdaLog -> fc2 +
-    residual.
+    residual;
+  * a Swin block the same way: norm1 -> shifted-window row map -> qkv; window core (q * scale in fp32 BEFORE the q quantiser, scores +
+    relative-position bias + shift mask by window mod nW, softmax, AdaLog, . v); proj -> row map back + residual; fc1; fc2 -- and
+    PatchMerging's 2 x 2 regroup.  The row map and the shift mask are restated from coordinates, not from roll / reshape.
 
 Uniform bins use the oracle's fp32 op sequence (rne(x / s) + rne(z), clamp, - rne(z)), which the kernels reproduce bit for bit;
 every product and sum is fp64.  Softmax and GELU are fp64 here, so an AdaLog bin may legitimately differ from the kernel's where
@@ -290,12 +293,11 @@ def conv_qf(lay, x):
 
 
 # ============================================================================================================ ViT block stages
-def attention_core(qkv, m1, m2, H, mul):
-    """Attention core of a block from the qkv projection's recorded fp32 output [B, N, 3 C]: split, q / k / v input quantisers,
-    q . k^T (fp64), * mul, softmax (fp64), post-softmax AdaLog, . v; merged heads -> (ref [B, N, C], bar, ambiguous fraction)."""
+def _qkv_codes(qkv, m1, m2, H, q_mul=None):
+    """Split of a recorded qkv output [B, N, 3 C] and the codes of the q / k / v input quantisers, [B H, N, D] each; ``q_mul``: q is
+    multiplied by it in fp32 (one multiply, as the module route does) BEFORE its quantiser.  -> (cq, ck, cv, sq, sk, sv, hm)."""
     B_, N, C3 = qkv.shape
-    C = C3 // 3
-    D = C // H
+    D = C3 // 3 // H
     hm = m1._heads()
     t = qkv.reshape(B_, N, 3, H, D).permute(2, 0, 3, 1, 4)          # [3, B, H, N, D]
     G = B_ * H
@@ -305,23 +307,45 @@ def attention_core(qkv, m1, m2, H, mul):
         return uniform_codes(x.reshape(G, N, D), per_group(s, G, hm, qkv.device).float(), per_group(z, G, hm, qkv.device).float(),
                              quant.n_bits), s
 
-    cq, sq = codes(t[0], m1.A_quantizer)
+    q = t[0].float() if q_mul is None else t[0].float() * q_mul
+    cq, sq = codes(q, m1.A_quantizer)
     ck, sk = codes(t[1], m1.B_quantizer)
     cv, sv = codes(t[2], m2.B_quantizer)
+    return cq, ck, cv, sq, sk, sv, hm
+
+
+def _qk_scores(cq, ck, sq, sk, hm, mul=1.0):
+    """fp64 q . k^T * scales * mul and the bound of an fp32 score's error: <= 2^-22 |s| from the int8 product, <= (D + 4) 2^-24
+    sum |q k| |scales| from a composed (fp32) one."""
+    G, _, D = cq.shape
     acc = torch.bmm(cq, ck.transpose(1, 2))
-    alpha = per_group(sq, G, hm, qkv.device) * per_group(sk, G, hm, qkv.device)
+    alpha = per_group(sq, G, hm, cq.device) * per_group(sk, G, hm, cq.device)
     s = acc * alpha * f32(mul)
-    p = torch.softmax(s, -1)
-    # fp32 scores: <= 2^-22 |s| from the int8 product, <= (D + 4) 2^-24 sum |q k| |scales| from a composed (fp32) one; the
-    # softmax adds a few ulps: relative error of u per row
     s_err = torch.maximum(U22 * s.abs(), (D + 4) * U24 * torch.bmm(cq.abs(), ck.abs().transpose(1, 2)) * alpha * abs(f32(mul)))
-    rel = 2 * s_err.amax(-1, keepdim=True) + 16 * U24
+    return s, s_err
+
+
+def _softmax_adalog_v(p, rel, cv, sv, m2, hm, H):
+    """Post-softmax AdaLog of the fp64 probabilities p [B H, N, N] (``rel``: relative uncertainty of the kernel's fp32 p), then . v,
+    heads merged -> (ref [B, N, C], bar, ambiguous fraction)."""
+    G, N, _ = p.shape
     q = int(m2.A_quantizer.q.reshape(-1)[0])
     a_s = float(m2.A_quantizer.scale.data.reshape(-1)[0])
     val, dval, amb = softmax_adalog(p, q, m2.A_quantizer.n_bits, m2.table_scale, a_s, rel_err=rel)
     ref, bar = product(val, cv.transpose(1, 2), m2.A_quantizer.scale.data, sv, sa_mul=f32(m2.table_scale), gmod=hm,
                        heads_last=H, kind="bf16", amb_A=dval)
-    return ref.reshape(B_, N, C), bar.reshape(B_, N, C), float(amb.double().mean())
+    return ref.reshape(G // H, N, -1), bar.reshape(G // H, N, -1), float(amb.double().mean())
+
+
+def attention_core(qkv, m1, m2, H, mul):
+    """Attention core of a block from the qkv projection's recorded fp32 output [B, N, 3 C]: split, q / k / v input quantisers,
+    q . k^T (fp64), * mul, softmax (fp64), post-softmax AdaLog, . v; merged heads -> (ref [B, N, C], bar, ambiguous fraction)."""
+    cq, ck, cv, sq, sk, sv, hm = _qkv_codes(qkv, m1, m2, H)
+    s, s_err = _qk_scores(cq, ck, sq, sk, hm, mul)
+    p = torch.softmax(s, -1)
+    # the softmax adds a few ulps to the scores' error: relative error of u per row
+    rel = 2 * s_err.amax(-1, keepdim=True) + 16 * U24
+    return _softmax_adalog_v(p, rel, cv, sv, m2, hm, H)
 
 
 def block_stages(block, x):
@@ -337,5 +361,98 @@ def block_stages(block, x):
     x1 = out["attn"].float()
     h2 = block.norm2(x1)
     out["fc1"] = linear_qf(block.mlp.fc1, h2)[0]
+    out["mlp"], _, out["amb_fc2"] = postgelu_qf(block.mlp.fc2, out["fc1"].float(), pre_gelu=True, addend=x1)
+    return out
+
+
+# ============================================================================================================ Swin block stages
+def swin_window_rows(res, ws, shift):
+    """The token of an image [H, W] held by row r = (window, i, j) of its shifted windows, from coordinates alone (no roll, no
+    reshape): window (wy, wx), position (i, j) reads token ((wy ws + i + shift) mod H, (wx ws + j + shift) mod W).  -> long [H W]"""
+    (H, W), (wh, ww), (sh, sw) = res, ws, shift
+    wy, wx, i, j = torch.meshgrid(torch.arange(H // wh), torch.arange(W // ww), torch.arange(wh), torch.arange(ww), indexing="ij")
+    return (((wy * wh + i + sh) % H) * W + (wx * ww + j + sw) % W).reshape(-1)
+
+
+def swin_shift_mask(res, ws, shift):
+    """The shift mask [nW, N, N] from coordinates alone: in the rolled frame a position p of an axis of length L lies in region
+    0 (p < L - ws), 1 (p < L - shift) or 2; tokens of different (row region, column region) do not see each other (-100)."""
+    (H, W), (wh, ww), (sh, sw) = res, ws, shift
+    if not (sh or sw):
+        return None
+
+    def region(p, L, w, s):
+        return (p >= L - w).long() + (p >= L - s).long()
+    wy, wx, i, j = torch.meshgrid(torch.arange(H // wh), torch.arange(W // ww), torch.arange(wh), torch.arange(ww), indexing="ij")
+    lab = (3 * region(wy * wh + i, H, wh, sh) + region(wx * ww + j, W, ww, sw)).reshape(-1, wh * ww)
+    return torch.where(lab[:, :, None] == lab[:, None, :], 0.0, -100.0)
+
+
+def patch_merging_rows(x):
+    """The 2 x 2 regroup in front of PatchMerging's norm: [B, H, W, C] -> [B, H / 2, W / 2, 4 C], channels in the order (row, column)
+    parity (0, 0), (1, 0), (0, 1), (1, 1)."""
+    return torch.cat([x[:, 0::2, 0::2], x[:, 1::2, 0::2], x[:, 0::2, 1::2], x[:, 1::2, 1::2]], -1)
+
+
+def window_scores(qkv, m1, m2, H, q_mul):
+    """q . k^T of the window attention as the int8 product gives it (before bias and mask) -> (ref [Bw H, N, N], bar)"""
+    cq, ck, _, sq, sk, _, hm = _qkv_codes(qkv, m1, m2, H, q_mul=q_mul)
+    return product(cq, ck, sq, sk, gmod=hm)
+
+
+def window_core(qkv, m1, m2, H, table, index, mask, q_mul=None, s_mul=1.0):
+    """Core of a window attention (wrap_net.py:35-52) from the recorded fp32 qkv output [Bw, N, 3 C] in window order: split,
+    q * q_mul in fp32, q / k / v quantisers, fp64 scores  acc sa sb s_mul + table[index[i, j], h] + mask[window mod nW, i, j],
+    softmax, post-softmax AdaLog, . v -> (ref [Bw, N, C], bar, ambiguous fraction).  (Swin: q_mul = scale, s_mul = 1.)
+
+    The kernels form the score in fp32 and add bias and mask in fp32, one rounding each: on top of the product's error an absolute
+    error <= 2^-24 (|s + bias| + |s + bias + mask|) <= 2^-23 (|s| + |bias| + |mask|) per score.  exp(s_j - max) takes one more rounding
+    of the difference, 2^-24 |s_j - max| (up to 100 for a masked key), and a few ulps.  The relative error of a probability is its
+    own score's error plus that of the row's normaliser, which is at most the largest error among the keys that carry the sum: keys
+    with p <= 1e-12 are left out of that maximum, or the -100 entries would inflate every row's flip allowance."""
+    Bw, N, _ = qkv.shape
+    cq, ck, cv, sq, sk, sv, hm = _qkv_codes(qkv, m1, m2, H, q_mul=q_mul)
+    s0, s_err = _qk_scores(cq, ck, sq, sk, hm, s_mul)
+    bias = table.detach().to(F64)[index.reshape(-1).long()].view(N, N, H).permute(2, 0, 1)           # [H, N, N]
+    add = bias.unsqueeze(0).expand(Bw, H, N, N)
+    mag = s0.abs().view(Bw, H, N, N) + bias.abs().unsqueeze(0)
+    if mask is not None:
+        m = mask.detach().to(F64)[torch.arange(Bw, device=qkv.device) % mask.shape[0]].unsqueeze(1)  # [Bw, 1, N, N]
+        add = add + m
+        mag = mag + m.abs()
+    s = s0 + add.reshape(Bw * H, N, N)
+    s_err = s_err + U23 * mag.reshape(Bw * H, N, N)
+    p = torch.softmax(s, -1)
+    carried = torch.where(p > 1e-12, s_err, torch.zeros_like(s_err)).amax(-1, keepdim=True)
+    rel = s_err + carried + 2 * U24 * (s - s.amax(-1, keepdim=True)).abs() + 16 * U24
+    return _softmax_adalog_v(p, rel, cv, sv, m2, hm, H)
+
+
+def window_attention_core(qkv, attn, mask):
+    """window_core with a (wrapped) WindowAttention's parameters; ``mask``: the block's attn_mask, None for an unshifted block."""
+    return window_core(qkv, attn.matmul1, attn.matmul2, attn.num_heads, attn.relative_position_bias_table.data,
+                       attn.relative_position_index, mask, q_mul=attn.scale)
+
+
+def swin_block_stages(block, x):
+    """All stages of a wrapped Swin block chained in fp64-reference form from the block input x [B, H, W, C] (block_stages' analogue):
+    norm1, the shifted-window row map, qkv, the window core, proj, the row map back + x, norm2, fc1, GELU -> AdaLog -> fc2 + residual.
+    -> dict of references (qkv, core, proj in window order; attn, fc1, mlp in token order [B, H W, .])."""
+    out = {}
+    B, Hh, W, C = x.shape
+    L = Hh * W
+    attn = block.attn
+    N = attn.window_area
+    rows = swin_window_rows((Hh, W), block.window_size, block.shift_size).to(x.device)
+    h1 = block.norm1(x).view(B, L, C)[:, rows].reshape(-1, N, C)
+    out["qkv"] = linear_qf(attn.qkv, h1)[0]
+    core, _, out["amb_core"] = window_attention_core(out["qkv"].float(), attn, block.attn_mask)
+    out["core"] = core
+    out["proj"] = linear_qf(attn.proj, core.float())[0]
+    back = torch.empty(B, L, C, dtype=F64, device=x.device)
+    back[:, rows] = out["proj"].view(B, L, C)
+    out["attn"] = back + x.view(B, L, C).to(F64)
+    x1 = out["attn"].float()
+    out["fc1"] = linear_qf(block.mlp.fc1, block.norm2(x1))[0]
     out["mlp"], _, out["amb_fc2"] = postgelu_qf(block.mlp.fc2, out["fc1"].float(), pre_gelu=True, addend=x1)
     return out

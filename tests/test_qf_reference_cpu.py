@@ -176,3 +176,156 @@ def test_flip_allowance_covers_a_planted_boundary_and_rejects_two_bins():
     got2, _ = QR.product(two, cv2, torch.ones(1), torch.ones(1), sa_mul=ts, kind="bf16")
     with pytest.raises(AssertionError):
         QR.check(got2, ref2, bar2, "two bins off")
+
+
+# ============================================================================================================ Swin
+# (dim, heads, res, ws, shift, bits, images, head_channel_wise, bias_reparamed); the last entry (head dimension 32, 32 windows: several
+# per mask pattern) is run by the GPU tier only (tests/test_gpu_swin_fp64.py).  The seeds were checked on the CPU with
+# tests/qf_reference.py alone (qf_cases.make_swin_block on the CPU specification backend): the share of the core's elements on a
+# boundary-flip allowance is 0, 0, 2.6e-5, 6.0e-6 and 2.0e-5 in this order (cap 1e-3), of fc2's 3.7e-4, 4.5e-4, 3.0e-4, 6.1e-4 and
+# 7.0e-4 (cap 1e-2).
+SWIN_BLOCKS = [
+    (48, 3, 8, 4, 2, 4, 2, True, False), (48, 3, 8, 4, 0, 3, 2, False, False), (32, 2, 14, 7, 3, 6, 2, True, True),
+    (64, 2, 24, 12, 6, 4, 1, True, False), (64, 2, 14, 7, 3, 4, 8, True, False)]
+
+
+def swin_seed(dim, res, ws, shift, bits):
+    return dim + res + ws + shift + bits
+
+
+def make_swin_case(case, device):
+    dim, heads, res, ws, shift, bits, B, hcw, reparamed = case
+    return QC.make_swin_block(dim, heads, res, ws, shift, bits, B, device, head_channel_wise=hcw, bias_reparamed=reparamed,
+                              seed=swin_seed(dim, res, ws, shift, bits))
+
+
+_SWIN_RUNS = {}
+
+
+def _swin_run(i):
+    """the armed block of SWIN_BLOCKS[i] and one recorded module-route forward of it, shared by the tests below"""
+    if i not in _SWIN_RUNS:
+        backend.set_backend(cpu_backend)
+        blk, x = make_swin_case(SWIN_BLOCKS[i], "cpu")
+        _SWIN_RUNS[i] = (blk, x) + QC.record_swin_block(blk, x)
+    return _SWIN_RUNS[i]
+
+
+@pytest.mark.parametrize("i", range(4))
+def test_swin_block_stages_equal_the_module_route(i):
+    """A wrapped Swin block on the CPU specification backend (module route): the reference's row map and shift mask, built from
+    coordinates, equal the block's; every stage's recorded output meets the reference's bar on its recorded input; the chained
+    reference reproduces the block's output."""
+    blk, x, r, y = _swin_run(i)
+    res, ws, shift = SWIN_BLOCKS[i][2:5]
+    assert torch.equal(QR.swin_window_rows((res, res), (ws, ws), (shift, shift)), blk.token_rows.long())
+    mask = QR.swin_shift_mask((res, res), (ws, ws), (shift, shift))
+    assert (mask is None and blk.attn_mask is None) if shift == 0 else torch.equal(mask, blk.attn_mask)
+    rep = QC.check_swin_record(blk, x, r, y, fused_expected=False)
+    print({k: v for k, v in rep.items() if k != "y"})
+    assert rep["amb_core"] < 1e-3 and rep["amb_fc2"] < 1e-2, rep
+    chained = QR.swin_block_stages(blk, x)
+    y64 = y.double().reshape(chained["mlp"].shape)
+    assert ((chained["mlp"] - y64).norm() / y64.norm()).item() < 1e-5
+
+
+SHIFTED = [i for i in range(4) if SWIN_BLOCKS[i][4]]
+
+
+@pytest.mark.parametrize("i", SHIFTED)
+def test_swin_reference_rejects_a_mask_rolled_by_one_window(i):
+    blk, x, r, y = _swin_run(i)
+    with pytest.raises(AssertionError, match="window attention core"):
+        QC.check_swin_record(blk, x, r, y, core=lambda qkv: QR.window_attention_core(qkv, blk.attn, blk.attn_mask.roll(1, 0)))
+
+
+@pytest.mark.parametrize("i", range(4))
+def test_swin_reference_rejects_the_transposed_bias_index(i):
+    blk, x, r, y = _swin_run(i)
+    a = blk.attn
+
+    def core(qkv):
+        return QR.window_core(qkv, a.matmul1, a.matmul2, a.num_heads, a.relative_position_bias_table.data,
+                              a.relative_position_index.t(), blk.attn_mask, q_mul=a.scale)
+    with pytest.raises(AssertionError, match="window attention core"):
+        QC.check_swin_record(blk, x, r, y, core=core)
+
+
+@pytest.mark.parametrize("i", range(4))
+def test_swin_reference_rejects_the_scale_applied_after_the_quantiser(i):
+    """ViT's reading of the core: q through its quantiser as it is, the scores multiplied by the head scale"""
+    blk, x, r, y = _swin_run(i)
+    a = blk.attn
+
+    def core(qkv):
+        return QR.window_core(qkv, a.matmul1, a.matmul2, a.num_heads, a.relative_position_bias_table.data, a.relative_position_index,
+                              blk.attn_mask, q_mul=None, s_mul=a.scale)
+    with pytest.raises(AssertionError, match="window attention core"):
+        QC.check_swin_record(blk, x, r, y, core=core)
+
+
+@pytest.mark.parametrize("i", SHIFTED)
+def test_swin_reference_rejects_the_unshifted_row_map(i):
+    blk, x, r, y = _swin_run(i)
+    res, ws = SWIN_BLOCKS[i][2:4]
+    with pytest.raises(AssertionError, match="row map of qkv"):
+        QC.check_swin_record(blk, x, r, y, rows=QR.swin_window_rows((res, res), (ws, ws), (0, 0)))
+
+
+def make_patch_merging(dim, bits, res, B, device, seed):
+    """A wrapped PatchMerging whose reduction (K = 4 dim, no bias) is armed as make_block arms a Linear -> (module, x [B, res, res, dim])"""
+    from adalog_amd.utils.models import PatchMerging
+    from adalog_amd.utils.wrap_net import wrap_modules_in_net
+    g = torch.Generator().manual_seed(seed)
+    pm = PatchMerging(dim)
+    pm.reduction.weight.data.copy_(torch.randn(pm.reduction.weight.shape, generator=g) * 0.06)
+    pm.norm.weight.data.copy_(1.0 + 0.2 * torch.randn(4 * dim, generator=g))
+    pm.norm.bias.data.copy_(0.1 * torch.randn(4 * dim, generator=g))
+    pm = wrap_modules_in_net(pm.eval(), QC.cfg(bits)).to(device)
+    x = (torch.randn(B, res, res, dim, generator=g) * 1.5).to(device)
+    lay = pm.reduction
+    assert lay.bias is None and lay.in_features == 4 * dim
+    with torch.no_grad():
+        QC.arm(lay.a_quantizer, *QC.minmax_params(pm.norm(QR.patch_merging_rows(x)), bits))
+    QC.arm(lay.w_quantizer, *QC.minmax_params(lay.weight.data.view(lay.n_V, lay.crb_rows, -1), bits, per=(0, 1)))
+    lay.calibrated = True
+    lay.mode = "quant_forward"
+    return pm, x
+
+
+def check_patch_merging(pm, x, kind="i8"):
+    """the module's regroup is the reference's, bit for bit; its output meets the bar of the reference's reduction"""
+    seen = {}
+    h = pm.norm.register_forward_hook(lambda m, a, out: seen.update(x=a[0].detach().clone(), out=out.detach().clone()))
+    with torch.no_grad():
+        y = pm(x)
+    h.remove()
+    assert torch.equal(seen["x"], QR.patch_merging_rows(x))
+    ref, bar = QR.linear_qf(pm.reduction, seen["out"], kind=kind)
+    return QR.check(y, ref, bar, "PatchMerging.reduction")
+
+
+def make_patch_embed_conv(bits, chans, out, size, B, device, seed):
+    """Swin's patch embedding: a 4 x 4 / stride-4 conv (fp32 input at 8 activation bits), weights armed per output channel"""
+    from adalog_amd import quant_layers as Q
+    g = torch.Generator().manual_seed(seed)
+    lay = Q.AsymmetricallyBatchingQuantConv2d(chans, out, 4, 4, mode="quant_forward", w_bit=bits, a_bit=8, fpcs=True)
+    lay.weight.data.copy_(torch.randn(lay.weight.shape, generator=g) * 0.1)
+    lay.bias.data.copy_(torch.randn(out, generator=g) * 0.1)
+    lay = lay.to(device)
+    x = torch.randn(B, chans, size, size, generator=g).to(device)
+    QC.arm(lay.w_quantizer, *QC.minmax_params(lay.weight.data.view(out, -1), bits, per=(0,)))
+    lay.a_quantizer.scale.data.fill_(float(x.abs().max()) / 127)
+    lay.a_quantizer.inited = True
+    lay.calibrated = True
+    return lay, x
+
+
+@pytest.mark.parametrize("bits", [3, 4, 6])
+def test_patch_merging_and_patch_embed_equal_spec(bits):
+    pm, x = make_patch_merging(32, bits, 8, 2, "cpu", seed=60 + bits)
+    check_patch_merging(pm, x, kind="f32")
+    lay, x = make_patch_embed_conv(bits, 3, 32, 16, 2, "cpu", seed=70 + bits)
+    ref, bar = QR.conv_qf(lay, x)
+    with torch.no_grad():
+        QR.check(lay(x), ref, bar, "patch embedding conv vs spec backend")
