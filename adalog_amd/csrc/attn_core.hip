@@ -48,6 +48,92 @@ struct AttnCoreArgs {
     int64_t bid0;                                        // first (group, row tile) pair of this launch
 };
 
+// The steps the two kernels share.  Each is written once, so that the two kernels cannot drift apart in the orders that the header
+// comment names (STORE epilogue, softmax + quantiser, softmax . v epilogue).
+
+// the two 16-byte code fragments (K-steps 0 and 1) of this lane's row of a packed int8 operand; a K-step without codes, or a row
+// that nobody multiplies (`live` false), is zero and is not read
+__device__ __forceinline__ void load_codes(v4i (&f)[2], const int8_t* row, bool live, int nks) {
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) f[ks] = (live && ks < nks) ? *reinterpret_cast<const v4i*>(row + ks * 32) : v4i{0, 0, 0, 0};
+}
+
+// one 32 x 32 block of scores: the ceil(D / 32) K-steps that hold codes, then the STORE epilogue of k_gemm_cand into the LDS tile S
+// (rows `ld` floats apart) at rows [row0, row0 + 32) x columns [col0, col0 + 32)
+__device__ __forceinline__ void score_block(const v4i (&af)[2], const v4i (&bf)[2], int nks, float alpha, float* S, int ld, int row0,
+                                            int col0, int frow, int fkg) {
+    v16i acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0;
+    acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(af[0], bf[0], acc, 0, 0, 0);
+    if (nks > 1) acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(af[1], bf[1], acc, 0, 0, 0);
+    float* sp = S + (row0 + 4 * fkg) * ld + col0 + frow;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        float s = (float)acc[r] * alpha;
+        s += 0.0f;
+        sp[((r & 3) + 8 * (r >> 2)) * ld] = s;
+    }
+}
+
+// softmax + quantiser over the tile's `rows` rows (query rows m0 ..), a wavefront per row, the WAVES wavefronts of the workgroup in
+// turn; NS slots per lane (softmax_adalog.h).  The bf16 row replaces the head of its own fp32 row, zero from N to Kp.
+template <int NS, bool BIAS, int WAVES>
+__device__ __forceinline__ void softmax_quant_rows(const AttnCoreArgs& a, float* S, int ld, const unsigned short* s_lut, int64_t g, int h,
+                                                   int m0, int rows, int w, int lane, float qf, float sc) {
+    const int N = a.N, Kp = a.Kp;
+    const float inv_s = __builtin_amdgcn_rcpf(sc), rq37 = 37.0f / qf;
+    const float* mk = nullptr;
+    if constexpr (BIAS) { if (a.mask) mk = a.mask + ((g / a.H) % a.nW) * (int64_t)N * N; }
+    for (int rl = w; rl < rows; rl += WAVES) {
+        float* srow = S + rl * ld;
+        float el[NS];
+#pragma unroll
+        for (int it = 0; it < NS; ++it) {
+            const int k = lane + 64 * it;
+            float e = -__builtin_inff();
+            if (k < N) {
+                const float s = srow[k];
+                if constexpr (BIAS) {
+                    const int64_t rc = (int64_t)(m0 + rl) * N + k;
+                    e = s + a.table[a.index[rc] * a.H + h];
+                    if (mk) e = e + mk[rc];
+                } else {
+                    e = s * a.mul;
+                }
+            }
+            el[it] = e;
+        }
+        const float sum = softmax_warp_row(el);
+        unsigned short* prow = reinterpret_cast<unsigned short*>(srow);
+#pragma unroll
+        for (int it = 0; it < NS; ++it) {
+            const int k = lane + 64 * it;
+            if (k >= Kp) break;
+            prow[k] = k < N ? adalog_prob_bf16(el[it], sum, sc, inv_s, qf, rq37, a.levels2, s_lut) : (unsigned short)0;
+        }
+    }
+}
+
+// the epilogue of softmax . v: o = (float)acc * (a_scale * sa_mul * sv); o += 0, stored heads-last [B][N][H][D] -- this lane's 16
+// values are rows row0 + 4 fkg + {0..3, 8..11, 16..19, 24..27} of channel `col`
+__device__ __forceinline__ void pv_store(const AttnCoreArgs& a, const v16f& acc, int64_t g, int gh, int h, int row0, int col, int fkg) {
+    const int N = a.N, D = a.D;
+    const float alpha = a.a_scale[0] * a.sa_mul * a.sv[gh * a.pg];
+    float* og = a.out + ((g / a.H) * (int64_t)N * a.H + h) * D + col;
+    if (col < D) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int row = row0 + 4 * fkg + (r & 3) + 8 * (r >> 2);
+            if (row < N) {
+                float o = acc[r] * alpha;
+                o += 0.0f;
+                og[(int64_t)row * a.H * D] = o;
+            }
+        }
+    }
+}
+
 template <int TM, bool BIAS>
 __global__ __launch_bounds__(256) void k_attn_core(AttnCoreArgs a) {
     constexpr int BMR = 32 * TM;
@@ -75,37 +161,14 @@ __global__ __launch_bounds__(256) void k_attn_core(AttnCoreArgs a) {
         const int8_t* kg = a.kp + g * (int64_t)N * 128 + fkg * 16;
         v4i af[TM][2], bf[2][2];
 #pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            const int r = min(m0 + i * 32 + frow, N - 1);
+        for (int i = 0; i < TM; ++i) load_codes(af[i], qg + (int64_t)min(m0 + i * 32 + frow, N - 1) * 128, true, nks);
 #pragma unroll
-            for (int ks = 0; ks < 2; ++ks)
-                af[i][ks] = ks < nks ? *reinterpret_cast<const v4i*>(qg + (int64_t)r * 128 + ks * 32) : v4i{0, 0, 0, 0};
-        }
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int c = min(w * 64 + j * 32 + frow, N - 1);
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks)
-                bf[j][ks] = ks < nks ? *reinterpret_cast<const v4i*>(kg + (int64_t)c * 128 + ks * 32) : v4i{0, 0, 0, 0};
-        }
+        for (int j = 0; j < 2; ++j) load_codes(bf[j], kg + (int64_t)min(w * 64 + j * 32 + frow, N - 1) * 128, true, nks);
         const float alpha = a.sq[gh * a.pg] * 1.0f * a.sk[gh * a.pg];
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                v16i acc;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[r] = 0;
-                acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(af[i][0], bf[j][0], acc, 0, 0, 0);
-                if (nks > 1) acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(af[i][1], bf[j][1], acc, 0, 0, 0);
-                float* sp = S + (i * 32 + 4 * fkg) * ld + w * 64 + j * 32 + frow;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    float s = (float)acc[r] * alpha;
-                    s += 0.0f;
-                    sp[((r & 3) + 8 * (r >> 2)) * ld] = s;
-                }
-            }
+            for (int j = 0; j < 2; ++j) score_block(af[i], bf[j], nks, alpha, S, ld, i * 32, w * 64 + j * 32, frow, fkg);
     }
 
     // ---- 3 (requests): this wavefront's fragments of v, all K chunks
@@ -124,40 +187,7 @@ __global__ __launch_bounds__(256) void k_attn_core(AttnCoreArgs a) {
     __syncthreads();
 
     // ---- 2. softmax + quantiser, a wavefront per row; the bf16 row replaces the head of the fp32 row
-    {
-        const float inv_s = __builtin_amdgcn_rcpf(sc), rq37 = 37.0f / qf;
-        const int rows = min(BMR, N - m0);
-        const float* mk = nullptr;
-        if constexpr (BIAS) { if (a.mask) mk = a.mask + ((g / a.H) % a.nW) * (int64_t)N * N; }
-        for (int rl = w; rl < rows; rl += 4) {
-            float* srow = S + rl * ld;
-            float el[4];
-#pragma unroll
-            for (int it = 0; it < 4; ++it) {
-                const int k = lane + 64 * it;
-                float e = -__builtin_inff();
-                if (k < N) {
-                    const float s = srow[k];
-                    if constexpr (BIAS) {
-                        const int64_t rc = (int64_t)(m0 + rl) * N + k;
-                        e = s + a.table[a.index[rc] * a.H + h];
-                        if (mk) e = e + mk[rc];
-                    } else {
-                        e = s * a.mul;
-                    }
-                }
-                el[it] = e;
-            }
-            const float sum = softmax_warp_row(el);
-            unsigned short* prow = reinterpret_cast<unsigned short*>(srow);
-#pragma unroll
-            for (int it = 0; it < 4; ++it) {
-                const int k = lane + 64 * it;
-                if (k >= Kp) break;
-                prow[k] = k < N ? adalog_prob_bf16(el[it], sum, sc, inv_s, qf, rq37, a.levels2, s_lut) : (unsigned short)0;
-            }
-        }
-    }
+    softmax_quant_rows<4, BIAS, 4>(a, S, ld, s_lut, g, h, m0, min(BMR, N - m0), w, lane, qf, sc);
     __syncthreads();
 
     // ---- 3. softmax . v: wavefront (pi, pj) -> rows [32 pi, 32 pi + 32) x channels [32 pj, 32 pj + 32)
@@ -174,20 +204,7 @@ __global__ __launch_bounds__(256) void k_attn_core(AttnCoreArgs a) {
                                                               acc, 0, 0, 0);
             }
         }
-        const float alpha = a.a_scale[0] * a.sa_mul * a.sv[gh * a.pg];
-        const int col = pj * 32 + frow;
-        float* og = a.out + ((g / a.H) * (int64_t)N * a.H + h) * D + col;
-        if (col < D) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = m0 + pi * 32 + 4 * fkg + (r & 3) + 8 * (r >> 2);
-                if (row < N) {
-                    float o = acc[r] * alpha;
-                    o += 0.0f;
-                    og[(int64_t)row * a.H * D] = o;
-                }
-            }
-        }
+        pv_store(a, acc, g, gh, h, m0 + pi * 32, pj * 32 + frow, fkg);
     }
 }
 
@@ -227,44 +244,18 @@ __global__ __launch_bounds__(64 * LONG_WAVES) void k_attn_core_long(AttnCoreArgs
         const int nkb = (N + 63) >> 6;                                 // key blocks that hold keys
         const int8_t* kg = a.kp + g * (int64_t)N * 128 + fkg * 16;
         v4i af[2], bf[2][2];
-        {
-            const int8_t* qr = a.qp + (g * (int64_t)N + min(m0 + frow, N - 1)) * 128 + fkg * 16;
+        load_codes(af, a.qp + (g * (int64_t)N + min(m0 + frow, N - 1)) * 128 + fkg * 16, true, nks);
 #pragma unroll
-            for (int ks = 0; ks < 2; ++ks) af[ks] = ks < nks ? *reinterpret_cast<const v4i*>(qr + ks * 32) : v4i{0, 0, 0, 0};
-        }
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int c = min(w * 64 + j * 32 + frow, N - 1);
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks)
-                bf[j][ks] = (w < nkb && ks < nks) ? *reinterpret_cast<const v4i*>(kg + (int64_t)c * 128 + ks * 32) : v4i{0, 0, 0, 0};
-        }
+        for (int j = 0; j < 2; ++j) load_codes(bf[j], kg + (int64_t)min(w * 64 + j * 32 + frow, N - 1) * 128, w < nkb, nks);
         const float alpha = a.sq[gh * a.pg] * 1.0f * a.sk[gh * a.pg];
         for (int kb = w; kb < nkb; kb += LONG_WAVES) {
             v4i bn[2][2];
             const bool more = kb + LONG_WAVES < nkb;
 #pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int c = min((kb + LONG_WAVES) * 64 + j * 32 + frow, N - 1);
+            for (int j = 0; j < 2; ++j)
+                load_codes(bn[j], kg + (int64_t)min((kb + LONG_WAVES) * 64 + j * 32 + frow, N - 1) * 128, more, nks);
 #pragma unroll
-                for (int ks = 0; ks < 2; ++ks)
-                    bn[j][ks] = (more && ks < nks) ? *reinterpret_cast<const v4i*>(kg + (int64_t)c * 128 + ks * 32) : v4i{0, 0, 0, 0};
-            }
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                v16i acc;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[r] = 0;
-                acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(af[0], bf[j][0], acc, 0, 0, 0);
-                if (nks > 1) acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(af[1], bf[j][1], acc, 0, 0, 0);
-                float* sp = S + (4 * fkg) * ld + kb * 64 + j * 32 + frow;       // (columns < Kp: Kp = 64 nkb)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    float s = (float)acc[r] * alpha;
-                    s += 0.0f;
-                    sp[((r & 3) + 8 * (r >> 2)) * ld] = s;
-                }
-            }
+            for (int j = 0; j < 2; ++j) score_block(af, bf[j], nks, alpha, S, ld, 0, kb * 64 + j * 32, frow, fkg);   // (columns < Kp = 64 nkb)
 #pragma unroll
             for (int j = 0; j < 2; ++j)
 #pragma unroll
@@ -282,27 +273,7 @@ __global__ __launch_bounds__(64 * LONG_WAVES) void k_attn_core_long(AttnCoreArgs
     __syncthreads();
 
     // ---- 2. softmax + quantiser, a wavefront per row; the bf16 row replaces the head of the fp32 row
-    {
-        const float inv_s = __builtin_amdgcn_rcpf(sc), rq37 = 37.0f / qf;
-        const int rows = min(32, N - m0);
-        for (int rl = w; rl < rows; rl += LONG_WAVES) {
-            float* srow = S + rl * ld;
-            float el[NS];
-#pragma unroll
-            for (int it = 0; it < NS; ++it) {
-                const int k = lane + 64 * it;
-                el[it] = k < N ? srow[k] * a.mul : -__builtin_inff();
-            }
-            const float sum = softmax_warp_row(el);
-            unsigned short* prow = reinterpret_cast<unsigned short*>(srow);
-#pragma unroll
-            for (int it = 0; it < NS; ++it) {
-                const int k = lane + 64 * it;
-                if (k >= Kp) break;
-                prow[k] = k < N ? adalog_prob_bf16(el[it], sum, sc, inv_s, qf, rq37, a.levels2, s_lut) : (unsigned short)0;
-            }
-        }
-    }
+    softmax_quant_rows<NS, false, LONG_WAVES>(a, S, ld, s_lut, g, h, m0, min(32, N - m0), w, lane, qf, sc);
     __syncthreads();
 
     // ---- 3. softmax . v: wavefront w -> the tile's 32 rows x channels [32 w, 32 w + 32)
@@ -327,78 +298,100 @@ __global__ __launch_bounds__(64 * LONG_WAVES) void k_attn_core_long(AttnCoreArgs
 #pragma unroll
             for (int i = 0; i < 8; ++i) vf[i] = vn[i];
         }
-        const float alpha = a.a_scale[0] * a.sa_mul * a.sv[gh * a.pg];
-        const int col = w * 32 + frow;
-        float* og = a.out + ((g / a.H) * (int64_t)N * a.H + h) * D + col;
-        if (col < D) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = m0 + 4 * fkg + (r & 3) + 8 * (r >> 2);
-                if (row < N) {
-                    float o = acc[r] * alpha;
-                    o += 0.0f;
-                    og[(int64_t)row * a.H * D] = o;
-                }
-            }
-        }
+        pv_store(a, acc, g, gh, h, m0, w * 32 + frow, fkg);
     }
+}
+
+// ---- host: one path for the two entry points
+
+bool head_dim_ok(int D) { return D == 16 || D == 32 || D == 48 || D == 64; }
+
+// the argument checks of adalog_attn_core (`name` "attn_core", n_max 256) and adalog_attn_core_long ("attn_core_long", 1024, no
+// table / index / mask): 0, or -1 with "<name>: <what is wrong>" as the error
+int attn_core_check(const char* name, int n_max, const void* qp, const void* kp, const void* vp, int64_t G, int N, int D, int H, int gmod,
+                    int64_t Np, const float* q_scale, const float* k_scale, const float* v_scale, int pg, const float* a_scale,
+                    const float* qv, int n_bits, const float* mant37, const float* table, const int64_t* index, const float* mask, int nW,
+                    const float* out) {
+    char n_range[48];
+    snprintf(n_range, sizeof(n_range), "1 <= N <= %d tokens per group", n_max);
+    const char* what =
+        !(qp && kp && vp && q_scale && k_scale && v_scale && a_scale && qv && mant37 && out) ? "null pointer"
+        : !head_dim_ok(D) ? "head dimension D must be 16, 32, 48 or 64"
+        : !(N >= 1 && N <= n_max) ? n_range
+        : Np != (int64_t)((N + 63) / 64) * 64 ? "Np (rows of vp) must be N rounded up to a multiple of 64"
+        : !(n_bits >= 2 && n_bits <= 7) ? "n_bits must be in [2,7]"
+        : !(G >= 1 && H >= 1 && gmod >= 1 && G % H == 0 && G % gmod == 0 && (pg == 0 || pg == 1))
+            ? "G must be a multiple of H and of gmod, pg 0 or 1"
+        : !((table != nullptr) == (index != nullptr) && (!mask || (table && nW >= 1)))
+            ? "table and index go together; a mask needs them and nW >= 1"
+        : !(((uintptr_t)qp & 15) == 0 && ((uintptr_t)kp & 15) == 0 && ((uintptr_t)vp & 15) == 0) ? "packed operands must be 16-byte aligned"
+        : nullptr;
+    if (!what) return 0;
+    char msg[160];
+    snprintf(msg, sizeof(msg), "%s: %s", name, what);
+    adalog_set_error_msg(msg);
+    return -1;
+}
+
+// the kernels' arguments from the (checked) arguments of an entry point; the grid's part (MT, bid0) is attn_core_launch's
+AttnCoreArgs attn_core_args(const void* qp, const void* kp, const void* vp, int64_t G, int N, int D, int H, int gmod, int64_t Np,
+                            const float* q_scale, const float* k_scale, const float* v_scale, int pg, float mul, const float* a_scale,
+                            const float* qv, int n_bits, const float* mant37, float sa_mul, const float* table, const int64_t* index,
+                            const float* mask, int nW, float* out) {
+    AttnCoreArgs a{};
+    a.qp = (const int8_t*)qp; a.kp = (const int8_t*)kp; a.vp = (const unsigned short*)vp;
+    a.G = G; a.N = N; a.D = D; a.H = H; a.gmod = gmod; a.Kp = (int)Np;
+    a.sq = q_scale; a.sk = k_scale; a.sv = v_scale; a.pg = pg; a.mul = mul;
+    a.a_scale = a_scale; a.qv = qv; a.mant = mant37; a.levels2 = 1 << n_bits; a.sa_mul = sa_mul;
+    a.table = table; a.index = index; a.mask = mask; a.nW = nW; a.out = out;
+    return a;
+}
+
+// Launches KERNEL (`threads` per workgroup, tile_rows query rows per workgroup) over the flattened (group, row tile) grid, split far
+// below the grid limit, after raising its dynamic-LDS limit to lds_max once per device.  0, or the HIP error (recorded under `entry`).
+template <void (*KERNEL)(AttnCoreArgs)>
+int attn_core_launch(const char* entry, AttnCoreArgs a, int tile_rows, int threads, int lds_max, hipStream_t st) {
+    static unsigned long long attr_dev = 0;                                 // (one per KERNEL)
+    const hipError_t ea = adalog_max_lds(reinterpret_cast<const void*>(KERNEL), lds_max, &attr_dev);
+    if (ea != hipSuccess) { adalog_set_error("hipFuncSetAttribute", ea); return (int)ea; }
+    a.MT = cdiv(a.N, tile_rows);
+    const size_t shm = (size_t)tile_rows * (a.Kp + 4) * 4 + 264 * sizeof(unsigned short);
+    const int64_t total = a.G * a.MT, per_launch = (int64_t)1 << 30;
+    for (int64_t b0 = 0; b0 < total; b0 += per_launch) {
+        a.bid0 = b0;
+        const int64_t nb = total - b0 < per_launch ? total - b0 : per_launch;
+        hipLaunchKernelGGL(KERNEL, dim3((unsigned)nb), dim3(threads), shm, st, a);
+    }
+    ADALOG_LAUNCH_CHECK(entry);
+    return 0;
 }
 
 }  // namespace
 
 // the shapes adalog_attn_core takes: 1 <= N <= 256 keys (the bound of adalog_softmax_adalog_pack_bf16), head dimension 16, 32, 48 or 64
-extern "C" int adalog_attn_core_supported(int N, int D) {
-    return (N >= 1 && N <= 256 && (D == 16 || D == 32 || D == 48 || D == 64)) ? 1 : 0;
-}
+extern "C" int adalog_attn_core_supported(int N, int D) { return (N >= 1 && N <= 256 && head_dim_ok(D)) ? 1 : 0; }
 
 extern "C" int adalog_attn_core(const void* qp, const void* kp, const void* vp, int64_t G, int N, int D, int H, int gmod, int64_t Np,
                                 const float* q_scale, const float* k_scale, const float* v_scale, int pg, float mul,
                                 const float* a_scale, const float* qv, int n_bits, const float* mant37, float sa_mul,
                                 const float* table, const int64_t* index, const float* mask, int nW, float* out, void* stream) {
-    ADALOG_ARG_CHECK(qp && kp && vp && q_scale && k_scale && v_scale && a_scale && qv && mant37 && out, "attn_core: null pointer");
-    ADALOG_ARG_CHECK(D == 16 || D == 32 || D == 48 || D == 64, "attn_core: head dimension D must be 16, 32, 48 or 64");
-    ADALOG_ARG_CHECK(N >= 1 && N <= 256, "attn_core: 1 <= N <= 256 tokens per group");
-    ADALOG_ARG_CHECK(Np == (int64_t)((N + 63) / 64) * 64, "attn_core: Np (rows of vp) must be N rounded up to a multiple of 64");
-    ADALOG_ARG_CHECK(n_bits >= 2 && n_bits <= 7, "attn_core: n_bits must be in [2,7]");
-    ADALOG_ARG_CHECK(G >= 1 && H >= 1 && gmod >= 1 && G % H == 0 && G % gmod == 0 && (pg == 0 || pg == 1),
-                     "attn_core: G must be a multiple of H and of gmod, pg 0 or 1");
-    ADALOG_ARG_CHECK((table != nullptr) == (index != nullptr) && (!mask || (table && nW >= 1)),
-                     "attn_core: table and index go together; a mask needs them and nW >= 1");
-    ADALOG_ARG_CHECK(((uintptr_t)qp & 15) == 0 && ((uintptr_t)kp & 15) == 0 && ((uintptr_t)vp & 15) == 0,
-                     "attn_core: packed operands must be 16-byte aligned");
+    if (attn_core_check("attn_core", 256, qp, kp, vp, G, N, D, H, gmod, Np, q_scale, k_scale, v_scale, pg, a_scale, qv, n_bits, mant37,
+                        table, index, mask, nW, out))
+        return -1;
     const int tm = ((N + 31) / 32) * 32 < ((N + 63) / 64) * 64 ? 1 : 2;     // 64-row tiles only when they pad no more than 32-row tiles
-    AttnCoreArgs a{};
-    a.qp = (const int8_t*)qp; a.kp = (const int8_t*)kp; a.vp = (const unsigned short*)vp;
-    a.G = G; a.N = N; a.D = D; a.H = H; a.gmod = gmod; a.MT = cdiv(N, 32 * tm); a.Kp = (int)Np;
-    a.sq = q_scale; a.sk = k_scale; a.sv = v_scale; a.pg = pg; a.mul = mul;
-    a.a_scale = a_scale; a.qv = qv; a.mant = mant37; a.levels2 = 1 << n_bits; a.sa_mul = sa_mul;
-    a.table = table; a.index = index; a.mask = mask; a.nW = nW; a.out = out;
-    const size_t shm = (size_t)32 * tm * (a.Kp + 4) * 4 + 264 * sizeof(unsigned short);
-    const int64_t total = G * a.MT, per_launch = (int64_t)1 << 30;          // flattened (group, row tile) grid, split far below the limit
+    const AttnCoreArgs a = attn_core_args(qp, kp, vp, G, N, D, H, gmod, Np, q_scale, k_scale, v_scale, pg, mul, a_scale, qv, n_bits,
+                                          mant37, sa_mul, table, index, mask, nW, out);
+    const char* entry = "adalog_attn_core";
     hipStream_t st = (hipStream_t)stream;
-#define LAUNCH_ATTN_CORE(TMV, BIASV)                                                                              \
-    do {                                                                                                          \
-        static unsigned long long attr_dev = 0;                                                                   \
-        { hipError_t ea__ = adalog_max_lds(reinterpret_cast<const void*>(&k_attn_core<TMV, BIASV>), (int)(68 * 1024), &attr_dev); \
-          if (ea__ != hipSuccess) { adalog_set_error("hipFuncSetAttribute", ea__); return (int)ea__; } }          \
-        for (int64_t b0 = 0; b0 < total; b0 += per_launch) {                                                      \
-            a.bid0 = b0;                                                                                          \
-            const int64_t nb = total - b0 < per_launch ? total - b0 : per_launch;                                 \
-            hipLaunchKernelGGL((k_attn_core<TMV, BIASV>), dim3((unsigned)nb), dim3(256), shm, st, a);            \
-        }                                                                                                         \
-    } while (0)
     adalog_note_kernel("k_attn_core");
-    if (table) { if (tm == 2) LAUNCH_ATTN_CORE(2, true); else LAUNCH_ATTN_CORE(1, true); }
-    else { if (tm == 2) LAUNCH_ATTN_CORE(2, false); else LAUNCH_ATTN_CORE(1, false); }
-#undef LAUNCH_ATTN_CORE
-    ADALOG_LAUNCH_CHECK("adalog_attn_core");
-    return 0;
+    if (table) return tm == 2 ? attn_core_launch<k_attn_core<2, true>>(entry, a, 64, 256, 68 * 1024, st)
+                              : attn_core_launch<k_attn_core<1, true>>(entry, a, 32, 256, 68 * 1024, st);
+    return tm == 2 ? attn_core_launch<k_attn_core<2, false>>(entry, a, 64, 256, 68 * 1024, st)
+                   : attn_core_launch<k_attn_core<1, false>>(entry, a, 32, 256, 68 * 1024, st);
 }
 
 // the shapes adalog_attn_core_long takes: 1 <= N <= 1024 keys (as far as ATen's per-warp softmax goes), head dimension 16, 32, 48 or 64
-extern "C" int adalog_attn_core_long_supported(int N, int D) {
-    return (N >= 1 && N <= 1024 && (D == 16 || D == 32 || D == 48 || D == 64)) ? 1 : 0;
-}
+extern "C" int adalog_attn_core_long_supported(int N, int D) { return (N >= 1 && N <= 1024 && head_dim_ok(D)) ? 1 : 0; }
 
 // The plain form (softmax(scores * mul): ViT / DeiT) of adalog_attn_core for up to 1024 tokens per group; same operands, same bits as
 // gemm_out(I8) -> adalog_softmax_adalog_pack(_long)_bf16 -> gemm_out(BF16, heads_last).  LDS per workgroup: 32 (Np + 4) 4 + 528 bytes.
@@ -406,40 +399,16 @@ extern "C" int adalog_attn_core_long(const void* qp, const void* kp, const void*
                                      const float* q_scale, const float* k_scale, const float* v_scale, int pg, float mul,
                                      const float* a_scale, const float* qv, int n_bits, const float* mant37, float sa_mul, float* out,
                                      void* stream) {
-    ADALOG_ARG_CHECK(qp && kp && vp && q_scale && k_scale && v_scale && a_scale && qv && mant37 && out, "attn_core_long: null pointer");
-    ADALOG_ARG_CHECK(D == 16 || D == 32 || D == 48 || D == 64, "attn_core_long: head dimension D must be 16, 32, 48 or 64");
-    ADALOG_ARG_CHECK(N >= 1 && N <= 1024, "attn_core_long: 1 <= N <= 1024 tokens per group");
-    ADALOG_ARG_CHECK(Np == (int64_t)((N + 63) / 64) * 64, "attn_core_long: Np (rows of vp) must be N rounded up to a multiple of 64");
-    ADALOG_ARG_CHECK(n_bits >= 2 && n_bits <= 7, "attn_core_long: n_bits must be in [2,7]");
-    ADALOG_ARG_CHECK(G >= 1 && H >= 1 && gmod >= 1 && G % H == 0 && G % gmod == 0 && (pg == 0 || pg == 1),
-                     "attn_core_long: G must be a multiple of H and of gmod, pg 0 or 1");
-    ADALOG_ARG_CHECK(((uintptr_t)qp & 15) == 0 && ((uintptr_t)kp & 15) == 0 && ((uintptr_t)vp & 15) == 0,
-                     "attn_core_long: packed operands must be 16-byte aligned");
-    AttnCoreArgs a{};
-    a.qp = (const int8_t*)qp; a.kp = (const int8_t*)kp; a.vp = (const unsigned short*)vp;
-    a.G = G; a.N = N; a.D = D; a.H = H; a.gmod = gmod; a.MT = cdiv(N, 32); a.Kp = (int)Np;
-    a.sq = q_scale; a.sk = k_scale; a.sv = v_scale; a.pg = pg; a.mul = mul;
-    a.a_scale = a_scale; a.qv = qv; a.mant = mant37; a.levels2 = 1 << n_bits; a.sa_mul = sa_mul;
-    a.out = out;
-    const size_t shm = (size_t)32 * (a.Kp + 4) * 4 + 264 * sizeof(unsigned short);
-    const int64_t total = G * a.MT, per_launch = (int64_t)1 << 30;
+    if (attn_core_check("attn_core_long", 1024, qp, kp, vp, G, N, D, H, gmod, Np, q_scale, k_scale, v_scale, pg, a_scale, qv, n_bits,
+                        mant37, nullptr, nullptr, nullptr, 0, out))
+        return -1;
+    const AttnCoreArgs a = attn_core_args(qp, kp, vp, G, N, D, H, gmod, Np, q_scale, k_scale, v_scale, pg, mul, a_scale, qv, n_bits,
+                                          mant37, sa_mul, nullptr, nullptr, nullptr, 0, out);
+    const char* entry = "adalog_attn_core_long";
+    const int threads = 64 * LONG_WAVES;
     hipStream_t st = (hipStream_t)stream;
-#define LAUNCH_ATTN_CORE_LONG(NSV)                                                                                \
-    do {                                                                                                          \
-        static unsigned long long attr_dev = 0;                                                                   \
-        { hipError_t ea__ = adalog_max_lds(reinterpret_cast<const void*>(&k_attn_core_long<NSV>), (int)(136 * 1024), &attr_dev); \
-          if (ea__ != hipSuccess) { adalog_set_error("hipFuncSetAttribute", ea__); return (int)ea__; } }          \
-        for (int64_t b0 = 0; b0 < total; b0 += per_launch) {                                                      \
-            a.bid0 = b0;                                                                                          \
-            const int64_t nb = total - b0 < per_launch ? total - b0 : per_launch;                                 \
-            hipLaunchKernelGGL((k_attn_core_long<NSV>), dim3((unsigned)nb), dim3(64 * LONG_WAVES), shm, st, a);   \
-        }                                                                                                         \
-    } while (0)
     adalog_note_kernel("k_attn_core_long");
-    if (N <= 256) LAUNCH_ATTN_CORE_LONG(4);
-    else if (N <= 512) LAUNCH_ATTN_CORE_LONG(8);
-    else LAUNCH_ATTN_CORE_LONG(16);
-#undef LAUNCH_ATTN_CORE_LONG
-    ADALOG_LAUNCH_CHECK("adalog_attn_core_long");
-    return 0;
+    if (N <= 256) return attn_core_launch<k_attn_core_long<4>>(entry, a, 32, threads, 136 * 1024, st);
+    if (N <= 512) return attn_core_launch<k_attn_core_long<8>>(entry, a, 32, threads, 136 * 1024, st);
+    return attn_core_launch<k_attn_core_long<16>>(entry, a, 32, threads, 136 * 1024, st);
 }

@@ -1007,40 +1007,78 @@ extern "C" int adalog_pack_split3_bf16(const float* x, int64_t G, int64_t R, int
     return 0;
 }
 
+// ---- the three softmax packs: one launcher
+
+namespace {
+
+struct SoftmaxPackForm {
+    const char* name;        // prefix of the error messages
+    const char* entry;       // C symbol, for a failed launch
+    const char* kernel;      // what adalog_note_kernel records
+    int S_lo, S_hi;          // rows of S_lo <= S <= Kp <= S_hi scores
+    bool bias;               // Swin's form: table and index required, `count` counts groups of S rows
+    // Empty input (count == 0) returns 0 BEFORE the argument checks (null pointers pass), and a negative count is refused with the
+    // null-pointer message.  false: the arguments are checked first, and a count outside [0, 2^31) has a message of its own.  The
+    // entry points have differed in this since they were written; kept as it is.
+    bool empty_first;
+};
+
+template <bool BIAS, int NS, int ROWS>
+void softmax_pack_launch(const SoftmaxPackArgs& a, hipStream_t st) {
+    hipLaunchKernelGGL((k_softmax_adalog_pack_t<BIAS, NS, ROWS>), dim3((unsigned)((a.rows + 4 * ROWS - 1) / (4 * ROWS))), dim3(256), 0, st, a);
+}
+
+// checks in the order the entry points have always made them, then the kernel for the form and the row length
+int softmax_pack(const SoftmaxPackForm& f, const float* x, int64_t count, int S, float mul, const float* scale, const float* qv, int n_bits,
+                 const float* mant37, void* out, int64_t Kp, const float* table, const int64_t* index, const float* mask, int H, int nW,
+                 void* stream) {
+    if (f.empty_first && count == 0) return 0;
+    char s_range[64];
+    snprintf(s_range, sizeof(s_range), "%d <= S <= Kp <= %d, Kp a multiple of 32", f.S_lo, f.S_hi);
+    const char* what =
+        !(x && scale && qv && mant37 && out && (!f.bias || (table && index)) && (!f.empty_first || count > 0)) ? "null pointer"
+        : !(S >= f.S_lo && S <= f.S_hi && Kp >= S && Kp <= f.S_hi && (Kp * 2) % 64 == 0) ? s_range
+        : !(H >= 1 && count % H == 0 && (!mask || nW >= 1)) ? "G must be a multiple of H, nW >= 1 with a mask"
+        : !(n_bits >= 2 && n_bits <= 7) ? "n_bits must be in [2,7]"
+        : !(f.empty_first || (count >= 0 && count <= (int64_t)0x7fffffff)) ? "0 <= rows < 2^31"
+        : nullptr;
+    if (what) {
+        char msg[160];
+        snprintf(msg, sizeof(msg), "%s: %s", f.name, what);
+        adalog_set_error_msg(msg);
+        return -1;
+    }
+    if (count == 0) return 0;
+    const SoftmaxPackArgs a{x, f.bias ? count * S : count, S, mul, scale, qv, mant37, 1 << n_bits, reinterpret_cast<unsigned short*>(out), Kp,
+                            table, index, mask, H, mask ? nW : 1};
+    adalog_note_kernel(f.kernel);
+    hipStream_t st = (hipStream_t)stream;
+    if (f.bias) softmax_pack_launch<true, 4, SM_ROWS>(a, st);
+    else if (S <= 256) softmax_pack_launch<false, 4, SM_ROWS>(a, st);
+    else if (S <= 512) softmax_pack_launch<false, 8, 2>(a, st);
+    else softmax_pack_launch<false, 16, 1>(a, st);
+    ADALOG_LAUNCH_CHECK(f.entry);
+    return 0;
+}
+
+}  // namespace
+
 // (x * mul).softmax(-1) quantised by the post-softmax AdaLog quantiser (per-tensor scale, log base 2^(-q/37), u clamped to
 // [1e-15, 1]: reference quant_layers/matmul.py:337-343 with the searched q) straight into the bf16 operand image [rows][Kp] of
 // the softmax . v product.  x: fp32 [rows][S] contiguous, S <= 256; Kp: a multiple of 32 elements covering S, <= 256.
 extern "C" int adalog_softmax_adalog_pack_bf16(const float* x, int64_t rows, int S, float mul, const float* scale, const float* qv,
                                                int n_bits, const float* mant37, void* out, int64_t Kp, void* stream) {
-    if (rows == 0) return 0;
-    ADALOG_ARG_CHECK(x && scale && qv && mant37 && out && rows > 0, "softmax_adalog_pack: null pointer");
-    ADALOG_ARG_CHECK(S >= 1 && S <= 256 && Kp >= S && Kp <= 256 && (Kp * 2) % 64 == 0, "softmax_adalog_pack: 1 <= S <= Kp <= 256, Kp a multiple of 32");
-    ADALOG_ARG_CHECK(n_bits >= 2 && n_bits <= 7, "softmax_adalog_pack: n_bits must be in [2,7]");
-    SoftmaxPackArgs a{x, rows, S, mul, scale, qv, mant37, 1 << n_bits, reinterpret_cast<unsigned short*>(out), Kp, nullptr, nullptr, nullptr, 1, 1};
-    adalog_note_kernel("k_softmax_adalog_pack");
-    hipLaunchKernelGGL(k_softmax_adalog_pack_t<false>, dim3((unsigned)((rows + 4 * SM_ROWS - 1) / (4 * SM_ROWS))), dim3(256), 0, (hipStream_t)stream, a);
-    ADALOG_LAUNCH_CHECK("adalog_softmax_adalog_pack_bf16");
-    return 0;
+    static const SoftmaxPackForm f{"softmax_adalog_pack", "adalog_softmax_adalog_pack_bf16", "k_softmax_adalog_pack", 1, 256, false, true};
+    return softmax_pack(f, x, rows, S, mul, scale, qv, n_bits, mant37, out, Kp, nullptr, nullptr, nullptr, 1, 1, stream);
 }
 
 // The same for rows of 257 <= S <= 1024 scores (a ViT / DeiT at 384 px: 577 tokens): 8 slots per lane up to 512, 16 up to 1024, which is
 // as far as ATen's per-warp softmax -- the arithmetic this kernel restates -- goes.  Kp: a multiple of 32 elements covering S, <= 1024.
 extern "C" int adalog_softmax_adalog_pack_long_bf16(const float* x, int64_t rows, int S, float mul, const float* scale, const float* qv,
                                                     int n_bits, const float* mant37, void* out, int64_t Kp, void* stream) {
-    ADALOG_ARG_CHECK(x && scale && qv && mant37 && out, "softmax_adalog_pack_long: null pointer");
-    ADALOG_ARG_CHECK(S >= 257 && S <= 1024 && Kp >= S && Kp <= 1024 && (Kp * 2) % 64 == 0,
-                     "softmax_adalog_pack_long: 257 <= S <= Kp <= 1024, Kp a multiple of 32");
-    ADALOG_ARG_CHECK(n_bits >= 2 && n_bits <= 7, "softmax_adalog_pack_long: n_bits must be in [2,7]");
-    ADALOG_ARG_CHECK(rows >= 0 && rows <= (int64_t)0x7fffffff, "softmax_adalog_pack_long: 0 <= rows < 2^31");
-    if (rows == 0) return 0;
-    SoftmaxPackArgs a{x, rows, S, mul, scale, qv, mant37, 1 << n_bits, reinterpret_cast<unsigned short*>(out), Kp, nullptr, nullptr, nullptr, 1, 1};
-    adalog_note_kernel("k_softmax_adalog_pack_long");
-    if (S <= 512)
-        hipLaunchKernelGGL((k_softmax_adalog_pack_t<false, 8, 2>), dim3((unsigned)((rows + 7) / 8)), dim3(256), 0, (hipStream_t)stream, a);
-    else
-        hipLaunchKernelGGL((k_softmax_adalog_pack_t<false, 16, 1>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a);
-    ADALOG_LAUNCH_CHECK("adalog_softmax_adalog_pack_long_bf16");
-    return 0;
+    static const SoftmaxPackForm f{"softmax_adalog_pack_long", "adalog_softmax_adalog_pack_long_bf16", "k_softmax_adalog_pack_long", 257,
+                                   1024, false, false};
+    return softmax_pack(f, x, rows, S, mul, scale, qv, n_bits, mant37, out, Kp, nullptr, nullptr, nullptr, 1, 1, stream);
 }
 
 // Swin's window attention: ((x + relative-position bias) + shift mask).softmax(-1) through the same quantiser into the same operand
@@ -1049,18 +1087,9 @@ extern "C" int adalog_softmax_adalog_pack_long_bf16(const float* x, int64_t rows
 extern "C" int adalog_softmax_bias_adalog_pack_bf16(const float* x, int64_t G, int S, int H, const float* table, const int64_t* index,
                                                     const float* mask, int nW, const float* scale, const float* qv, int n_bits,
                                                     const float* mant37, void* out, int64_t Kp, void* stream) {
-    if (G == 0) return 0;
-    ADALOG_ARG_CHECK(x && table && index && scale && qv && mant37 && out && G > 0, "softmax_bias_adalog_pack: null pointer");
-    ADALOG_ARG_CHECK(S >= 1 && S <= 256 && Kp >= S && Kp <= 256 && (Kp * 2) % 64 == 0, "softmax_bias_adalog_pack: 1 <= S <= Kp <= 256, Kp a multiple of 32");
-    ADALOG_ARG_CHECK(H >= 1 && G % H == 0 && (!mask || nW >= 1), "softmax_bias_adalog_pack: G must be a multiple of H, nW >= 1 with a mask");
-    ADALOG_ARG_CHECK(n_bits >= 2 && n_bits <= 7, "softmax_bias_adalog_pack: n_bits must be in [2,7]");
-    const int64_t rows = G * S;
-    SoftmaxPackArgs a{x, rows, S, 1.0f, scale, qv, mant37, 1 << n_bits, reinterpret_cast<unsigned short*>(out), Kp, table, index, mask, H,
-                      mask ? nW : 1};
-    adalog_note_kernel("k_softmax_bias_adalog_pack");
-    hipLaunchKernelGGL(k_softmax_adalog_pack_t<true>, dim3((unsigned)((rows + 4 * SM_ROWS - 1) / (4 * SM_ROWS))), dim3(256), 0, (hipStream_t)stream, a);
-    ADALOG_LAUNCH_CHECK("adalog_softmax_bias_adalog_pack_bf16");
-    return 0;
+    static const SoftmaxPackForm f{"softmax_bias_adalog_pack", "adalog_softmax_bias_adalog_pack_bf16", "k_softmax_bias_adalog_pack", 1, 256,
+                                   true, true};
+    return softmax_pack(f, x, G, S, 1.0f, scale, qv, n_bits, mant37, out, Kp, table, index, mask, H, nW, stream);
 }
 
 // The three operand packs of an attention block's quant_forward in one launch per 65535 images (k_attn_split_pack): qkv fp32

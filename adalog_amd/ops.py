@@ -594,48 +594,58 @@ def gemm_out_gen(x3, a_scale, a_zp, n_bits: int, B, N: int, gmod: int, sa: Strid
 QF_EXTRAS = True
 
 
-def softmax_adalog_pack(x3, mul: float, scale, qv, n_bits: int, mant37):
-    """(x3 * mul).softmax(-1) through the post-softmax AdaLog quantiser, as the packed bf16 operand [1, G, R, Kp] of softmax . v
-    (adalog_softmax_adalog_pack_bf16: one pass, the probabilities are never stored).  x3: fp32 [G, R, S] contiguous, S <= 256."""
+def _softmax_pack(c_name: str, x3, mul: float, scale, qv, n_bits: int, mant37):
+    """softmax_adalog_pack / softmax_adalog_pack_long: the C entry point ``c_name`` over x3 fp32 [G, R, S] -> bf16 [1, G, R, Kp]"""
     x3 = _f32c(x3, "scores")
     G, R, S = x3.shape
     Kp = pad_k(S, BF16)
     out = torch.empty((1, G, R, Kp), dtype=torch.bfloat16, device=x3.device)
-    rc = _lib.load().adalog_softmax_adalog_pack_bf16(x3.data_ptr(), G * R, S, float(mul), _ptr(_f32c(scale, "scale")),
-                                                    _ptr(_f32c(qv, "qv")), int(n_bits), _ptr(_f32c(mant37, "mant37")),
-                                                    out.data_ptr(), Kp, _stream())
-    _lib.check(rc, "adalog_softmax_adalog_pack_bf16")
+    rc = getattr(_lib.load(), c_name)(x3.data_ptr(), G * R, S, float(mul), _ptr(_f32c(scale, "scale")), _ptr(_f32c(qv, "qv")),
+                                      int(n_bits), _ptr(_f32c(mant37, "mant37")), out.data_ptr(), Kp, _stream())
+    _lib.check(rc, c_name)
     out.k_valid = S
     return out
+
+
+def softmax_adalog_pack(x3, mul: float, scale, qv, n_bits: int, mant37):
+    """(x3 * mul).softmax(-1) through the post-softmax AdaLog quantiser, as the packed bf16 operand [1, G, R, Kp] of softmax . v
+    (adalog_softmax_adalog_pack_bf16: one pass, the probabilities are never stored).  x3: fp32 [G, R, S] contiguous, S <= 256."""
+    return _softmax_pack("adalog_softmax_adalog_pack_bf16", x3, mul, scale, qv, n_bits, mant37)
 
 
 def softmax_adalog_pack_ok(S: int) -> bool:
     return S <= 256 and pad_k(S, BF16) <= 256
 
 
+def _attn_split_pack(c_name: str, qkv, H: int, q_par, k_par, v_par, per_head: bool, D: int, ex_args=()):
+    """attn_split_pack / attn_split_pack_ex: the C entry point ``c_name`` (``ex_args``: what adalog_attn_split_pack_ex takes after H)
+    over qkv fp32 [B, N, 3*H*D] -> qp, kp int8 [1, B*H, N, 128], vp bf16 [1, B*H, D, Np]"""
+    qkv = _f32c(qkv, "qkv")
+    B, N, C3 = qkv.shape
+    assert D in (16, 32, 48, 64) and C3 == 3 * H * D
+    Np = ((N + 63) // 64) * 64
+    qp = torch.empty((1, B * H, N, 128), dtype=torch.int8, device=qkv.device)
+    kp = torch.empty((1, B * H, N, 128), dtype=torch.int8, device=qkv.device)
+    vp = torch.empty((1, B * H, D, Np), dtype=torch.bfloat16, device=qkv.device)
+    par = []                                                             # (holds the tensors until the call has been made)
+    for s_, z_, b_ in (q_par, k_par, v_par):
+        s_, z_ = _f32c(s_, "scale").reshape(-1), _f32c(z_, "zero_point").reshape(-1)
+        assert s_.numel() == z_.numel() == (H if per_head else 1)
+        par.append((s_, z_, int(b_)))
+    quant_args = [v for s_, z_, b_ in par for v in (s_.data_ptr(), z_.data_ptr(), b_)]
+    rc = getattr(_lib.load(), c_name)(qkv.data_ptr(), B, N, H, *ex_args, *quant_args, 1 if per_head else 0, qp.data_ptr(), kp.data_ptr(),
+                                      vp.data_ptr(), Np, _stream())
+    _lib.check(rc, c_name)
+    qp.k_valid = kp.k_valid = D
+    vp.k_valid = N
+    return qp, kp, vp
+
+
 def attn_split_pack(qkv, H: int, q_par, k_par, v_par, per_head: bool):
     """qkv fp32 [B, N, 3*H*64] (the qkv projection's output) -> (qp, kp, vp): the packed operands of q . k^T (int8 [1, B*H, N, 128])
     and of softmax . v's second operand (bf16 [1, B*H, 64, Np], v transposed) through the three uniform input quantisers
     ((scale, zero_point, n_bits) each; per head or per tensor) in one launch (adalog_attn_split_pack)."""
-    qkv = _f32c(qkv, "qkv")
-    B, N, C3 = qkv.shape
-    assert C3 == 3 * H * 64
-    Np = ((N + 63) // 64) * 64
-    qp = torch.empty((1, B * H, N, 128), dtype=torch.int8, device=qkv.device)
-    kp = torch.empty((1, B * H, N, 128), dtype=torch.int8, device=qkv.device)
-    vp = torch.empty((1, B * H, 64, Np), dtype=torch.bfloat16, device=qkv.device)
-    par = []
-    for s_, z_, b_ in (q_par, k_par, v_par):
-        s_, z_ = _f32c(s_, "scale").reshape(-1), _f32c(z_, "zero_point").reshape(-1)
-        assert s_.numel() == z_.numel() == (H if per_head else 1)
-        par += [s_, z_, int(b_)]
-    rc = _lib.load().adalog_attn_split_pack(qkv.data_ptr(), B, N, H, par[0].data_ptr(), par[1].data_ptr(), par[2], par[3].data_ptr(),
-                                           par[4].data_ptr(), par[5], par[6].data_ptr(), par[7].data_ptr(), par[8],
-                                           1 if per_head else 0, qp.data_ptr(), kp.data_ptr(), vp.data_ptr(), Np, _stream())
-    _lib.check(rc, "adalog_attn_split_pack")
-    qp.k_valid = kp.k_valid = 64
-    vp.k_valid = N
-    return qp, kp, vp
+    return _attn_split_pack("adalog_attn_split_pack", qkv, H, q_par, k_par, v_par, per_head, 64)
 
 
 # Capability flag of the Swin block's fused quant_forward (utils/models.py: SwinTransformerBlock), read like QF_EXTRAS: attn_split_pack_ex,
@@ -647,26 +657,8 @@ def attn_split_pack_ex(qkv, H: int, q_par, k_par, v_par, per_head: bool, D: int 
     """attn_split_pack for head dimension D in {16, 32, 48, 64} (qkv fp32 [B, N, 3*H*D]): qp, kp int8 [1, B*H, N, 128] (D codes, then
     zeros), vp bf16 [1, B*H, D, Np].  ``q_mul``: q is multiplied by float32(q_mul) before its quantiser -- Swin's q * scale, the product
     ATen forms (adalog_attn_split_pack_ex).  Any number of images B."""
-    qkv = _f32c(qkv, "qkv")
-    B, N, C3 = qkv.shape
-    assert D in (16, 32, 48, 64) and C3 == 3 * H * D
-    Np = ((N + 63) // 64) * 64
-    qp = torch.empty((1, B * H, N, 128), dtype=torch.int8, device=qkv.device)
-    kp = torch.empty((1, B * H, N, 128), dtype=torch.int8, device=qkv.device)
-    vp = torch.empty((1, B * H, D, Np), dtype=torch.bfloat16, device=qkv.device)
-    par = []
-    for s_, z_, b_ in (q_par, k_par, v_par):
-        s_, z_ = _f32c(s_, "scale").reshape(-1), _f32c(z_, "zero_point").reshape(-1)
-        assert s_.numel() == z_.numel() == (H if per_head else 1)
-        par += [s_, z_, int(b_)]
-    rc = _lib.load().adalog_attn_split_pack_ex(qkv.data_ptr(), B, N, H, int(D), 1.0 if q_mul is None else float(q_mul),
-                                              par[0].data_ptr(), par[1].data_ptr(), par[2], par[3].data_ptr(), par[4].data_ptr(), par[5],
-                                              par[6].data_ptr(), par[7].data_ptr(), par[8], 1 if per_head else 0, qp.data_ptr(),
-                                              kp.data_ptr(), vp.data_ptr(), Np, _stream())
-    _lib.check(rc, "adalog_attn_split_pack_ex")
-    qp.k_valid = kp.k_valid = D
-    vp.k_valid = N
-    return qp, kp, vp
+    return _attn_split_pack("adalog_attn_split_pack_ex", qkv, H, q_par, k_par, v_par, per_head, D,
+                            (int(D), 1.0 if q_mul is None else float(q_mul)))
 
 
 def softmax_bias_adalog_pack(x3, H: int, table, index, mask, scale, qv, n_bits: int, mant37):
@@ -705,6 +697,43 @@ def attn_core_ok(N: int, D: int) -> bool:
     return softmax_adalog_pack_ok(N) and bool(_lib.load().adalog_attn_core_supported(int(N), int(D)))
 
 
+def _attn_core(c_name: str, qp, kp, vp, N: int, D: int, H: int, gmod: int, sA, sB, sV, mul: float, a_scale, qv, n_bits: int, mant37,
+               sa_mul: float, bias=None):
+    """attn_core / attn_core_long: the C entry point ``c_name``.  ``bias``: (table, index, mask) for adalog_attn_core, which takes
+    them (null without a table); None for adalog_attn_core_long, which has no such arguments."""
+    G = qp.shape[1]
+    assert qp.dtype == torch.int8 and kp.dtype == torch.int8 and vp.dtype == torch.bfloat16
+    assert qp.is_cuda and qp.is_contiguous() and kp.is_contiguous() and vp.is_contiguous()
+    assert qp.shape[-2:] == (N, 128) and kp.shape == qp.shape and vp.shape[1] == G and vp.shape[2] == D and G % H == 0
+    Np = vp.shape[-1]
+    sA, sB, sV = (_f32c(t, "scale").reshape(-1) for t in (sA, sB, sV))
+    assert sA.numel() == sB.numel() == sV.numel() and sA.numel() in (1, gmod)
+    pg = 0 if sA.numel() == 1 else 1
+    bias_args = ()
+    if bias is not None:
+        table, index, mask = bias
+        nW = 0
+        if table is not None:
+            table = _f32c(table, "table")
+            assert table.dim() == 2 and table.shape[1] == H
+            assert index is not None and index.dtype == torch.int64 and index.is_cuda and index.numel() == N * N
+            index = index.contiguous()
+            if mask is not None:
+                mask = _f32c(mask, "mask")
+                assert mask.dim() == 3 and mask.shape[1:] == (N, N)
+                nW = mask.shape[0]
+        else:
+            assert index is None and mask is None
+        bias_args = (_ptr(table), _ptr(index), _ptr(mask), nW)
+    out = torch.empty((G // H, N, H, D), dtype=torch.float32, device=qp.device)
+    rc = getattr(_lib.load(), c_name)(qp.data_ptr(), kp.data_ptr(), vp.data_ptr(), G, int(N), int(D), int(H), int(gmod), Np,
+                                      sA.data_ptr(), sB.data_ptr(), sV.data_ptr(), pg, float(mul), _ptr(_f32c(a_scale, "scale")),
+                                      _ptr(_f32c(qv, "qv")), int(n_bits), _ptr(_f32c(mant37, "mant37")), float(sa_mul), *bias_args,
+                                      out.data_ptr(), _stream())
+    _lib.check(rc, c_name)
+    return out
+
+
 def attn_core(qp, kp, vp, N: int, D: int, H: int, gmod: int, sA, sB, sV, mul: float, a_scale, qv, n_bits: int, mant37,
               sa_mul: float = 1.0, table=None, index=None, mask=None):
     """The attention core of quant_forward in one launch (adalog_attn_core): from the packed operands of attn_split_pack(_ex) to
@@ -715,33 +744,8 @@ def attn_core(qp, kp, vp, N: int, D: int, H: int, gmod: int, sA, sB, sV, mul: fl
     gmod == H) or per tensor; a_scale, qv, mant37: the post-softmax AdaLog quantiser; sa_mul: folded into a_scale.  ``table`` and
     ``index`` (Swin): relative_position_bias_table [*, H] and relative_position_index [N, N] in front of the softmax instead of
     ``mul``, plus ``mask`` [nW, N, N] or None."""
-    G = qp.shape[1]
-    assert qp.dtype == torch.int8 and kp.dtype == torch.int8 and vp.dtype == torch.bfloat16
-    assert qp.is_cuda and qp.is_contiguous() and kp.is_contiguous() and vp.is_contiguous()
-    assert qp.shape[-2:] == (N, 128) and kp.shape == qp.shape and vp.shape[1] == G and vp.shape[2] == D and G % H == 0
-    Np = vp.shape[-1]
-    sA, sB, sV = (_f32c(t, "scale").reshape(-1) for t in (sA, sB, sV))
-    assert sA.numel() == sB.numel() == sV.numel() and sA.numel() in (1, gmod)
-    pg = 0 if sA.numel() == 1 else 1
-    nW = 0
-    if table is not None:
-        table = _f32c(table, "table")
-        assert table.dim() == 2 and table.shape[1] == H
-        assert index is not None and index.dtype == torch.int64 and index.is_cuda and index.numel() == N * N
-        index = index.contiguous()
-        if mask is not None:
-            mask = _f32c(mask, "mask")
-            assert mask.dim() == 3 and mask.shape[1:] == (N, N)
-            nW = mask.shape[0]
-    else:
-        assert index is None and mask is None
-    out = torch.empty((G // H, N, H, D), dtype=torch.float32, device=qp.device)
-    rc = _lib.load().adalog_attn_core(qp.data_ptr(), kp.data_ptr(), vp.data_ptr(), G, int(N), int(D), int(H), int(gmod), Np,
-                                      sA.data_ptr(), sB.data_ptr(), sV.data_ptr(), pg, float(mul), _ptr(_f32c(a_scale, "scale")),
-                                      _ptr(_f32c(qv, "qv")), int(n_bits), _ptr(_f32c(mant37, "mant37")), float(sa_mul), _ptr(table),
-                                      _ptr(index), _ptr(mask), nW, out.data_ptr(), _stream())
-    _lib.check(rc, "adalog_attn_core")
-    return out
+    return _attn_core("adalog_attn_core", qp, kp, vp, N, D, H, gmod, sA, sB, sV, mul, a_scale, qv, n_bits, mant37, sa_mul,
+                      bias=(table, index, mask))
 
 
 # Capability flag of the long-row fused route (utils/models.py: QF_LONG), read like QF_EXTRAS: softmax_adalog_pack_long(_ok),
@@ -757,16 +761,7 @@ def softmax_adalog_pack_long_ok(S: int) -> bool:
 def softmax_adalog_pack_long(x3, mul: float, scale, qv, n_bits: int, mant37):
     """softmax_adalog_pack for rows of 257 <= S <= 1024 scores (adalog_softmax_adalog_pack_long_bf16): x3 fp32 [G, R, S] contiguous ->
     the packed bf16 operand [1, G, R, Kp] of softmax . v, the same bits as pack_adalog of (x3 * mul).softmax(-1)."""
-    x3 = _f32c(x3, "scores")
-    G, R, S = x3.shape
-    Kp = pad_k(S, BF16)
-    out = torch.empty((1, G, R, Kp), dtype=torch.bfloat16, device=x3.device)
-    rc = _lib.load().adalog_softmax_adalog_pack_long_bf16(x3.data_ptr(), G * R, S, float(mul), _ptr(_f32c(scale, "scale")),
-                                                         _ptr(_f32c(qv, "qv")), int(n_bits), _ptr(_f32c(mant37, "mant37")),
-                                                         out.data_ptr(), Kp, _stream())
-    _lib.check(rc, "adalog_softmax_adalog_pack_long_bf16")
-    out.k_valid = S
-    return out
+    return _softmax_pack("adalog_softmax_adalog_pack_long_bf16", x3, mul, scale, qv, n_bits, mant37)
 
 
 def attn_core_long_ok(N: int, D: int) -> bool:
@@ -779,21 +774,7 @@ def attn_core_long(qp, kp, vp, N: int, D: int, H: int, gmod: int, sA, sB, sV, mu
     """The plain form of attn_core for up to 1024 tokens per group (adalog_attn_core_long): fp32 [B, N, H, D], bit-identical to
         gemm_out(I8, qp, kp) -> softmax_adalog_pack(_long)(., mul) -> gemm_out(BF16, ., vp, heads_last=H)
     with the 32-row score tile in LDS.  Arguments as attn_core's (no table, index or mask: ViT / DeiT only)."""
-    G = qp.shape[1]
-    assert qp.dtype == torch.int8 and kp.dtype == torch.int8 and vp.dtype == torch.bfloat16
-    assert qp.is_cuda and qp.is_contiguous() and kp.is_contiguous() and vp.is_contiguous()
-    assert qp.shape[-2:] == (N, 128) and kp.shape == qp.shape and vp.shape[1] == G and vp.shape[2] == D and G % H == 0
-    Np = vp.shape[-1]
-    sA, sB, sV = (_f32c(t, "scale").reshape(-1) for t in (sA, sB, sV))
-    assert sA.numel() == sB.numel() == sV.numel() and sA.numel() in (1, gmod)
-    pg = 0 if sA.numel() == 1 else 1
-    out = torch.empty((G // H, N, H, D), dtype=torch.float32, device=qp.device)
-    rc = _lib.load().adalog_attn_core_long(qp.data_ptr(), kp.data_ptr(), vp.data_ptr(), G, int(N), int(D), int(H), int(gmod), Np,
-                                           sA.data_ptr(), sB.data_ptr(), sV.data_ptr(), pg, float(mul), _ptr(_f32c(a_scale, "scale")),
-                                           _ptr(_f32c(qv, "qv")), int(n_bits), _ptr(_f32c(mant37, "mant37")), float(sa_mul),
-                                           out.data_ptr(), _stream())
-    _lib.check(rc, "adalog_attn_core_long")
-    return out
+    return _attn_core("adalog_attn_core_long", qp, kp, vp, N, D, H, gmod, sA, sB, sV, mul, a_scale, qv, n_bits, mant37, sa_mul)
 
 
 def gemm_out_gen_rows(x2, a_scale, a_zp, n_bits: int, B, N: int, sa: Strided, sb: Strided, bias: Optional[Strided],

@@ -15,6 +15,7 @@ Weights: seeded trunc_normal(std=0.02) init (there is no network for pretrained 
 """
 import math
 from functools import partial
+from typing import NamedTuple
 
 import torch
 import torch.nn as nn
@@ -37,16 +38,82 @@ QF_ATTN_CORE = os.environ.get("ADALOG_QF_ATTN_CORE", "0") == "1"
 QF_LONG = os.environ.get("ADALOG_QF_LONG", "0") == "1"
 
 
-def _attn_core_on(be, N, D):
-    """the switch is on, the backend has the one-launch attention core and it takes this shape"""
-    return QF_ATTN_CORE and getattr(be, "QF_ATTN_CORE", False) and be.attn_core_ok(N, D)
-
-
 def _plain_quant_forward(m):
     """m is one of the package's quantised modules, calibrated, in quant_forward mode, and nobody listens on its forward (the
     calibrator's capture hooks need the module-by-module route)."""
     return (getattr(m, "mode", None) == "quant_forward" and getattr(m, "calibrated", False)
             and not m._forward_hooks and not m._forward_pre_hooks)
+
+
+def _fused_products_ok(qkv, proj, m1, m2):
+    """What the fused quant_forward routes of Attention and WindowAttention ask of the block's quantised modules: both products are
+    the package's batching MatMuls, all four modules in plain quant_forward mode, the three uniform input quantisers (q, k, v) of the
+    kind and width the packers implement, the same head grouping in both products, a scalar post-softmax scale, and codes that fit
+    the packed operands.  Each class adds its own shape and backend conditions."""
+    from ..quant_layers.matmul import AsymmetricallyBatchingQuantMatMul, PostSoftmaxAsymmetricallyBatchingQuantMatMul
+    from ..quantizers.uniform import UniformQuantizer
+    if not (type(m1) is AsymmetricallyBatchingQuantMatMul and type(m2) is PostSoftmaxAsymmetricallyBatchingQuantMatMul
+            and all(_plain_quant_forward(m) for m in (qkv, proj, m1, m2))):
+        return False
+    qs = (m1.A_quantizer, m1.B_quantizer, m2.B_quantizer)
+    return (all(isinstance(q, UniformQuantizer) and 2 <= q.n_bits <= 7 and not q.training_mode for q in qs)
+            and not m2.A_quantizer.training_mode and m1._heads() == m2._heads() and m2.A_quantizer.scale.numel() == 1
+            and m1.packed_codes_fit() and m2.packed_codes_fit())
+
+
+class _CoreParams(NamedTuple):
+    """what the attention core of quant_forward needs of the two products' quantisers (_core_params)"""
+    q_par: tuple          # (scale, zero_point, n_bits) of q, of k, of v: the uniform input quantisers, per head or per tensor
+    k_par: tuple
+    v_par: tuple
+    a_scale: torch.Tensor  # the post-softmax AdaLog quantiser: scale [1], q as a device scalar, n_bits, the 37 numerators
+    qv: torch.Tensor
+    n_bits: int
+    mant37: torch.Tensor
+    sa_mul: float          # table_scale, folded into a_scale in the second product's epilogue
+
+
+def _core_params(m1, m2, device):
+    """_CoreParams of matmul1 / matmul2, fetched once per forward (one host read of q per calibration: m2._q_host)"""
+    sA, zA = m1._q_params(m1.A_quantizer)
+    sB, zB = m1._q_params(m1.B_quantizer)
+    sV, zV = m2._q_params(m2.B_quantizer)
+    if m2._q_host is None:
+        m2._q_host = int(m2.A_quantizer.q.item())
+    return _CoreParams((sA, zA, m1.A_quantizer.n_bits), (sB, zB, m1.B_quantizer.n_bits), (sV, zV, m2.B_quantizer.n_bits),
+                       m2.A_quantizer.scale.data.view(-1), _search.const_tensor([float(m2._q_host)], device), m2.A_quantizer.n_bits,
+                       m2._mant37(device), m2._ts32())
+
+
+def _quant_attn_core(be, qp, kp, vp, G, N, D, H, hm, p, mul=1.0, bias=None):
+    """The attention core of quant_forward from the packed operands of attn_split_pack(_ex) (G = images * H groups of N tokens, head
+    dimension D, hm quantiser heads) to softmax . v as [G / H, N, H, D] -- the ONE place that chooses the route:
+      one launch    QF_ATTN_CORE on and a backend with the capability: attn_core (<= 256 tokens) or attn_core_long (more), if the
+                    backend takes the shape; a shape it refuses goes on to
+      three launches  q . k^T (int8 MFMA), softmax + AdaLog quantiser + pack, softmax . v (bf16 MFMA, heads last), with
+                    softmax_bias_adalog_pack for ``bias``, else softmax_adalog_pack_long for more than 256 tokens, else softmax_adalog_pack.
+    p: _CoreParams.  mul: the multiplier in front of the softmax (plain form).  bias: (relative_position_bias_table,
+    relative_position_index, shift mask or None) in front of the softmax instead (Swin; <= 256 tokens).  The backend's functions are
+    looked up when they are called."""
+    from ..ops import BF16, I8, Strided
+    sA, sB, sV = p.q_par[0], p.k_par[0], p.v_par[0]
+    long_rows = N > 256
+    assert bias is None or not long_rows
+    if QF_ATTN_CORE and getattr(be, "QF_ATTN_CORE", False):
+        if long_rows:
+            if be.attn_core_long_ok(N, D):
+                return be.attn_core_long(qp, kp, vp, N, D, H, hm, sA, sB, sV, mul, p.a_scale, p.qv, p.n_bits, p.mant37, p.sa_mul)
+        elif be.attn_core_ok(N, D):
+            kw = {} if bias is None else dict(table=bias[0], index=bias[1], mask=bias[2])
+            return be.attn_core(qp, kp, vp, N, D, H, hm, sA, sB, sV, mul, p.a_scale, p.qv, p.n_bits, p.mant37, p.sa_mul, **kw)
+    pg = 1 if hm > 1 else 0
+    scores = be.gemm_out(I8, qp, kp, N, N, G, hm, Strided(sA, g=pg), Strided(sB, g=pg), None)
+    if bias is not None:
+        ap = be.softmax_bias_adalog_pack(scores, H, bias[0], bias[1], bias[2], p.a_scale, p.qv, p.n_bits, p.mant37)
+    else:
+        soft = be.softmax_adalog_pack_long if long_rows else be.softmax_adalog_pack
+        ap = soft(scores, mul, p.a_scale, p.qv, p.n_bits, p.mant37)
+    return be.gemm_out(BF16, ap, vp, N, D, G, hm, Strided(p.a_scale), Strided(sV, g=pg), None, sa_mul=p.sa_mul, heads_last=H)
 
 
 class MatMul(nn.Module):
@@ -106,20 +173,10 @@ class Attention(nn.Module):
         """quant_forward of the whole block on the fused route (below): every quantised module of the block is in plain
         quant_forward mode with the input quantisers the packers implement, head dimension 64, <= 256 tokens -- with QF_LONG, head
         dimension 16, 32, 48 or 64 and up to 1024 tokens."""
-        from ..quant_layers.matmul import AsymmetricallyBatchingQuantMatMul, PostSoftmaxAsymmetricallyBatchingQuantMatMul
-        from ..quantizers.uniform import UniformQuantizer
-        m1, m2 = self.matmul1, self.matmul2
-        if not (QF_FUSED and not torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32
+        return (QF_FUSED and not torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32
                 and self._fused_shape_ok(x.shape[1]) and isinstance(self.q_norm, nn.Identity) and isinstance(self.k_norm, nn.Identity)
-                and isinstance(self.attn_drop, nn.Identity) and isinstance(self.proj_drop, nn.Identity)):
-            return False
-        if not (type(m1) is AsymmetricallyBatchingQuantMatMul and type(m2) is PostSoftmaxAsymmetricallyBatchingQuantMatMul
-                and all(_plain_quant_forward(m) for m in (self.qkv, self.proj, m1, m2))):
-            return False
-        qs = (m1.A_quantizer, m1.B_quantizer, m2.B_quantizer)
-        return (all(isinstance(q, UniformQuantizer) and 2 <= q.n_bits <= 7 and not q.training_mode for q in qs)
-                and not m2.A_quantizer.training_mode and m1._heads() == m2._heads() and m2.A_quantizer.scale.numel() == 1
-                and getattr(_backend.get(), "QF_EXTRAS", False) and m1.packed_codes_fit() and m2.packed_codes_fit())
+                and isinstance(self.attn_drop, nn.Identity) and isinstance(self.proj_drop, nn.Identity)
+                and getattr(_backend.get(), "QF_EXTRAS", False) and _fused_products_ok(self.qkv, self.proj, self.matmul1, self.matmul2))
 
     def _fused_shape_ok(self, tokens):
         """head dimension 64 and <= 256 tokens; with QF_LONG on and a backend that has the long-row kernels, head dimension 16, 32, 48
@@ -136,42 +193,18 @@ class Attention(nn.Module):
         quant_layers/matmul.py:43-45) as five launches after the qkv projection: split + three input quantisers + operand packs;
         q . k^T (int8 MFMA); scale + softmax + AdaLog quantiser + pack; softmax . v (bf16 MFMA) written as [B, N, H, D]; the
         projection with the residual stream added in its epilogue."""
-        from ..ops import BF16, I8, Strided
         be = _backend.get()
         B, N, C = x.shape
-        H = self.num_heads
-        m1, m2 = self.matmul1, self.matmul2
+        H, D = self.num_heads, self.head_dim
+        m1 = self.matmul1
         qkv = self.qkv(x)
         hm = m1._heads()
-        pg = 1 if hm > 1 else 0
-        sA, zA = m1._q_params(m1.A_quantizer)
-        sB, zB = m1._q_params(m1.B_quantizer)
-        sV, zV = m2._q_params(m2.B_quantizer)
-        long_rows = N > 256                                              # (only behind QF_LONG: _fused_shape_ok)
-        if self.head_dim == 64:
-            qp, kp, vp = be.attn_split_pack(qkv, H, (sA, zA, m1.A_quantizer.n_bits), (sB, zB, m1.B_quantizer.n_bits),
-                                            (sV, zV, m2.B_quantizer.n_bits), hm > 1)
+        p = _core_params(m1, self.matmul2, x.device)
+        if D == 64:
+            qp, kp, vp = be.attn_split_pack(qkv, H, p.q_par, p.k_par, p.v_par, hm > 1)
         else:                                                            # (QF_LONG) the scale stays behind the product: no q_mul
-            qp, kp, vp = be.attn_split_pack_ex(qkv, H, (sA, zA, m1.A_quantizer.n_bits), (sB, zB, m1.B_quantizer.n_bits),
-                                               (sV, zV, m2.B_quantizer.n_bits), hm > 1, D=self.head_dim)
-        if m2._q_host is None:
-            m2._q_host = int(m2.A_quantizer.q.item())
-        qv = _search.const_tensor([float(m2._q_host)], x.device)
-        a_scale = m2.A_quantizer.scale.data.view(-1)
-        if long_rows:
-            if QF_ATTN_CORE and getattr(be, "QF_ATTN_CORE", False) and be.attn_core_long_ok(N, self.head_dim):
-                out = be.attn_core_long(qp, kp, vp, N, self.head_dim, H, hm, sA, sB, sV, self.scale, a_scale, qv,
-                                        m2.A_quantizer.n_bits, m2._mant37(x.device), m2._ts32())
-                return self.proj.quant_forward(out.view(B, N, C), addend=residual)
-        elif _attn_core_on(be, N, self.head_dim):
-            out = be.attn_core(qp, kp, vp, N, self.head_dim, H, hm, sA, sB, sV, self.scale, a_scale, qv, m2.A_quantizer.n_bits,
-                               m2._mant37(x.device), m2._ts32())
-            return self.proj.quant_forward(out.view(B, N, C), addend=residual)
-        scores = be.gemm_out(I8, qp, kp, N, N, B * H, hm, Strided(sA, g=pg), Strided(sB, g=pg), None)
-        soft = be.softmax_adalog_pack_long if long_rows else be.softmax_adalog_pack
-        ap = soft(scores, self.scale, a_scale, qv, m2.A_quantizer.n_bits, m2._mant37(x.device))
-        out = be.gemm_out(BF16, ap, vp, N, self.head_dim, B * H, hm, Strided(a_scale), Strided(sV, g=pg), None, sa_mul=m2._ts32(),
-                          heads_last=H)
+            qp, kp, vp = be.attn_split_pack_ex(qkv, H, p.q_par, p.k_par, p.v_par, hm > 1, D=D)
+        out = _quant_attn_core(be, qp, kp, vp, B * H, N, D, H, hm, p, mul=self.scale)
         return self.proj.quant_forward(out.view(B, N, C), addend=residual)
 
     def forward(self, x, residual=None):
@@ -359,24 +392,14 @@ class WindowAttention(nn.Module):
         """quant_forward of the window attention on the fused route (SwinTransformerBlock._fused_attn_residual): Attention's conditions
         with head dimension a multiple of 16 up to 64, <= 256 tokens per window, and qkv / proj on the generated-A GEMM with row maps.
         x: the tokens in front of qkv (any order)."""
-        from ..quant_layers.matmul import AsymmetricallyBatchingQuantMatMul, PostSoftmaxAsymmetricallyBatchingQuantMatMul
-        from ..quantizers.uniform import UniformQuantizer
-        m1, m2 = self.matmul1, self.matmul2
         D, N = self.dim // self.num_heads, self.window_area
         if not (QF_FUSED and not torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32 and D % 16 == 0 and D <= 64
                 and N <= 256 and isinstance(self.attn_drop, nn.Identity) and isinstance(self.proj_drop, nn.Identity)):
             return False
         be = _backend.get()
-        if not (getattr(be, "QF_SWIN", False) and be.softmax_adalog_pack_ok(N)):
-            return False
-        if not (type(m1) is AsymmetricallyBatchingQuantMatMul and type(m2) is PostSoftmaxAsymmetricallyBatchingQuantMatMul
-                and all(_plain_quant_forward(m) for m in (self.qkv, self.proj, m1, m2))
-                and all(hasattr(m, "rows_ok") and m.rows_ok(x) for m in (self.qkv, self.proj))):
-            return False
-        qs = (m1.A_quantizer, m1.B_quantizer, m2.B_quantizer)
-        return (all(isinstance(q, UniformQuantizer) and 2 <= q.n_bits <= 7 and not q.training_mode for q in qs)
-                and not m2.A_quantizer.training_mode and m1._heads() == m2._heads() and m2.A_quantizer.scale.numel() == 1
-                and m1.packed_codes_fit() and m2.packed_codes_fit())
+        return (getattr(be, "QF_SWIN", False) and be.softmax_adalog_pack_ok(N)
+                and _fused_products_ok(self.qkv, self.proj, self.matmul1, self.matmul2)
+                and all(hasattr(m, "rows_ok") and m.rows_ok(x) for m in (self.qkv, self.proj)))
 
     def _fused_quant_forward(self, x2, rows, period, mask, residual):
         """The window attention in quant_forward mode (reference utils/wrap_net.py:35-52, every product in quant_forward) as five
@@ -384,32 +407,17 @@ class WindowAttention(nn.Module):
         split + q * scale + three input quantisers + operand packs; q . k^T (int8 MFMA, the module route's call); relative-position bias
         + shift mask + softmax + AdaLog quantiser + pack; softmax . v (bf16 MFMA) written as [B_, N, H, D]; proj with its rows scattered
         back through ``rows`` and ``residual`` added in its epilogue.  x2, residual: [images * period, C] in token order -> same."""
-        from ..ops import BF16, I8, Strided
         be = _backend.get()
         C, H, N = self.dim, self.num_heads, self.window_area
         D = C // H
         Bw = x2.shape[0] // N
-        m1, m2 = self.matmul1, self.matmul2
+        m1 = self.matmul1
         qkv = self.qkv.quant_forward_rows(x2, a_rows=rows, period=period)
         hm = m1._heads()
-        pg = 1 if hm > 1 else 0
-        sA, zA = m1._q_params(m1.A_quantizer)
-        sB, zB = m1._q_params(m1.B_quantizer)
-        sV, zV = m2._q_params(m2.B_quantizer)
-        qp, kp, vp = be.attn_split_pack_ex(qkv.view(Bw, N, 3 * C), H, (sA, zA, m1.A_quantizer.n_bits), (sB, zB, m1.B_quantizer.n_bits),
-                                           (sV, zV, m2.B_quantizer.n_bits), hm > 1, D=D, q_mul=self.scale)
-        if m2._q_host is None:
-            m2._q_host = int(m2.A_quantizer.q.item())
-        qv = _search.const_tensor([float(m2._q_host)], x2.device)
-        a_scale = m2.A_quantizer.scale.data.view(-1)
-        if _attn_core_on(be, N, D):
-            out = be.attn_core(qp, kp, vp, N, D, H, hm, sA, sB, sV, 1.0, a_scale, qv, m2.A_quantizer.n_bits, m2._mant37(x2.device),
-                               m2._ts32(), table=self.relative_position_bias_table.data, index=self.relative_position_index, mask=mask)
-            return self.proj.quant_forward_rows(out.view(Bw * N, C), o_rows=rows, period=period, addend=residual)
-        scores = be.gemm_out(I8, qp, kp, N, N, Bw * H, hm, Strided(sA, g=pg), Strided(sB, g=pg), None)
-        ap = be.softmax_bias_adalog_pack(scores, H, self.relative_position_bias_table.data, self.relative_position_index, mask,
-                                         a_scale, qv, m2.A_quantizer.n_bits, m2._mant37(x2.device))
-        out = be.gemm_out(BF16, ap, vp, N, D, Bw * H, hm, Strided(a_scale), Strided(sV, g=pg), None, sa_mul=m2._ts32(), heads_last=H)
+        p = _core_params(m1, self.matmul2, x2.device)
+        qp, kp, vp = be.attn_split_pack_ex(qkv.view(Bw, N, 3 * C), H, p.q_par, p.k_par, p.v_par, hm > 1, D=D, q_mul=self.scale)
+        out = _quant_attn_core(be, qp, kp, vp, Bw * H, N, D, H, hm, p,
+                               bias=(self.relative_position_bias_table.data, self.relative_position_index, mask))
         return self.proj.quant_forward_rows(out.view(Bw * N, C), o_rows=rows, period=period, addend=residual)
 
     def forward(self, x, mask=None):
