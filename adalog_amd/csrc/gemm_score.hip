@@ -169,15 +169,31 @@ static Layout layout_of(int M, int N, int C, int G, int gmod, int ref_div, int r
     return L;
 }
 
+// The reference comes in columns of 64, 128 or 256 candidates
+static bool ref_div_ok(int N, int ref_div) { return (ref_div == 64 || ref_div == 128 || ref_div == 256) && N % ref_div == 0; }
+
+// what the loader-wave group kernels ask of a launch whatever their operands: 5..7 row blocks, many groups, per-head sums that fit
+// LDS, plain column factors, a reference group within 32-bit addressing
+static bool grp_shape_ok(int M, int N, int G, int gmod, int ref_div, const float* bias, const float* row_scale, int64_t sb_n, int64_t ref_cs) {
+    static const int use_grp = getenv("ADALOG_GEMM_GRP") ? atoi(getenv("ADALOG_GEMM_GRP")) : 1;
+    return use_grp && M > 128 && M <= 224 && G >= 8 && gmod <= 16 && !bias && !row_scale && sb_n == 0 && ref_div_ok(N, ref_div) &&
+           (int64_t)(N / ref_div) * ref_cs * 4 < ((int64_t)1 << 31);
+}
+// ... and the window kernels: at most 64 rows, hundreds of groups or more, at least as many waves as heads per image (every
+// participating wave owns one head), a reference slice that fits a wave's LDS
+static bool win_shape_ok(int M, int N, int G, int gmod, int ref_div, const float* bias, const float* row_scale, int64_t sb_n, int64_t ref_cs,
+                         int wgs) {
+    static const int use_win = getenv("ADALOG_GEMM_WIN") ? atoi(getenv("ADALOG_GEMM_WIN")) : 1;
+    return use_win && M >= 4 && M <= 64 && G >= 256 && gmod <= 32 && !bias && !row_scale && sb_n == 0 && ref_div_ok(N, ref_div) &&
+           N / ref_div <= 64 && wgs * 4 >= gmod && ref_cs >= M;
+}
+
 // Launch-time choice of the group kernel (it shares the streaming kernel's accumulator layout, so the layout query does
 // not need to know): int8 or fp8, one K-step, 5..7 row blocks, many groups (up to 16 heads per image: the per-head fp64
 // sums live in LDS), plain column factors.
 static bool grp_ok(int dtype, int M, int N, int G, int gmod, int ref_div, int64_t kvalid_bytes, const float* bias,
                    const float* row_scale, int64_t sb_n, int64_t ref_cs) {
-    static const int use_grp = getenv("ADALOG_GEMM_GRP") ? atoi(getenv("ADALOG_GEMM_GRP")) : 1;
-    return use_grp && (dtype == 0 || dtype == 3) && kvalid_bytes <= BK3 && M > 128 && M <= 224 && G >= 8 && gmod <= 16 && !bias && !row_scale &&
-           sb_n == 0 && (ref_div == 64 || ref_div == 128 || ref_div == 256) && N % ref_div == 0 &&
-           (int64_t)(N / ref_div) * ref_cs * 4 < ((int64_t)1 << 31);
+    return (dtype == 0 || dtype == 3) && kvalid_bytes <= BK3 && grp_shape_ok(M, N, G, gmod, ref_div, bias, row_scale, sb_n, ref_cs);
 }
 
 static bool grpw_on() {
@@ -188,19 +204,13 @@ static bool grpw_on() {
 // ... and of its several-K-steps form: bf16, exactly 7 K-steps (K = 193..224 elements: the 197 tokens of a 224 x 224 ViT).
 static bool grpk_ok(int dtype, int M, int N, int G, int gmod, int ref_div, int64_t kvalid_bytes, const float* bias,
                     const float* row_scale, int64_t sb_n, int64_t ref_cs) {
-    static const int use_grp = getenv("ADALOG_GEMM_GRP") ? atoi(getenv("ADALOG_GEMM_GRP")) : 1;
-    return use_grp && dtype == 1 && kvalid_bytes > 6 * BK3 && kvalid_bytes <= 7 * BK3 && M > 128 && M <= 224 && G >= 8 && gmod <= 16 &&
-           !bias && !row_scale && sb_n == 0 && (ref_div == 64 || ref_div == 128 || ref_div == 256) && N % ref_div == 0 &&
-           (int64_t)(N / ref_div) * ref_cs * 4 < ((int64_t)1 << 31);
+    return dtype == 1 && kvalid_bytes > 6 * BK3 && kvalid_bytes <= 7 * BK3 && grp_shape_ok(M, N, G, gmod, ref_div, bias, row_scale, sb_n, ref_cs);
 }
 
 // ... and of its mixed form (dtype 4: bf16 rows x fp8 columns): exactly 4 K-steps of 64 elements (K = 193..256).
 static bool grpk8_ok(int M, int N, int G, int gmod, int ref_div, int64_t k_valid, const float* bias, const float* row_scale,
                      int64_t sb_n, int64_t ref_cs) {
-    static const int use_grp = getenv("ADALOG_GEMM_GRP") ? atoi(getenv("ADALOG_GEMM_GRP")) : 1;
-    return use_grp && k_valid > 192 && k_valid <= 256 && M > 128 && M <= 224 && G >= 8 && gmod <= 16 && !bias && !row_scale &&
-           sb_n == 0 && (ref_div == 64 || ref_div == 128 || ref_div == 256) && N % ref_div == 0 &&
-           (int64_t)(N / ref_div) * ref_cs * 4 < ((int64_t)1 << 31);
+    return k_valid > 192 && k_valid <= 256 && grp_shape_ok(M, N, G, gmod, ref_div, bias, row_scale, sb_n, ref_cs);
 }
 
 // ... and of the trimmed-K form of the mixed kernel (k_gemm_grpk8t): rows of 208 elements, K = 193..208
@@ -212,21 +222,44 @@ static bool grpk8t_ok(int M, int N, int G, int gmod, int ref_div, int64_t k_vali
 // ... mixed operands, window family: K <= 64 elements (one 64-byte fp8 K-step against 128-byte bf16 rows), at most 64 rows.
 static bool winb_ok(int M, int N, int G, int gmod, int ref_div, int64_t k_valid, const float* bias, const float* row_scale, int64_t sb_n,
                     int64_t ref_cs, int wgs) {
-    static const int use_win = getenv("ADALOG_GEMM_WIN") ? atoi(getenv("ADALOG_GEMM_WIN")) : 1;
-    const int n_eff = ref_div > 0 ? N / ref_div : 0;
-    return use_win && k_valid >= 1 && k_valid <= 64 && M >= 4 && M <= 64 && G >= 256 && gmod <= 32 && !bias && !row_scale && sb_n == 0 &&
-           (ref_div == 64 || ref_div == 128 || ref_div == 256) && N % ref_div == 0 && n_eff <= 64 && wgs * 4 >= gmod && ref_cs >= M;
+    return k_valid >= 1 && k_valid <= 64 && win_shape_ok(M, N, G, gmod, ref_div, bias, row_scale, sb_n, ref_cs, wgs);
 }
 
 // ... and of the window kernel: int8 or fp8, one K-step, at most 64 rows, hundreds of groups or more, at least as many waves as
 // heads per image (every participating wave owns one head).
 static bool win_ok(int dtype, int M, int N, int G, int gmod, int ref_div, int64_t kvalid_bytes, const float* bias,
                    const float* row_scale, int64_t sb_n, int64_t ref_cs, int wgs) {
-    static const int use_win = getenv("ADALOG_GEMM_WIN") ? atoi(getenv("ADALOG_GEMM_WIN")) : 1;
-    const int n_eff = ref_div > 0 ? N / ref_div : 0;
-    return use_win && (dtype == 0 || dtype == 3) && kvalid_bytes <= BK3 && M >= 4 && M <= 64 && G >= 256 && gmod <= 32 && !bias &&
-           !row_scale && sb_n == 0 && (ref_div == 64 || ref_div == 128 || ref_div == 256) && N % ref_div == 0 && n_eff <= 64 &&
-           wgs * 4 >= gmod && ref_cs >= M;
+    return (dtype == 0 || dtype == 3) && kvalid_bytes <= BK3 && win_shape_ok(M, N, G, gmod, ref_div, bias, row_scale, sb_n, ref_cs, wgs);
+}
+
+// Launch of one instantiation K of the attention group / window kernels: raise its dynamic-LDS limit once per device (max_lds = 0:
+// the default limit is enough), note the label for adalog_last_kernel, launch.  K is a template argument, so the once-per-device
+// state is one per instantiation.
+template <auto K>
+static int launch_attn(const char* label, int max_lds, int wgs, int threads, size_t shm, hipStream_t st, const GemmArgs& p) {
+    if (max_lds > 0) {
+        static unsigned long long attr_dev = 0;
+        const hipError_t e = adalog_max_lds(reinterpret_cast<const void*>(K), max_lds, &attr_dev);
+        if (e != hipSuccess) { adalog_set_error("hipFuncSetAttribute", e); return (int)e; }
+    }
+    adalog_note_kernel(label);
+    hipLaunchKernelGGL(K, dim3((unsigned)wgs), dim3((unsigned)threads), shm, st, p);
+    return 0;
+}
+// candidates per reference column -> 32-column blocks per reference column, as a compile-time constant: f(integral_constant<int, NJ>)
+template <class F>
+static int with_nj(int ref_div, F&& f) {
+    if (ref_div == 64) return f(std::integral_constant<int, 2>{});
+    if (ref_div == 128) return f(std::integral_constant<int, 4>{});
+    return f(std::integral_constant<int, 8>{});
+}
+// items of the loader-wave group kernels: a group's NB 32-column blocks in chunks of CB (a multiple of 8: chunks start on a reference
+// column), about three items per workgroup
+static void grp_chunks(GemmArgs& p, int N, int wgs, int G) {
+    const int NB = N / 32;
+    const int nch0 = cdiv((int64_t)3 * wgs, G);
+    const int CB = cdiv(cdiv(NB, nch0 < 1 ? 1 : nch0), 8) * 8;
+    p.slab_R = CB; p.slab_U = cdiv(NB, CB);
 }
 
 // M, N: GEMM rows / columns (N includes the candidate factor when ref_div > 1).  Outputs the partial-buffer layout
@@ -371,52 +404,28 @@ static int gemm_score_impl(int dtype, const void* A, const void* B, int64_t sAc,
             const int n_eff = N / ref_div;
             const size_t ref_lds = (size_t)4 * n_eff * 64 * 4, acc_lds = (size_t)gmod * 256 * 8;
             const size_t shm_w = ref_lds > acc_lds ? ref_lds : acc_lds;
-#define LAUNCH_WINB(NJV)                                                                                          \
-            do {                                                                                                  \
-                static unsigned long long attr_dev = 0; \
-                { hipError_t ea__ = adalog_max_lds(reinterpret_cast<const void*>(&k_gemm_winb<NJV>), (int)(80 * 1024), &attr_dev); \
-                  if (ea__ != hipSuccess) { adalog_set_error("hipFuncSetAttribute", ea__); return (int)ea__; } } \
-                adalog_note_kernel("k_gemm_winb<bf16xfp8>");                                                      \
-                hipLaunchKernelGGL((k_gemm_winb<NJV>), dim3((unsigned)L.wgs), dim3(256), shm_w, st, p);           \
-            } while (0)
-            if (ref_div == 64) LAUNCH_WINB(2); else if (ref_div == 128) LAUNCH_WINB(4); else LAUNCH_WINB(8);
-#undef LAUNCH_WINB
+            if (const int e = with_nj(ref_div, [&](auto nj) {
+                    return launch_attn<k_gemm_winb<decltype(nj)::value>>("k_gemm_winb<bf16xfp8>", 80 * 1024, L.wgs, 256, shm_w, st, p);
+                })) return e;
             ADALOG_LAUNCH_CHECK("adalog_gemm_score (bf16 x fp8, windows)");
             return 0;
         }
-        const int NB = N / 32;
-        const int nch0 = cdiv((int64_t)3 * L.wgs, G);
-        const int CB = cdiv(cdiv(NB, nch0 < 1 ? 1 : nch0), 8) * 8;
-        p.slab_R = CB; p.slab_U = cdiv(NB, CB);
+        grp_chunks(p, N, L.wgs, G);
         if (ktrim) {
             // rows of 13 sixteen-element slots: 13 MFMAs per block hold every non-zero product of K <= 200, 14 of K <= 208
             const size_t shm_t = (size_t)3 * 4 * 32 * 208 + (size_t)7 * ref_div * 4 + (size_t)gmod * 256 * 8;   // 3 stages of 4 blocks x 208 bytes
-#define LAUNCH_GRPK8T(NJV, NKSV)                                                                                  \
-            do {                                                                                                  \
-                static unsigned long long attr_dev = 0; \
-                { hipError_t ea__ = adalog_max_lds(reinterpret_cast<const void*>(&k_gemm_grpk8t<NJV, NKSV>), (int)(160 * 1024), &attr_dev); \
-                  if (ea__ != hipSuccess) { adalog_set_error("hipFuncSetAttribute", ea__); return (int)ea__; } } \
-                adalog_note_kernel(NKSV == 13 ? "k_gemm_grpk8t<13,bf16xfp8>" : "k_gemm_grpk8t<14,bf16xfp8>");     \
-                hipLaunchKernelGGL((k_gemm_grpk8t<NJV, NKSV>), dim3((unsigned)L.wgs), dim3(512), shm_t, st, p);   \
-            } while (0)
-#define LAUNCH_GRPK8T_NJ(NKSV) do { if (ref_div == 64) LAUNCH_GRPK8T(2, NKSV); else if (ref_div == 128) LAUNCH_GRPK8T(4, NKSV); else LAUNCH_GRPK8T(8, NKSV); } while (0)
-            if (k_valid <= 200) LAUNCH_GRPK8T_NJ(13); else LAUNCH_GRPK8T_NJ(14);
-#undef LAUNCH_GRPK8T_NJ
-#undef LAUNCH_GRPK8T
+            if (const int e = with_nj(ref_div, [&](auto nj) {
+                    constexpr int NJ = decltype(nj)::value;
+                    return k_valid <= 200 ? launch_attn<k_gemm_grpk8t<NJ, 13>>("k_gemm_grpk8t<13,bf16xfp8>", 160 * 1024, L.wgs, 512, shm_t, st, p)
+                                          : launch_attn<k_gemm_grpk8t<NJ, 14>>("k_gemm_grpk8t<14,bf16xfp8>", 160 * 1024, L.wgs, 512, shm_t, st, p);
+                })) return e;
             ADALOG_LAUNCH_CHECK("adalog_gemm_score (bf16 x fp8, trimmed K)");
             return 0;
         }
         const size_t shm = (size_t)3 * 4 * 4 * 32 * BK3 + (size_t)7 * ref_div * 4 + (size_t)gmod * 256 * 8;   // 3 stages of 4 K-steps x 4 blocks
-#define LAUNCH_GRPK8(NJV)                                                                                         \
-        do {                                                                                                      \
-            static unsigned long long attr_dev = 0; \
-            { hipError_t ea__ = adalog_max_lds(reinterpret_cast<const void*>(&k_gemm_grpk8<NJV, 4>), (int)(160 * 1024), &attr_dev); \
-              if (ea__ != hipSuccess) { adalog_set_error("hipFuncSetAttribute", ea__); return (int)ea__; } } \
-            adalog_note_kernel("k_gemm_grpk8<bf16xfp8>");                                                         \
-            hipLaunchKernelGGL((k_gemm_grpk8<NJV, 4>), dim3((unsigned)L.wgs), dim3(512), shm, st, p);             \
-        } while (0)
-        if (ref_div == 64) LAUNCH_GRPK8(2); else if (ref_div == 128) LAUNCH_GRPK8(4); else LAUNCH_GRPK8(8);
-#undef LAUNCH_GRPK8
+        if (const int e = with_nj(ref_div, [&](auto nj) {
+                return launch_attn<k_gemm_grpk8<decltype(nj)::value, 4>>("k_gemm_grpk8<bf16xfp8>", 160 * 1024, L.wgs, 512, shm, st, p);
+            })) return e;
         ADALOG_LAUNCH_CHECK("adalog_gemm_score (bf16 x fp8)");
         return 0;
     }
@@ -507,25 +516,14 @@ static int gemm_score_impl(int dtype, const void* A, const void* B, int64_t sAc,
         const int n_eff = N / ref_div;
         const size_t ref_lds = (size_t)4 * n_eff * 64 * 4, acc_lds = (size_t)gmod * 256 * 8;
         const size_t shm = ref_lds > acc_lds ? ref_lds : acc_lds;
-#define LAUNCH_WIN(NJV, DTV)                                                                                      \
-        do {                                                                                                      \
-            static unsigned long long attr_dev = 0; \
-            { hipError_t ea__ = adalog_max_lds(reinterpret_cast<const void*>(&k_gemm_win<NJV, DTV>), (int)(80 * 1024), &attr_dev); \
-              if (ea__ != hipSuccess) { adalog_set_error("hipFuncSetAttribute", ea__); return (int)ea__; } } \
-            if (gen) {                                                                                            \
-                static unsigned long long attr_gen = 0; \
-                { hipError_t ea__ = adalog_max_lds(reinterpret_cast<const void*>(&k_gemm_win<NJV, DTV, true>), (int)(80 * 1024), &attr_gen); \
-                  if (ea__ != hipSuccess) { adalog_set_error("hipFuncSetAttribute", ea__); return (int)ea__; } } \
-                adalog_note_kernel(DTV == 3 ? "k_gemm_win_gen<fp8>" : "k_gemm_win_gen<i8>");                       \
-                hipLaunchKernelGGL((k_gemm_win<NJV, DTV, true>), dim3((unsigned)L.wgs), dim3(256), shm, st, p);   \
-            } else {                                                                                              \
-                adalog_note_kernel(DTV == 3 ? "k_gemm_win<fp8>" : "k_gemm_win<i8>");                               \
-                hipLaunchKernelGGL((k_gemm_win<NJV, DTV>), dim3((unsigned)L.wgs), dim3(256), shm, st, p);         \
-            }                                                                                                     \
-        } while (0)
-        if (dtype == 3) { if (ref_div == 64) LAUNCH_WIN(2, 3); else if (ref_div == 128) LAUNCH_WIN(4, 3); else LAUNCH_WIN(8, 3); }
-        else { if (ref_div == 64) LAUNCH_WIN(2, 0); else if (ref_div == 128) LAUNCH_WIN(4, 0); else LAUNCH_WIN(8, 0); }
-#undef LAUNCH_WIN
+        if (const int e = with_nj(ref_div, [&](auto nj) {
+                constexpr int NJ = decltype(nj)::value;
+                if (dtype == 3)
+                    return gen ? launch_attn<k_gemm_win<NJ, 3, true>>("k_gemm_win_gen<fp8>", 80 * 1024, L.wgs, 256, shm, st, p)
+                               : launch_attn<k_gemm_win<NJ, 3>>("k_gemm_win<fp8>", 80 * 1024, L.wgs, 256, shm, st, p);
+                return gen ? launch_attn<k_gemm_win<NJ, 0, true>>("k_gemm_win_gen<i8>", 80 * 1024, L.wgs, 256, shm, st, p)
+                           : launch_attn<k_gemm_win<NJ, 0>>("k_gemm_win<i8>", 80 * 1024, L.wgs, 256, shm, st, p);
+            })) return e;
     } else if (L.stream && !out && L.acc && grp_ok(dtype, M, N, G, gmod, ref_div, p.Kvb, bias, row_scale, sb_n, ref_cs) &&
                grpw_on() && L.wgs * 4 >= gmod && ref_cs >= M) {
         // wave-private group kernel (q.k^T searches): a wave per (group, chunk of reference columns), no barrier in the loop
@@ -537,54 +535,30 @@ static int gemm_score_impl(int dtype, const void* A, const void* B, int64_t sAc,
         p.slab_R = cbc; p.slab_U = cdiv(n_eff, cbc);
         const size_t ref_lds = (size_t)4 * 2 * 224 * 4, acc_lds = (size_t)gmod * 256 * 8;
         const size_t shm = ref_lds > acc_lds ? ref_lds : acc_lds;
-#define LAUNCH_GRPW(NJV, DTV)                                                                                     \
-        do {                                                                                                      \
-            if (gen) {                                                                                            \
-                adalog_note_kernel(DTV == 3 ? "k_gemm_grpw_gen<fp8>" : "k_gemm_grpw_gen<i8>");                     \
-                hipLaunchKernelGGL((k_gemm_grpw<NJV, DTV, true>), dim3((unsigned)L.wgs), dim3(256), shm, st, p);  \
-            } else {                                                                                              \
-                adalog_note_kernel(DTV == 3 ? "k_gemm_grpw<fp8>" : "k_gemm_grpw<i8>");                             \
-                hipLaunchKernelGGL((k_gemm_grpw<NJV, DTV>), dim3((unsigned)L.wgs), dim3(256), shm, st, p);        \
-            }                                                                                                     \
-        } while (0)
-        if (dtype == 3) { if (ref_div == 64) LAUNCH_GRPW(2, 3); else if (ref_div == 128) LAUNCH_GRPW(4, 3); else LAUNCH_GRPW(8, 3); }
-        else { if (ref_div == 64) LAUNCH_GRPW(2, 0); else if (ref_div == 128) LAUNCH_GRPW(4, 0); else LAUNCH_GRPW(8, 0); }
-#undef LAUNCH_GRPW
+        if (const int e = with_nj(ref_div, [&](auto nj) {             // (no LDS-limit call: 3.5 KiB, or gmod x 2 KiB <= 32 KiB)
+                constexpr int NJ = decltype(nj)::value;
+                if (dtype == 3)
+                    return gen ? launch_attn<k_gemm_grpw<NJ, 3, true>>("k_gemm_grpw_gen<fp8>", 0, L.wgs, 256, shm, st, p)
+                               : launch_attn<k_gemm_grpw<NJ, 3>>("k_gemm_grpw<fp8>", 0, L.wgs, 256, shm, st, p);
+                return gen ? launch_attn<k_gemm_grpw<NJ, 0, true>>("k_gemm_grpw_gen<i8>", 0, L.wgs, 256, shm, st, p)
+                           : launch_attn<k_gemm_grpw<NJ, 0>>("k_gemm_grpw<i8>", 0, L.wgs, 256, shm, st, p);
+            })) return e;
     } else if (L.stream && !out && L.acc && grp_ok(dtype, M, N, G, gmod, ref_div, p.Kvb, bias, row_scale, sb_n, ref_cs)) {
         // group kernel (q.k^T searches): same accumulator layout and workgroup count as the streaming kernel
-        const int NB = N / 32;
-        const int nch0 = cdiv((int64_t)3 * L.wgs, G);
-        const int CB = cdiv(cdiv(NB, nch0 < 1 ? 1 : nch0), 8) * 8;
-        p.slab_R = CB; p.slab_U = cdiv(NB, CB);
+        grp_chunks(p, N, L.wgs, G);
         const size_t shm = (size_t)3 * 8 * 32 * BK3 + 7 * 256 * 4 + (size_t)gmod * 256 * 8;
-#define LAUNCH_GRP(NJV, DTV)                                                                                      \
-        do {                                                                                                      \
-            static unsigned long long attr_dev = 0; \
-            { hipError_t ea__ = adalog_max_lds(reinterpret_cast<const void*>(&k_gemm_grp<NJV, DTV>), (int)(96 * 1024), &attr_dev); \
-              if (ea__ != hipSuccess) { adalog_set_error("hipFuncSetAttribute", ea__); return (int)ea__; } } \
-            adalog_note_kernel(DTV == 3 ? "k_gemm_grp<fp8>" : "k_gemm_grp<i8>");                                   \
-            hipLaunchKernelGGL((k_gemm_grp<NJV, DTV>), dim3((unsigned)L.wgs), dim3(512), shm, st, p);             \
-        } while (0)
-        if (dtype == 3) { if (ref_div == 64) LAUNCH_GRP(2, 3); else if (ref_div == 128) LAUNCH_GRP(4, 3); else LAUNCH_GRP(8, 3); }
-        else { if (ref_div == 64) LAUNCH_GRP(2, 0); else if (ref_div == 128) LAUNCH_GRP(4, 0); else LAUNCH_GRP(8, 0); }
-#undef LAUNCH_GRP
+        if (const int e = with_nj(ref_div, [&](auto nj) {
+                constexpr int NJ = decltype(nj)::value;
+                return dtype == 3 ? launch_attn<k_gemm_grp<NJ, 3>>("k_gemm_grp<fp8>", 96 * 1024, L.wgs, 512, shm, st, p)
+                                  : launch_attn<k_gemm_grp<NJ, 0>>("k_gemm_grp<i8>", 96 * 1024, L.wgs, 512, shm, st, p);
+            })) return e;
     } else if (L.stream && !out && L.acc && grpk_ok(dtype, M, N, G, gmod, ref_div, p.Kvb, bias, row_scale, sb_n, ref_cs)) {
         // group kernel, 7 K-steps (softmax.v weight search)
-        const int NB = N / 32;
-        const int nch0 = cdiv((int64_t)3 * L.wgs, G);
-        const int CB = cdiv(cdiv(NB, nch0 < 1 ? 1 : nch0), 8) * 8;
-        p.slab_R = CB; p.slab_U = cdiv(NB, CB);
+        grp_chunks(p, N, L.wgs, G);
         const size_t shm = (size_t)3 * 7 * 2 * 32 * BK3 + (size_t)7 * ref_div * 4 + (size_t)gmod * 256 * 8;
-#define LAUNCH_GRPK(NJV)                                                                                          \
-        do {                                                                                                      \
-            static unsigned long long attr_dev = 0; \
-            { hipError_t ea__ = adalog_max_lds(reinterpret_cast<const void*>(&k_gemm_grpk<NJV, 7>), (int)(160 * 1024), &attr_dev); \
-              if (ea__ != hipSuccess) { adalog_set_error("hipFuncSetAttribute", ea__); return (int)ea__; } } \
-            adalog_note_kernel("k_gemm_grpk<bf16>");                                                              \
-            hipLaunchKernelGGL((k_gemm_grpk<NJV, 7>), dim3((unsigned)L.wgs), dim3(512), shm, st, p);              \
-        } while (0)
-        if (ref_div == 64) LAUNCH_GRPK(2); else if (ref_div == 128) LAUNCH_GRPK(4); else LAUNCH_GRPK(8);
-#undef LAUNCH_GRPK
+        if (const int e = with_nj(ref_div, [&](auto nj) {
+                return launch_attn<k_gemm_grpk<decltype(nj)::value, 7>>("k_gemm_grpk<bf16>", 160 * 1024, L.wgs, 512, shm, st, p);
+            })) return e;
     } else if (L.stream && !out) {
         // persistent streaming kernel: two (wide form: one) workgroups per CU walk the tile list
         {   // m-tiles per group: the group's A rows are re-read once per n-tile (from L2 / the 256 MiB Infinity Cache), the B
@@ -868,17 +842,11 @@ extern "C" int adalog_gemm_score_avq(const void* A, int64_t sAg, int M, int N, i
     const size_t acc_b = (size_t)gmod * 256 * 8;
     const size_t shm = lut_b + rows_b > acc_b ? lut_b + rows_b : acc_b;
     hipStream_t st = (hipStream_t)stream;
-#define LAUNCH_AVQ(NKSV, RBV)                                                                                     \
-    do {                                                                                                          \
-        static unsigned long long attr_dev = 0; \
-        { hipError_t ea__ = adalog_max_lds(reinterpret_cast<const void*>(&k_gemm_avq<4, NKSV, RBV>), (int)(80 * 1024), &attr_dev); \
-          if (ea__ != hipSuccess) { adalog_set_error("hipFuncSetAttribute", ea__); return (int)ea__; } } \
-        adalog_note_kernel(NKSV == 13 ? "k_gemm_avq<13,bf16>" : "k_gemm_avq<4,bf16>");                              \
-        hipLaunchKernelGGL((k_gemm_avq<4, NKSV, RBV>), dim3((unsigned)L.wgs), dim3(256), shm, st, p);             \
-    } while (0)
-    if (nks == 13) { if (M > 32) LAUNCH_AVQ(13, 2); else LAUNCH_AVQ(13, 1); }
-    else { if (M > 32) LAUNCH_AVQ(4, 2); else LAUNCH_AVQ(4, 1); }
-#undef LAUNCH_AVQ
+    const int e = nks == 13 ? (M > 32 ? launch_attn<k_gemm_avq<4, 13, 2>>("k_gemm_avq<13,bf16>", 80 * 1024, L.wgs, 256, shm, st, p)
+                                      : launch_attn<k_gemm_avq<4, 13, 1>>("k_gemm_avq<13,bf16>", 80 * 1024, L.wgs, 256, shm, st, p))
+                            : (M > 32 ? launch_attn<k_gemm_avq<4, 4, 2>>("k_gemm_avq<4,bf16>", 80 * 1024, L.wgs, 256, shm, st, p)
+                                      : launch_attn<k_gemm_avq<4, 4, 1>>("k_gemm_avq<4,bf16>", 80 * 1024, L.wgs, 256, shm, st, p));
+    if (e) return e;
     ADALOG_LAUNCH_CHECK("adalog_gemm_score_avq");
     return 0;
 }
