@@ -72,17 +72,10 @@ __global__ __launch_bounds__(256) void k_sel_hist(const float* __restrict__ x, i
     }
 }
 
-// one wavefront per (segment, rank): each lane takes four bins, a 64-lane scan locates the bin holding the rank, the
-// state descends one byte, and the histogram is cleared for the next pass (a single thread walking 256 bins took 30 us)
-__global__ __launch_bounds__(256) void k_sel_pick(SelState* st, unsigned* hist, int S, int R, int pass,
-                                                  const float* __restrict__ qfrac, int positive_only) {
-    const int lane = threadIdx.x & 63;
-    const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (i >= S * R) return;
-    uint4* h4 = reinterpret_cast<uint4*>(hist + (int64_t)i * 256);
-    const uint4 c = h4[lane];
-    h4[lane] = make_uint4(0u, 0u, 0u, 0u);
-    SelState s = st[i];
+// The descent by one byte as a device function of ONE wavefront over a 256-bin histogram held in four values per lane (bins
+// 4 lane .. 4 lane + 3), wherever it was read from (global memory: k_sel_pick; LDS: the one-block-per-segment kernel; global memory
+// at agent scope: the last block of a segment in k_sel_hist_pick).  A 64-lane scan locates the lane whose bins hold the rank.
+__device__ __forceinline__ SelState pick_wave(uint4 c, SelState s, int pass, int positive_only, float qf, int lane) {
     const int64_t own = (int64_t)c.x + c.y + c.z + c.w;
     int64_t incl = own;
 #pragma unroll
@@ -93,10 +86,11 @@ __global__ __launch_bounds__(256) void k_sel_pick(SelState* st, unsigned* hist, 
     const int64_t total = __shfl(incl, 63);
     if (pass == 0 && positive_only) {
         // ranks = clamp(ceil(count * q) - 1, 0)      (linear.py:785-790; counts.float() * q in fp32)
-        const float cq = ceilf((float)total * qfrac[i % R]);
+        const float cq = ceilf((float)total * qf);
         const int64_t rk = (int64_t)cq - 1;
         // counts.float() rounds to even above 2^24 positives: the rank can land ONE PAST the last positive value, where the
-        // reference's sorted tensor holds NaN and the result is masked to 0 (linear.py:794-797) -- same here (-1 -> 0)
+        // reference's sorted tensor holds the NaN of a non-positive entry and the result is masked to 0 (linear.py:794-797) -- same
+        // here (-1 -> 0).  (On a row without any non-positive entry the reference's gather raises; the result here is 0 as well.)
         s.remaining = (total == 0 || rk >= total) ? -1 : (rk < 0 ? 0 : rk);
     }
     if (s.remaining >= 0) {
@@ -115,43 +109,21 @@ __global__ __launch_bounds__(256) void k_sel_pick(SelState* st, unsigned* hist, 
         s.prefix = (s.prefix << 8) | (unsigned)b;
         s.remaining -= cum;
     }
-    if (lane == 0) st[i] = s;
+    return s;
 }
 
-// The descent of k_sel_pick as a device function of ONE wavefront over a 256-bin histogram held in four values per lane (bins
-// 4 lane .. 4 lane + 3), wherever it was read from (LDS: the one-block-per-segment kernel; global memory at agent scope: the last
-// block of a segment in k_sel_hist_pick).
-__device__ __forceinline__ SelState pick_wave(uint4 c, SelState s, int pass, int positive_only, float qf, int lane) {
-    const int64_t own = (int64_t)c.x + c.y + c.z + c.w;
-    int64_t incl = own;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int64_t up = __shfl_up(incl, d);
-        if (lane >= d) incl += up;
-    }
-    const int64_t total = __shfl(incl, 63);
-    if (pass == 0 && positive_only) {                      // (see k_sel_pick: linear.py:785-790 and the > 2^24 positives quirk)
-        const float cq = ceilf((float)total * qf);
-        const int64_t rk = (int64_t)cq - 1;
-        s.remaining = (total == 0 || rk >= total) ? -1 : (rk < 0 ? 0 : rk);
-    }
-    if (s.remaining >= 0) {
-        const unsigned long long hit = __ballot(incl > s.remaining);
-        int b = 255;
-        int64_t cum = total;
-        if (hit) {
-            const int fl = __ffsll(hit) - 1;
-            const int64_t excl = __shfl(incl - own, fl);
-            const unsigned cx = __shfl(c.x, fl), cy = __shfl(c.y, fl), cz = __shfl(c.z, fl);
-            cum = excl; b = 4 * fl;
-            if (cum + cx <= s.remaining) { cum += cx; ++b;
-                if (cum + cy <= s.remaining) { cum += cy; ++b;
-                    if (cum + cz <= s.remaining) { cum += cz; ++b; } } }
-        }
-        s.prefix = (s.prefix << 8) | (unsigned)b;
-        s.remaining -= cum;
-    }
-    return s;
+// one wavefront per (segment, rank): the state descends one byte and the histogram is cleared for the next pass (a single thread
+// walking 256 bins took 30 us)
+__global__ __launch_bounds__(256) void k_sel_pick(SelState* st, unsigned* hist, int S, int R, int pass,
+                                                  const float* __restrict__ qfrac, int positive_only) {
+    const int lane = threadIdx.x & 63;
+    const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= S * R) return;
+    uint4* h4 = reinterpret_cast<uint4*>(hist + (int64_t)i * 256);
+    const uint4 c = h4[lane];
+    h4[lane] = make_uint4(0u, 0u, 0u, 0u);
+    const SelState s = pick_wave(c, st[i], pass, positive_only, qfrac ? qfrac[i % R] : 0.0f, lane);
+    if (lane == 0) st[i] = s;
 }
 
 // ATen lerp (vectorised CPU form): weight < 0.5 ? fma(w, b-a, a) : fma(w-1, b-a, b)
