@@ -351,9 +351,7 @@ AttnCoreArgs attn_core_args(const void* qp, const void* kp, const void* vp, int6
 // below the grid limit, after raising its dynamic-LDS limit to lds_max once per device.  0, or the HIP error (recorded under `entry`).
 template <void (*KERNEL)(AttnCoreArgs)>
 int attn_core_launch(const char* entry, AttnCoreArgs a, int tile_rows, int threads, int lds_max, hipStream_t st) {
-    static unsigned long long attr_dev = 0;                                 // (one per KERNEL)
-    const hipError_t ea = adalog_max_lds(reinterpret_cast<const void*>(KERNEL), lds_max, &attr_dev);
-    if (ea != hipSuccess) { adalog_set_error("hipFuncSetAttribute", ea); return (int)ea; }
+    if (const int e = adalog_lds_limit<KERNEL>(lds_max)) return e;
     a.MT = cdiv(a.N, tile_rows);
     const size_t shm = (size_t)tile_rows * (a.Kp + 4) * 4 + 264 * sizeof(unsigned short);
     const int64_t total = a.G * a.MT, per_launch = (int64_t)1 << 30;

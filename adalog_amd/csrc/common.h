@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <type_traits>
 
 #define ADALOG_R 37            // AdaLog fixed denominator r (reference quantizers/logarithm.py:71)
 
@@ -38,6 +39,35 @@ static inline hipError_t adalog_max_lds(const void* fn, int bytes, unsigned long
     e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     if (e == hipSuccess) *done_mask |= bit;
     return e;
+}
+
+// ... for kernel instantiation K, to max_lds bytes.  K is a template argument, so the once-per-device state is one per instantiation.
+// 0, or the HIP error (recorded).
+template <auto K>
+static inline int adalog_lds_limit(int max_lds) {
+    static unsigned long long attr_dev = 0;
+    const hipError_t e = adalog_max_lds(reinterpret_cast<const void*>(K), max_lds, &attr_dev);
+    if (e != hipSuccess) { adalog_set_error("hipFuncSetAttribute", e); return (int)e; }
+    return 0;
+}
+
+// Launch of kernel instantiation K: raise its dynamic-LDS limit (max_lds = 0: the default limit is enough), note the label for
+// adalog_last_kernel (a string literal: the pointer is kept), launch.  0, or the HIP error of the limit call.
+template <auto K, class... Args>
+static inline int adalog_launch(const char* label, int max_lds, dim3 grid, int threads, size_t shm, hipStream_t st, const Args&... args) {
+    if (max_lds > 0)
+        if (const int e = adalog_lds_limit<K>(max_lds)) return e;
+    adalog_note_kernel(label);
+    hipLaunchKernelGGL(K, grid, dim3((unsigned)threads), shm, st, args...);
+    return 0;
+}
+
+// A run-time value from a fixed list as a compile-time constant: f(std::integral_constant<.., V>{}) for the V that equals v; the LAST
+// value of the list is taken when none does (the closing `else` of an if-ladder).  Nested calls enumerate a kernel's instantiations.
+template <auto V0, auto... Vs, class T, class F>
+static inline int adalog_dispatch(T v, F&& f) {
+    if constexpr (sizeof...(Vs) == 0) return f(std::integral_constant<decltype(V0), V0>{});
+    else return v == V0 ? f(std::integral_constant<decltype(V0), V0>{}) : adalog_dispatch<Vs...>(v, f);
 }
 
 // compute units of the CURRENT device (cached per device ordinal, not per process)

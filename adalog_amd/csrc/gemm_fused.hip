@@ -616,37 +616,23 @@ extern "C" int adalog_score_act_fused(const void* Wp, int M, int64_t Kp, const f
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(k_tie_thresholds, dim3((unsigned)a.levels2), dim3(128), 0, st, scale, qv, a.levels2, thr);
     ADALOG_LAUNCH_CHECK("adalog_score_act_fused (thresholds)");
-#define LAUNCH_FUSED(NRBV, FNSV)                                                                               \
-    do {                                                                                                       \
-        static unsigned long long attr_dev = 0; \
-        { hipError_t ea__ = adalog_max_lds(reinterpret_cast<const void*>(&k_act_fused<NRBV, FNSV>), (int)(160 * 1024), &attr_dev); \
-          if (ea__ != hipSuccess) { adalog_set_error("hipFuncSetAttribute", ea__); return (int)ea__; } } \
-        adalog_note_kernel("k_act_fused<bf16>");                                                             \
-        hipLaunchKernelGGL((k_act_fused<NRBV, FNSV>), dim3((unsigned)nwg), dim3(256), shm, st, a);             \
-    } while (0)
-#define LAUNCH_FUSED_N(NRBV) do { if (fns == 4) LAUNCH_FUSED(NRBV, 4); else LAUNCH_FUSED(NRBV, 3); } while (0)
     const bool use_asm = fused_use_asm();
     const size_t shm_asm = 256 + shm;
-#define LAUNCH_ASM(KERNEL, TAG)                                                                                 \
-    do {                                                                                                       \
-        static unsigned long long attr_dev = 0; \
-        { hipError_t ea__ = adalog_max_lds(reinterpret_cast<const void*>(&KERNEL), (int)(160 * 1024), &attr_dev); \
-          if (ea__ != hipSuccess) { adalog_set_error("hipFuncSetAttribute", ea__); return (int)ea__; } } \
-        adalog_note_kernel(TAG);                                                                               \
-        hipLaunchKernelGGL(KERNEL, dim3((unsigned)nwg), dim3(512), shm_asm, st, a);                            \
-    } while (0)
+    const int lim = 160 * 1024;
+    const unsigned grid = (unsigned)nwg;
+    int rc;
     if (use_asm && shm_asm <= 160 * 1024) {
-        if (nrb == 12 && fns == 4) LAUNCH_ASM(k_act_fused_asm_12_4, "k_act_fused_asm<12,4,bf16>");
-        else if (nrb == 12) LAUNCH_ASM(k_act_fused_asm_12_3, "k_act_fused_asm<12,3,bf16>");
-        else if (nrb == 8) LAUNCH_ASM(k_act_fused_asm_8_4, "k_act_fused_asm<8,4,bf16>");
-        else LAUNCH_ASM(k_act_fused_asm_4_4, "k_act_fused_asm<4,4,bf16>");
-    } else if (nrb == 12) LAUNCH_FUSED_N(12);
-    else if (nrb == 8) LAUNCH_FUSED_N(8);
-    else if (nrb == 6) LAUNCH_FUSED_N(6);
-    else LAUNCH_FUSED_N(4);
-#undef LAUNCH_ASM
-#undef LAUNCH_FUSED_N
-#undef LAUNCH_FUSED
+        if (nrb == 12 && fns == 4) rc = adalog_launch<k_act_fused_asm_12_4>("k_act_fused_asm<12,4,bf16>", lim, grid, 512, shm_asm, st, a);
+        else if (nrb == 12) rc = adalog_launch<k_act_fused_asm_12_3>("k_act_fused_asm<12,3,bf16>", lim, grid, 512, shm_asm, st, a);
+        else if (nrb == 8) rc = adalog_launch<k_act_fused_asm_8_4>("k_act_fused_asm<8,4,bf16>", lim, grid, 512, shm_asm, st, a);
+        else rc = adalog_launch<k_act_fused_asm_4_4>("k_act_fused_asm<4,4,bf16>", lim, grid, 512, shm_asm, st, a);
+    } else
+        rc = adalog_dispatch<12, 8, 6, 4>(nrb, [&](auto nr) {
+            return adalog_dispatch<4, 3>(fns, [&](auto fn) {
+                return adalog_launch<k_act_fused<decltype(nr)::value, decltype(fn)::value>>("k_act_fused<bf16>", lim, grid, 256, shm, st, a);
+            });
+        });
+    if (rc) return rc;
     ADALOG_LAUNCH_CHECK("adalog_score_act_fused");
     hipLaunchKernelGGL(k_fused_finish, dim3(128), dim3(64), 0, st, (const double*)workspace, nwg, norm, scores);
     ADALOG_LAUNCH_CHECK("adalog_score_act_fused (finish)");

@@ -28,7 +28,6 @@
 // tiles sharing an operand run on one XCD (its L2).
 #include "common.h"
 #include "fpcs_tail.h"
-#include <type_traits>
 #include <stdlib.h>
 
 // The quantisation kernels are compiled without FMA contraction (bin indices must round like the reference); this file
@@ -172,86 +171,138 @@ static Layout layout_of(int M, int N, int C, int G, int gmod, int ref_div, int r
 // The reference comes in columns of 64, 128 or 256 candidates
 static bool ref_div_ok(int N, int ref_div) { return (ref_div == 64 || ref_div == 128 || ref_div == 256) && N % ref_div == 0; }
 
-// what the loader-wave group kernels ask of a launch whatever their operands: 5..7 row blocks, many groups, per-head sums that fit
-// LDS, plain column factors, a reference group within 32-bit addressing
-static bool grp_shape_ok(int M, int N, int G, int gmod, int ref_div, const float* bias, const float* row_scale, int64_t sb_n, int64_t ref_cs) {
+// GEN form of the attention searches (adalog_gemm_score_gen): the candidate operand B is not read but generated in the kernel
+// from the fp32 tensor x [G][N / ref_div][K] with the candidates' (sb, zp) pairs
+struct MmGen { const float* x; int64_t ldx, sg; const float* zp; int n_bits; };
+// extras of the STORE epilogue (GemmArgs: addend, out_gi, sOo)
+struct MmOutEx { const float* addend; int out_gi; int64_t sOo; };
+
+// One launch as its entry point describes it (strides in elements, 0 = shared; the argument lists of adalog_gemm_score and its
+// relatives say what each field means).  Entry points fill it field by field: what they leave out is zero / null.
+struct MmCall {
+    int dtype; const void *A, *B; int64_t sAc, sAg, sBc, sBg;                 // operands
+    int M, N; int64_t Kp, k_valid; int C, G, gmod;                            // sizes
+    const float* ref; int64_t ldr, sRg, ref_cs; int ref_div;                  // reference
+    const float* sa; int64_t sa_c, sa_g; float sa_mul;                        // epilogue: out = D * (sa * sa_mul * sb) + bias
+    const float* sb; int64_t sb_c, sb_g, sb_n;
+    const float* bias; int64_t bi_c, bi_g, bi_n;
+    const float *row_scale, *row_bias;
+    float* partial; int64_t partial_elems;                                    // outputs: score partials, or the stored product
+    float* out; int64_t ldo, sOc, sOg;
+    int order, reduce_cols; void* stream;                                     // options
+    const MmGen* gen; const MmOutEx* ox;
+};
+
+// the launch the adalog_gemm_*_ok queries ask about: C = 1, transposed reference [G][N / ref_div][M], plain column factors, no bias
+static MmCall shape_call(int dtype, int M, int N, int G, int gmod, int ref_div, int64_t k_valid, int64_t Kp, int reduce_cols) {
+    MmCall c{};
+    c.dtype = dtype; c.M = M; c.N = N; c.Kp = Kp; c.k_valid = k_valid; c.C = 1; c.G = G; c.gmod = gmod;
+    c.ldr = 1; c.ref_cs = M; c.ref_div = ref_div; c.reduce_cols = reduce_cols;
+    return c;
+}
+
+// bytes per element of A / of B (dtype 4: bf16 rows x fp8 columns, laid out like the bf16 launch)
+static int esz_a(int dtype) { return (dtype == 0 || dtype == 3) ? 1 : (dtype == 1 || dtype == 4) ? 2 : 4; }
+static int esz_b(int dtype) { return dtype == 4 ? 1 : esz_a(dtype); }
+
+static Layout call_layout(const MmCall& c, bool ref_transposed) {
+    const int es = esz_a(c.dtype);
+    return layout_of(c.M, c.N, c.C, c.G, c.gmod, c.ref_div, c.reduce_cols, c.out == nullptr, (c.k_valid > 0 ? c.k_valid : c.Kp) * es, c.Kp * es,
+                     ref_transposed, c.dtype == 4 ? 1 : c.dtype);
+}
+
+// ---- what each kernel family asks of a launch: the single place where a kernel's limits are written (kvb: valid K in bytes)
+// the loader-wave group kernels, whatever their operands: 5..7 row blocks, many groups, per-head sums that fit LDS, plain column
+// factors, a reference group within 32-bit addressing
+static bool grp_shape_ok(const MmCall& c) {
     static const int use_grp = getenv("ADALOG_GEMM_GRP") ? atoi(getenv("ADALOG_GEMM_GRP")) : 1;
-    return use_grp && M > 128 && M <= 224 && G >= 8 && gmod <= 16 && !bias && !row_scale && sb_n == 0 && ref_div_ok(N, ref_div) &&
-           (int64_t)(N / ref_div) * ref_cs * 4 < ((int64_t)1 << 31);
+    return use_grp && c.M > 128 && c.M <= 224 && c.G >= 8 && c.gmod <= 16 && !c.bias && !c.row_scale && c.sb_n == 0 && ref_div_ok(c.N, c.ref_div) &&
+           (int64_t)(c.N / c.ref_div) * c.ref_cs * 4 < ((int64_t)1 << 31);
 }
 // ... and the window kernels: at most 64 rows, hundreds of groups or more, at least as many waves as heads per image (every
 // participating wave owns one head), a reference slice that fits a wave's LDS
-static bool win_shape_ok(int M, int N, int G, int gmod, int ref_div, const float* bias, const float* row_scale, int64_t sb_n, int64_t ref_cs,
-                         int wgs) {
+static bool win_shape_ok(const MmCall& c, int wgs) {
     static const int use_win = getenv("ADALOG_GEMM_WIN") ? atoi(getenv("ADALOG_GEMM_WIN")) : 1;
-    return use_win && M >= 4 && M <= 64 && G >= 256 && gmod <= 32 && !bias && !row_scale && sb_n == 0 && ref_div_ok(N, ref_div) &&
-           N / ref_div <= 64 && wgs * 4 >= gmod && ref_cs >= M;
+    return use_win && c.M >= 4 && c.M <= 64 && c.G >= 256 && c.gmod <= 32 && !c.bias && !c.row_scale && c.sb_n == 0 && ref_div_ok(c.N, c.ref_div) &&
+           c.N / c.ref_div <= 64 && wgs * 4 >= c.gmod && c.ref_cs >= c.M;
 }
-
-// Launch-time choice of the group kernel (it shares the streaming kernel's accumulator layout, so the layout query does
-// not need to know): int8 or fp8, one K-step, 5..7 row blocks, many groups (up to 16 heads per image: the per-head fp64
-// sums live in LDS), plain column factors.
-static bool grp_ok(int dtype, int M, int N, int G, int gmod, int ref_div, int64_t kvalid_bytes, const float* bias,
-                   const float* row_scale, int64_t sb_n, int64_t ref_cs) {
-    return (dtype == 0 || dtype == 3) && kvalid_bytes <= BK3 && grp_shape_ok(M, N, G, gmod, ref_div, bias, row_scale, sb_n, ref_cs);
+static bool byte_operands(const MmCall& c) { return c.dtype == 0 || c.dtype == 3; }
+// the group kernel (it shares the streaming kernel's accumulator layout, so the layout query does not need to know): int8 or fp8,
+// one K-step
+static bool grp_ok(const MmCall& c, int64_t kvb) { return byte_operands(c) && kvb <= BK3 && grp_shape_ok(c); }
+// ... its wave-private form: a switch, and every participating wave owns one head
+static bool grpw_ok(const MmCall& c, int wgs) {
+    static const int use_grpw = getenv("ADALOG_GEMM_GRPW") ? atoi(getenv("ADALOG_GEMM_GRPW")) : 1;
+    return use_grpw != 0 && wgs * 4 >= c.gmod && c.ref_cs >= c.M;
 }
+// ... its several-K-steps form: bf16, exactly 7 K-steps (K = 193..224 elements: the 197 tokens of a 224 x 224 ViT)
+static bool grpk_ok(const MmCall& c, int64_t kvb) { return c.dtype == 1 && kvb > 6 * BK3 && kvb <= 7 * BK3 && grp_shape_ok(c); }
+// ... its mixed form (dtype 4: bf16 rows x fp8 columns): exactly 4 K-steps of 64 elements (K = 193..256)
+static bool grpk8_ok(const MmCall& c) { return c.k_valid > 192 && c.k_valid <= 256 && grp_shape_ok(c); }
+// ... the trimmed-K form of the mixed kernel (k_gemm_grpk8t): rows of 208 elements, K = 193..208
+static bool grpk8t_ok(const MmCall& c) { return c.k_valid <= 208 && grpk8_ok(c); }
+// the window kernel: int8 or fp8, one K-step
+static bool win_ok(const MmCall& c, int64_t kvb, int wgs) { return byte_operands(c) && kvb <= BK3 && win_shape_ok(c, wgs); }
+// ... mixed operands: K <= 64 elements (one 64-byte fp8 K-step against 128-byte bf16 rows)
+static bool winb_ok(const MmCall& c, int wgs) { return c.k_valid >= 1 && c.k_valid <= 64 && win_shape_ok(c, wgs); }
 
-static bool grpw_on() {
-    static const int v = getenv("ADALOG_GEMM_GRPW") ? atoi(getenv("ADALOG_GEMM_GRPW")) : 1;     // wave-private form of the q.k^T kernel
-    return v != 0;
-}
+// The kernel family a launch runs on.  R_NONE: mixed operands (dtype 4) of a shape none of their three families takes.
+enum Route { R_NONE, R_SLAB, R_WIN, R_GRPW, R_GRP, R_GRPK, R_STREAM, R_GLDS, R_CAND, R_SCORE, R_MX_STREAM, R_MX_WIN, R_MX_GRPK8, R_MX_GRPK8T };
 
-// ... and of its several-K-steps form: bf16, exactly 7 K-steps (K = 193..224 elements: the 197 tokens of a 224 x 224 ViT).
-static bool grpk_ok(int dtype, int M, int N, int G, int gmod, int ref_div, int64_t kvalid_bytes, const float* bias,
-                    const float* row_scale, int64_t sb_n, int64_t ref_cs) {
-    return dtype == 1 && kvalid_bytes > 6 * BK3 && kvalid_bytes <= 7 * BK3 && grp_shape_ok(M, N, G, gmod, ref_div, bias, row_scale, sb_n, ref_cs);
-}
-
-// ... and of its mixed form (dtype 4: bf16 rows x fp8 columns): exactly 4 K-steps of 64 elements (K = 193..256).
-static bool grpk8_ok(int M, int N, int G, int gmod, int ref_div, int64_t k_valid, const float* bias, const float* row_scale,
-                     int64_t sb_n, int64_t ref_cs) {
-    return k_valid > 192 && k_valid <= 256 && grp_shape_ok(M, N, G, gmod, ref_div, bias, row_scale, sb_n, ref_cs);
-}
-
-// ... and of the trimmed-K form of the mixed kernel (k_gemm_grpk8t): rows of 208 elements, K = 193..208
-static bool grpk8t_ok(int M, int N, int G, int gmod, int ref_div, int64_t k_valid, const float* bias, const float* row_scale,
-                      int64_t sb_n, int64_t ref_cs) {
-    return k_valid <= 208 && grpk8_ok(M, N, G, gmod, ref_div, k_valid, bias, row_scale, sb_n, ref_cs);
-}
-
-// ... mixed operands, window family: K <= 64 elements (one 64-byte fp8 K-step against 128-byte bf16 rows), at most 64 rows.
-static bool winb_ok(int M, int N, int G, int gmod, int ref_div, int64_t k_valid, const float* bias, const float* row_scale, int64_t sb_n,
-                    int64_t ref_cs, int wgs) {
-    return k_valid >= 1 && k_valid <= 64 && win_shape_ok(M, N, G, gmod, ref_div, bias, row_scale, sb_n, ref_cs, wgs);
-}
-
-// ... and of the window kernel: int8 or fp8, one K-step, at most 64 rows, hundreds of groups or more, at least as many waves as
-// heads per image (every participating wave owns one head).
-static bool win_ok(int dtype, int M, int N, int G, int gmod, int ref_div, int64_t kvalid_bytes, const float* bias,
-                   const float* row_scale, int64_t sb_n, int64_t ref_cs, int wgs) {
-    return (dtype == 0 || dtype == 3) && kvalid_bytes <= BK3 && win_shape_ok(M, N, G, gmod, ref_div, bias, row_scale, sb_n, ref_cs, wgs);
-}
-
-// Launch of one instantiation K of the attention group / window kernels: raise its dynamic-LDS limit once per device (max_lds = 0:
-// the default limit is enough), note the label for adalog_last_kernel, launch.  K is a template argument, so the once-per-device
-// state is one per instantiation.
-template <auto K>
-static int launch_attn(const char* label, int max_lds, int wgs, int threads, size_t shm, hipStream_t st, const GemmArgs& p) {
-    if (max_lds > 0) {
-        static unsigned long long attr_dev = 0;
-        const hipError_t e = adalog_max_lds(reinterpret_cast<const void*>(K), max_lds, &attr_dev);
-        if (e != hipSuccess) { adalog_set_error("hipFuncSetAttribute", e); return (int)e; }
+// THE route decision: the launch code, its argument checks and the adalog_gemm_*_ok queries (on which ops.py routes) all ask this
+// function.  From the call (shape, operand type, epilogue options) and its Layout; first match wins:
+//   slab -> window -> wave-private group -> barrier group -> 7-step group -> stream -> LDS-DMA cand -> cand -> C > 1 fallback,
+// mixed operands: wide stream (K > 256) | window (K <= 64) | 4-step group, trimmed where the rows are 208 elements.
+static Route route_of(const MmCall& c, const Layout& L) {
+    const bool acc_search = L.stream && !c.out && L.acc;
+    if (c.dtype == 4) {
+        static const int use_mx = getenv("ADALOG_GEMM_STREAM_MX") ? atoi(getenv("ADALOG_GEMM_STREAM_MX")) : 1;
+        if (c.k_valid > 256) return (use_mx && L.stream && L.wide && !L.slab) ? R_MX_STREAM : R_NONE;
+        if (!acc_search) return R_NONE;
+        if (c.k_valid <= 64) return winb_ok(c, L.wgs) ? R_MX_WIN : R_NONE;
+        if (!grpk8_ok(c)) return R_NONE;
+        return (c.Kp == 208 && grpk8t_ok(c)) ? R_MX_GRPK8T : R_MX_GRPK8;
     }
-    adalog_note_kernel(label);
-    hipLaunchKernelGGL(K, dim3((unsigned)wgs), dim3((unsigned)threads), shm, st, p);
-    return 0;
+    const int64_t kvb = (c.k_valid > 0 ? c.k_valid : c.Kp) * esz_a(c.dtype);
+    if (L.slab && !c.out) return R_SLAB;
+    if (acc_search && win_ok(c, kvb, L.wgs)) return R_WIN;
+    if (acc_search && grp_ok(c, kvb)) return grpw_ok(c, L.wgs) ? R_GRPW : R_GRP;
+    if (acc_search && grpk_ok(c, kvb)) return R_GRPK;
+    if (L.stream && !c.out) return R_STREAM;
+    static const int use_glds = getenv("ADALOG_GEMM_GLDS") ? atoi(getenv("ADALOG_GEMM_GLDS")) : 1;   // LDS-DMA pipeline (default on)
+    if (L.big && use_glds && !c.out && L.tm <= 2) return R_GLDS;
+    return L.big ? R_CAND : R_SCORE;
 }
+
 // candidates per reference column -> 32-column blocks per reference column, as a compile-time constant: f(integral_constant<int, NJ>)
 template <class F>
 static int with_nj(int ref_div, F&& f) {
-    if (ref_div == 64) return f(std::integral_constant<int, 2>{});
-    if (ref_div == 128) return f(std::integral_constant<int, 4>{});
-    return f(std::integral_constant<int, 8>{});
+    return adalog_dispatch<64, 128, 256>(ref_div, [&](auto rd) { return f(std::integral_constant<int, decltype(rd)::value / 32>{}); });
+}
+// the slab kernels' instantiations: f(NREF, DT, NB) for fp8 / int8 storage, 256- / 128-column slabs of 1, 2, 4 / 1, 2 reference columns
+template <class F>
+static int with_slab(int dtype, int slab_nb, int ref_div, F&& f) {
+    const int nref = 32 * slab_nb / ref_div;
+    return adalog_dispatch<3, 0>(dtype, [&](auto dt) {
+        return adalog_dispatch<8, 4>(slab_nb, [&](auto nb) {
+            auto go = [&](auto nr) { return f(nr, dt, nb); };
+            if constexpr (decltype(nb)::value == 8) return adalog_dispatch<1, 2, 4>(nref, go);
+            else return adalog_dispatch<1, 2>(nref, go);
+        });
+    });
+}
+// their labels: form 0 = packed candidates, 1 = generated activation candidates, 2 = generated weight candidates
+static const char* slab_label(int form, int dt, int nb) {
+    static const char* const names[3][2][2] = {
+        {{"k_gemm_slab<i8>", "k_gemm_slab128<i8>"}, {"k_gemm_slab<fp8>", "k_gemm_slab128<fp8>"}},
+        {{"k_gemm_slab_gen<i8>", "k_gemm_slab128_gen<i8>"}, {"k_gemm_slab_gen<fp8>", "k_gemm_slab128_gen<fp8>"}},
+        {{"k_gemm_slab_wgen<i8>", "k_gemm_slab128_wgen<i8>"}, {"k_gemm_slab_wgen<fp8>", "k_gemm_slab128_wgen<fp8>"}}};
+    return names[form][dt == 3][nb != 8];
+}
+// dynamic LDS of a slab launch: the resident slab, the streamed operand's ring, reference and sums
+static size_t slab_lds(int64_t kvb, int slab_nb) {
+    const int nk = (int)((kvb + BK3 - 1) / BK3), SBN = 32 * slab_nb;
+    return (size_t)nk * SBN * BK3 + 8 * 3 * 32 * BK3 + 8 * 192 * 4 + 8 * SBN * 4;
 }
 // items of the loader-wave group kernels: a group's NB 32-column blocks in chunks of CB (a multiple of 8: chunks start on a reference
 // column), about three items per workgroup
@@ -261,15 +312,61 @@ static void grp_chunks(GemmArgs& p, int N, int wgs, int G) {
     const int CB = cdiv(cdiv(NB, nch0 < 1 ? 1 : nch0), 8) * 8;
     p.slab_R = CB; p.slab_U = cdiv(NB, CB);
 }
+// items of the wave-private kernels (a wave per item): a group's n reference columns in chunks, about three items per wave, at least
+// min_chunks of them
+static void wave_chunks(GemmArgs& p, int n, int wgs, int G, int min_chunks = 1) {
+    int nch = (int)cdiv(3 * ((int64_t)wgs * 4), G);
+    if (nch < min_chunks) nch = min_chunks;
+    nch = nch < 1 ? 1 : nch > n ? n : nch;
+    const int cbc = cdiv(n, nch);
+    p.slab_R = cbc; p.slab_U = cdiv(n, cbc);
+}
+// m-tiles per group of the streaming kernel: the group's A rows are re-read once per n-tile (from L2 / the 256 MiB Infinity Cache), the
+// B tiles stream from HBM once per GROUP -- with the candidate operand at 150..600 MB per launch that stream is what must not repeat:
+// groups of <= 8 MiB of A rows (2 MiB, half of an XCD's L2, re-read vit_base's fc2 candidates 25 times: 4.16 -> 4.05 s per
+// calibration, 3.99 at 64 MiB; deit_small -- its operand fits the Infinity Cache -- is indifferent up to 16 MiB and 2 % slower at 64)
+static int stream_gm(const Layout& L, int64_t a_row_bytes) {
+    static const int64_t grp_bytes = getenv("ADALOG_GEMM_GM_BYTES") ? atoll(getenv("ADALOG_GEMM_GM_BYTES")) : ((int64_t)8 << 20);
+    int64_t gm = grp_bytes / ((int64_t)64 * L.tm * a_row_bytes);
+    if (const char* e = getenv("ADALOG_GEMM_GM")) gm = atoi(e);
+    return (int)(gm < 1 ? 1 : gm > L.MT ? L.MT : gm);
+}
+
+// The kernels' arguments from a call and its Layout, operands and strides in bytes.  Every route starts from this one fill and states
+// its deviations after it.
+static GemmArgs gemm_args(const MmCall& c, const Layout& L) {
+    const int ea = esz_a(c.dtype), eb = esz_b(c.dtype);
+    GemmArgs p{};
+    p.A = (const uint8_t*)c.A; p.B = (const uint8_t*)c.B;
+    p.sAc = c.sAc * ea; p.sAg = c.sAg * ea; p.sBc = c.sBc * eb; p.sBg = c.sBg * eb;
+    p.M = c.M; p.N = c.N; p.Kb = c.Kp * eb; p.Kvb = (c.k_valid > 0 ? c.k_valid : c.Kp) * eb; p.C = c.C; p.G = c.G; p.gmod = c.gmod;
+    p.ref = c.ref; p.ldr = c.ldr; p.sRg = c.sRg; p.ref_cs = c.ref_cs; p.ref_div = c.ref_div;
+    p.sa = c.sa; p.sa_c = c.sa_c; p.sa_g = c.sa_g; p.sa_mul = c.sa_mul;
+    p.sb = c.sb; p.sb_c = c.sb_c; p.sb_g = c.sb_g; p.sb_n = c.sb_n;
+    p.bias = c.bias; p.bi_c = c.bi_c; p.bi_g = c.bi_g; p.bi_n = c.bi_n;
+    p.row_scale = c.row_scale; p.row_bias = c.row_bias;
+    p.MT = L.MT; p.NT = L.NT; p.Npad = L.Npad;
+    p.order = c.order; p.reduce_cols = c.reduce_cols && c.ref_div == 1; p.timeline = g_timeline;
+    p.partial = c.partial; p.out = c.out; p.ldo = c.ldo; p.sOc = c.sOc; p.sOg = c.sOg;
+    if (c.ox) { p.addend = c.ox->addend; p.out_gi = c.ox->out_gi; p.sOo = c.ox->sOo; }
+    if (L.acc) p.wg_acc = (double*)c.partial;
+    return p;
+}
+// ... of the mixed families (dtype 4): the bf16 rows have their own length in bytes; scoring only, never timed in the lab
+static GemmArgs gemm_args_mixed(const MmCall& c, const Layout& L) {
+    GemmArgs p = gemm_args(c, L);
+    p.KbA = c.Kp * 2; p.reduce_cols = 0; p.timeline = nullptr;
+    p.row_scale = nullptr; p.ldo = 0; p.sOc = 0; p.sOg = 0;
+    return p;
+}
 
 // M, N: GEMM rows / columns (N includes the candidate factor when ref_div > 1).  Outputs the partial-buffer layout
 // [c_eff][G][MT][Npad] the kernel will write, for allocation and for adalog_finish_scores.
 extern "C" int64_t adalog_gemm_score_layout(int M, int N, int C, int G, int gmod, int ref_div, int reduce_cols, int dtype,
                                             int64_t Kp, int64_t k_valid, int ref_transposed, int* MT, int* Npad, int* mode) {
-    if (dtype == 4) dtype = 1;                          // mixed operands (bf16 rows x fp8 columns): laid out like the bf16 launch
-    const int esz = (dtype == 0 || dtype == 3) ? 1 : dtype == 1 ? 2 : 4;
-    const Layout L = layout_of(M, N, C, G, gmod, ref_div, reduce_cols, true, (k_valid > 0 ? k_valid : Kp) * esz, Kp * esz,
-                               ref_transposed != 0, dtype);
+    MmCall c = shape_call(dtype, M, N, G, gmod, ref_div, k_valid, Kp, reduce_cols);
+    c.C = C;
+    const Layout L = call_layout(c, ref_transposed != 0);
     if (MT) *MT = L.acc ? L.wgs : L.MT;
     if (Npad) *Npad = L.acc ? BN2 : L.Npad;
     if (mode) *mode = L.acc ? 2 : (ref_div > 1 ? 1 : 0);
@@ -279,55 +376,41 @@ extern "C" int64_t adalog_gemm_score_layout(int M, int N, int C, int G, int gmod
 // 1 when a scoring launch of this shape runs on the window kernel, i.e. when int8 / fp8 operands of K <= 32 may be packed
 // with 32-byte rows (half the operand bytes of the 64-byte K-step padding).  C = 1, reduce_cols = 1, transposed reference.
 extern "C" int adalog_gemm_win_ok(int dtype, int M, int N, int G, int gmod, int ref_div, int64_t k_valid) {
-    const int esz = 1;
     if (!(dtype == 0 || dtype == 3) || k_valid > 32 || ref_div < 1 || N % ref_div != 0) return 0;
-    const Layout L = layout_of(M, N, 1, G, gmod, ref_div, 1, true, k_valid * esz, 32 * esz, true, dtype);
-    return (L.stream && L.acc && win_ok(dtype, M, N, G, gmod, ref_div, k_valid * esz, nullptr, nullptr, 0, M, L.wgs)) ? 1 : 0;
+    const MmCall c = shape_call(dtype, M, N, G, gmod, ref_div, k_valid, 32, 1);
+    return route_of(c, call_layout(c, true)) == R_WIN ? 1 : 0;
+}
+
+// the mixed launch of a shape with rows of Kp elements, and its route (R_NONE: not taken)
+static Route mixed_route(int M, int N, int G, int gmod, int ref_div, int64_t k_valid, int64_t Kp) {
+    if (ref_div < 1 || N % ref_div != 0 || k_valid < 1) return R_NONE;
+    const MmCall c = shape_call(4, M, N, G, gmod, ref_div, k_valid, Kp, k_valid > 256 ? 0 : 1);
+    return route_of(c, call_layout(c, true));
 }
 
 // 1 when adalog_gemm_score takes dtype 4 (A: bf16 rows, B: fp8 e4m3 candidate columns, both [..][Kp] with Kp = 256 elements) for
-// this shape: the softmax.v weight search of a 197-token ViT (M = 197 attention rows, K = 197 keys) with <= 4-bit candidates.
+// this shape: the softmax.v weight search of a 197-token ViT (M = 197 attention rows, K = 197 keys) with <= 4-bit candidates; the
+// windows of a Swin (K <= 64, Kp = 64); and a third family, the wide streaming kernel (one group or many), rows of any multiple of
+// 64 elements: taken when the all-bf16 launch of this shape would run on the wide form (K >= 256 elements, M >= 192).
 // C = 1, reduce_cols = 1, transposed reference.
 extern "C" int adalog_gemm_mixed_ok(int M, int N, int G, int gmod, int ref_div, int64_t k_valid) {
-    if (ref_div < 1 || N % ref_div != 0 || k_valid < 1) return 0;
-    if (k_valid > 256) {
-        // third family: the wide streaming kernel (one group or many), rows of any multiple of 64 elements: taken when the all-bf16
-        // launch of this shape would run on the wide form (K >= 256 elements, M >= 192)
-        static const int use_mx = getenv("ADALOG_GEMM_STREAM_MX") ? atoi(getenv("ADALOG_GEMM_STREAM_MX")) : 1;
-        const int64_t Kp = (k_valid + 63) / 64 * 64;
-        const Layout L = layout_of(M, N, 1, G, gmod, ref_div, 0, true, k_valid * 2, Kp * 2, true, 1);
-        return (use_mx && L.stream && L.wide && !L.slab) ? 1 : 0;
-    }
-    const int64_t Kp = k_valid <= 64 ? 64 : 256;                        // windows / 197-token groups
-    const Layout L = layout_of(M, N, 1, G, gmod, ref_div, 1, true, k_valid * 2, Kp * 2, true, 1);
-    if (!(L.stream && L.acc)) return 0;
-    if (k_valid <= 64) return winb_ok(M, N, G, gmod, ref_div, k_valid, nullptr, nullptr, 0, M, L.wgs) ? 1 : 0;
-    return grpk8_ok(M, N, G, gmod, ref_div, k_valid, nullptr, nullptr, 0, M) ? 1 : 0;
+    const int64_t Kp = k_valid > 256 ? (k_valid + 63) / 64 * 64 : k_valid <= 64 ? 64 : 256;
+    return mixed_route(M, N, G, gmod, ref_div, k_valid, Kp) != R_NONE ? 1 : 0;
 }
 
 // Row length (elements) of the trimmed-K form of the mixed 197-token family, or 0 when the shape is not taken by it (then Kp = 256 as
 // adalog_gemm_mixed_ok describes): both operands may be packed with rows of 208 elements (13 sixteen-element slots) for K = 193..208.
 extern "C" int adalog_gemm_mixed_ktrim(int M, int N, int G, int gmod, int ref_div, int64_t k_valid) {
-    if (k_valid <= 64 || k_valid > 208 || !adalog_gemm_mixed_ok(M, N, G, gmod, ref_div, k_valid)) return 0;
-    return grpk8t_ok(M, N, G, gmod, ref_div, k_valid, nullptr, nullptr, 0, M) ? 208 : 0;
+    return mixed_route(M, N, G, gmod, ref_div, k_valid, 208) == R_MX_GRPK8T ? 208 : 0;
 }
 
-// GEN form of the attention searches (adalog_gemm_score_gen): the candidate operand B is not read but generated in the kernel
-// from the fp32 tensor x [G][N / ref_div][K] with the candidates' (sb, zp) pairs
-struct MmGen { const float* x; int64_t ldx, sg; const float* zp; int n_bits; };
-// extras of the STORE epilogue (GemmArgs: addend, out_gi, sOo)
-struct MmOutEx { const float* addend; int out_gi; int64_t sOo; };
-
-static int gemm_score_impl(int dtype, const void* A, const void* B, int64_t sAc, int64_t sAg, int64_t sBc,
-                           int64_t sBg, int M, int N, int64_t Kp, int64_t k_valid, int C, int G, int gmod, const float* ref,
-                           int64_t ldr, int64_t sRg, int64_t ref_cs, int ref_div, const float* sa, int64_t sa_c,
-                           int64_t sa_g, float sa_mul, const float* sb, int64_t sb_c, int64_t sb_g, int64_t sb_n,
-                           const float* bias, int64_t bi_c, int64_t bi_g, int64_t bi_n, const float* row_scale,
-                           const float* row_bias, float* partial, int64_t partial_elems, float* out, int64_t ldo,
-                           int64_t sOc, int64_t sOg, int order, int reduce_cols, void* stream, const MmGen* gen,
-                           const MmOutEx* ox = nullptr) {
-    ADALOG_ARG_CHECK(A && (B || gen) && sa && sb, "gemm_score: null operand/scale pointer");
-    ADALOG_ARG_CHECK(!ox || (out && C == 1 && !row_scale && (ox->out_gi == 0 || (ox->out_gi > 0 && G % ox->out_gi == 0))),
+static int gemm_score_impl(const MmCall& c) {
+    const int dtype = c.dtype, M = c.M, N = c.N, C = c.C, G = c.G, gmod = c.gmod, ref_div = c.ref_div;
+    const int64_t Kp = c.Kp, k_valid = c.k_valid;
+    const MmGen* gen = c.gen;
+    hipStream_t st = (hipStream_t)c.stream;
+    ADALOG_ARG_CHECK(c.A && (c.B || gen) && c.sa && c.sb, "gemm_score: null operand/scale pointer");
+    ADALOG_ARG_CHECK(!c.ox || (c.out && C == 1 && !c.row_scale && (c.ox->out_gi == 0 || (c.ox->out_gi > 0 && G % c.ox->out_gi == 0))),
                      "gemm_out_ex: the epilogue extras need out, C == 1 and an inner group count that divides G");
     ADALOG_ARG_CHECK(!gen || ((dtype == 0 || dtype == 3) && gen->x && gen->zp && k_valid > 0 && k_valid % 16 == 0 && k_valid <= 64 &&
                               gen->ldx % 4 == 0 && gen->sg % 4 == 0 && (((uintptr_t)gen->x) & 15) == 0),
@@ -336,76 +419,45 @@ static int gemm_score_impl(int dtype, const void* A, const void* B, int64_t sAc,
     ADALOG_ARG_CHECK(M >= 1 && N >= 1 && C >= 1 && G >= 1 && gmod >= 1 && G % gmod == 0 && ref_div >= 1, "gemm_score: bad sizes");
     if (dtype == 4 && k_valid > 256) {
         // mixed operands, streaming family: the wide persistent kernel with two 64-byte planes of bf16 rows per fp8 K-step
-        ADALOG_ARG_CHECK(Kp % 64 == 0 && k_valid <= Kp && C == 1 && partial && ref && !out && ldr == 1 && !row_scale &&
+        ADALOG_ARG_CHECK(Kp % 64 == 0 && k_valid <= Kp && C == 1 && c.partial && c.ref && !c.out && c.ldr == 1 && !c.row_scale &&
                          adalog_gemm_mixed_ok(M, N, G, gmod, ref_div, k_valid),
                          "gemm_score: bf16 x fp8 operands, streaming family: Kp a multiple of 64, C = 1, transposed reference, a shape adalog_gemm_mixed_ok accepts");
-        ADALOG_ARG_CHECK(order >= 0 && order <= 2, "gemm_score: order must be 0, 1 or 2");
-        const Layout L = layout_of(M, N, C, G, gmod, ref_div, reduce_cols, true, k_valid * 2, Kp * 2, true, 1);
-        ADALOG_ARG_CHECK(L.stream && L.wide && !L.slab, "gemm_score: bf16 x fp8 operands: not a wide streaming shape");
-        GemmArgs p{};
-        p.A = (const uint8_t*)A; p.B = (const uint8_t*)B;
-        p.sAc = sAc * 2; p.sAg = sAg * 2; p.sBc = sBc; p.sBg = sBg;
-        p.M = M; p.N = N; p.Kb = Kp; p.KbA = Kp * 2; p.Kvb = k_valid; p.C = C; p.G = G; p.gmod = gmod;
-        p.ref = ref; p.ldr = ldr; p.sRg = sRg; p.ref_cs = ref_cs; p.ref_div = ref_div;
-        ADALOG_ARG_CHECK(((int64_t)(M - 1) * ldr + (int64_t)(L.n_eff - 1) * (ref_cs > 0 ? ref_cs : 1) < ((int64_t)1 << 31)),
+        ADALOG_ARG_CHECK(c.order >= 0 && c.order <= 2, "gemm_score: order must be 0, 1 or 2");
+        const Layout L = call_layout(c, true);
+        ADALOG_ARG_CHECK(route_of(c, L) == R_MX_STREAM, "gemm_score: bf16 x fp8 operands: not a wide streaming shape");
+        ADALOG_ARG_CHECK(((int64_t)(M - 1) * c.ldr + (int64_t)(L.n_eff - 1) * (c.ref_cs > 0 ? c.ref_cs : 1) < ((int64_t)1 << 31)),
                          "gemm_score: reference group exceeds 32-bit addressing");
-        p.sa = sa; p.sa_c = sa_c; p.sa_g = sa_g; p.sa_mul = sa_mul;
-        p.sb = sb; p.sb_c = sb_c; p.sb_g = sb_g; p.sb_n = sb_n;
-        p.bias = bias; p.bi_c = bi_c; p.bi_g = bi_g; p.bi_n = bi_n;
-        p.row_bias = row_bias;
-        p.MT = L.MT; p.NT = L.NT; p.Npad = L.Npad;
-        p.order = order; p.reduce_cols = 0; p.partial = partial;
-        ADALOG_ARG_CHECK(partial_elems >= L.elems, "gemm_score: partial buffer too small");
-        if (L.acc) { ADALOG_ARG_CHECK(((uintptr_t)partial & 7) == 0, "gemm_score: accumulator buffer must be 8-byte aligned"); p.wg_acc = (double*)partial; }
-        {
-            static const int64_t grp_bytes = getenv("ADALOG_GEMM_GM_BYTES") ? atoll(getenv("ADALOG_GEMM_GM_BYTES")) : ((int64_t)8 << 20);
-            int64_t gm = grp_bytes / ((int64_t)64 * L.tm * p.KbA);
-            if (const char* e = getenv("ADALOG_GEMM_GM")) gm = atoi(e);
-            p.gm = (int)(gm < 1 ? 1 : gm > L.MT ? L.MT : gm);
-        }
-        hipStream_t st = (hipStream_t)stream;
+        ADALOG_ARG_CHECK(c.partial_elems >= L.elems, "gemm_score: partial buffer too small");
+        if (L.acc) ADALOG_ARG_CHECK(((uintptr_t)c.partial & 7) == 0, "gemm_score: accumulator buffer must be 8-byte aligned");
+        GemmArgs p = gemm_args_mixed(c, L);
+        p.gm = stream_gm(L, p.KbA);
         const size_t shm = (size_t)3 * (2 * 64 * L.tm + BN2) * BK3;
-#define LAUNCH_STREAM_MX(RIV)                                                                                     \
-        do {                                                                                                      \
-            static unsigned long long attr_dev = 0; \
-            { hipError_t ea__ = adalog_max_lds(reinterpret_cast<const void*>(&k_gemm_stream<1, RIV, 8, 3, true>), (int)(150 * 1024), &attr_dev); \
-              if (ea__ != hipSuccess) { adalog_set_error("hipFuncSetAttribute", ea__); return (int)ea__; } } \
-            adalog_note_kernel("k_gemm_stream<bf16xfp8>");                                                        \
-            hipLaunchKernelGGL((k_gemm_stream<1, RIV, 8, 3, true>), dim3((unsigned)L.wgs), dim3(512), shm, st, p); \
-        } while (0)
-        if (L.wide == 4) LAUNCH_STREAM_MX(4); else LAUNCH_STREAM_MX(3);
-#undef LAUNCH_STREAM_MX
+        if (const int e = adalog_dispatch<4, 3>(L.wide, [&](auto ri) {
+                return adalog_launch<k_gemm_stream<1, decltype(ri)::value, 8, 3, true>>("k_gemm_stream<bf16xfp8>", 150 * 1024, (unsigned)L.wgs, 512,
+                                                                                        shm, st, p);
+            })) return e;
         ADALOG_LAUNCH_CHECK("adalog_gemm_score (bf16 x fp8, streaming)");
         return 0;
     }
     if (dtype == 4) {
         // mixed operands: one kernel, one shape family (adalog_gemm_mixed_ok)
         const bool window = k_valid > 0 && k_valid <= 64;
-        const bool ktrim = !window && Kp == 208 && grpk8t_ok(M, N, G, gmod, ref_div, k_valid, bias, row_scale, sb_n, ref_cs);
-        ADALOG_ARG_CHECK((Kp == (window ? 64 : 256) || ktrim) && k_valid > 0 && C == 1 && partial && ref && !out && ldr == 1 && reduce_cols == 1 &&
+        const bool ktrim = !window && Kp == 208 && grpk8t_ok(c);
+        ADALOG_ARG_CHECK((Kp == (window ? 64 : 256) || ktrim) && k_valid > 0 && C == 1 && c.partial && c.ref && !c.out && c.ldr == 1 && c.reduce_cols == 1 &&
                          adalog_gemm_mixed_ok(M, N, G, gmod, ref_div, k_valid),
                          "gemm_score: bf16 x fp8 operands are taken for the shapes adalog_gemm_mixed_ok accepts only (Kp = 64 or 256, or 208 where adalog_gemm_mixed_ktrim says so; C = 1, transposed reference)");
-        const Layout L = layout_of(M, N, C, G, gmod, ref_div, reduce_cols, true, k_valid * 2, Kp * 2, true, 1);
-        ADALOG_ARG_CHECK(window ? winb_ok(M, N, G, gmod, ref_div, k_valid, bias, row_scale, sb_n, ref_cs, L.wgs)
-                                : grpk8_ok(M, N, G, gmod, ref_div, k_valid, bias, row_scale, sb_n, ref_cs),
+        const Layout L = call_layout(c, true);
+        ADALOG_ARG_CHECK(route_of(c, L) == (window ? R_MX_WIN : ktrim ? R_MX_GRPK8T : R_MX_GRPK8),
                          "gemm_score: bf16 x fp8 operands: epilogue options not supported for this shape");
-        GemmArgs p{};
-        p.A = (const uint8_t*)A; p.B = (const uint8_t*)B;
-        p.sAc = sAc * 2; p.sAg = sAg * 2; p.sBc = sBc; p.sBg = sBg;
-        p.M = M; p.N = N; p.Kb = Kp; p.KbA = Kp * 2; p.Kvb = k_valid; p.C = C; p.G = G; p.gmod = gmod;
-        p.ref = ref; p.ldr = ldr; p.sRg = sRg; p.ref_cs = ref_cs; p.ref_div = ref_div;
-        p.sa = sa; p.sa_c = sa_c; p.sa_g = sa_g; p.sa_mul = sa_mul;
-        p.sb = sb; p.sb_c = sb_c; p.sb_g = sb_g; p.sb_n = sb_n;
-        p.MT = L.MT; p.NT = L.NT; p.Npad = L.Npad; p.order = order; p.reduce_cols = 0; p.partial = partial;
-        ADALOG_ARG_CHECK(partial_elems >= L.elems && ((uintptr_t)partial & 7) == 0, "gemm_score: accumulator buffer too small or misaligned");
-        p.wg_acc = (double*)partial;
-        hipStream_t st = (hipStream_t)stream;
+        ADALOG_ARG_CHECK(c.partial_elems >= L.elems && ((uintptr_t)c.partial & 7) == 0, "gemm_score: accumulator buffer too small or misaligned");
+        GemmArgs p = gemm_args_mixed(c, L);
+        p.bias = nullptr; p.bi_c = 0; p.bi_g = 0; p.bi_n = 0; p.row_bias = nullptr;     // the group / window kernels take no bias, no row vectors
         if (window) {
             const int n_eff = N / ref_div;
             const size_t ref_lds = (size_t)4 * n_eff * 64 * 4, acc_lds = (size_t)gmod * 256 * 8;
             const size_t shm_w = ref_lds > acc_lds ? ref_lds : acc_lds;
             if (const int e = with_nj(ref_div, [&](auto nj) {
-                    return launch_attn<k_gemm_winb<decltype(nj)::value>>("k_gemm_winb<bf16xfp8>", 80 * 1024, L.wgs, 256, shm_w, st, p);
+                    return adalog_launch<k_gemm_winb<decltype(nj)::value>>("k_gemm_winb<bf16xfp8>", 80 * 1024, (unsigned)L.wgs, 256, shm_w, st, p);
                 })) return e;
             ADALOG_LAUNCH_CHECK("adalog_gemm_score (bf16 x fp8, windows)");
             return 0;
@@ -416,53 +468,38 @@ static int gemm_score_impl(int dtype, const void* A, const void* B, int64_t sAc,
             const size_t shm_t = (size_t)3 * 4 * 32 * 208 + (size_t)7 * ref_div * 4 + (size_t)gmod * 256 * 8;   // 3 stages of 4 blocks x 208 bytes
             if (const int e = with_nj(ref_div, [&](auto nj) {
                     constexpr int NJ = decltype(nj)::value;
-                    return k_valid <= 200 ? launch_attn<k_gemm_grpk8t<NJ, 13>>("k_gemm_grpk8t<13,bf16xfp8>", 160 * 1024, L.wgs, 512, shm_t, st, p)
-                                          : launch_attn<k_gemm_grpk8t<NJ, 14>>("k_gemm_grpk8t<14,bf16xfp8>", 160 * 1024, L.wgs, 512, shm_t, st, p);
+                    return k_valid <= 200 ? adalog_launch<k_gemm_grpk8t<NJ, 13>>("k_gemm_grpk8t<13,bf16xfp8>", 160 * 1024, (unsigned)L.wgs, 512, shm_t, st, p)
+                                          : adalog_launch<k_gemm_grpk8t<NJ, 14>>("k_gemm_grpk8t<14,bf16xfp8>", 160 * 1024, (unsigned)L.wgs, 512, shm_t, st, p);
                 })) return e;
             ADALOG_LAUNCH_CHECK("adalog_gemm_score (bf16 x fp8, trimmed K)");
             return 0;
         }
         const size_t shm = (size_t)3 * 4 * 4 * 32 * BK3 + (size_t)7 * ref_div * 4 + (size_t)gmod * 256 * 8;   // 3 stages of 4 K-steps x 4 blocks
         if (const int e = with_nj(ref_div, [&](auto nj) {
-                return launch_attn<k_gemm_grpk8<decltype(nj)::value, 4>>("k_gemm_grpk8<bf16xfp8>", 160 * 1024, L.wgs, 512, shm, st, p);
+                return adalog_launch<k_gemm_grpk8<decltype(nj)::value, 4>>("k_gemm_grpk8<bf16xfp8>", 160 * 1024, (unsigned)L.wgs, 512, shm, st, p);
             })) return e;
         ADALOG_LAUNCH_CHECK("adalog_gemm_score (bf16 x fp8)");
         return 0;
     }
-    const int esz = (dtype == 0 || dtype == 3) ? 1 : dtype == 1 ? 2 : 4;
+    const int esz = esz_a(dtype);
     ADALOG_ARG_CHECK(Kp > 0 && ((Kp * esz) % BK3 == 0 || (Kp * esz == 32 && (dtype == 0 || dtype == 3))),
                      "gemm_score: padded K must be a multiple of 64 bytes (32-byte rows: int8 / fp8, window kernel only)");
-    ADALOG_ARG_CHECK((partial != nullptr) == (ref != nullptr), "gemm_score: partial and ref go together");
-    ADALOG_ARG_CHECK(partial || out, "gemm_score: nothing to produce");
-    ADALOG_ARG_CHECK(order >= 0 && order <= 2, "gemm_score: order must be 0, 1 or 2");
-    ADALOG_ARG_CHECK(ref_div == 1 || (C == 1 && N % ref_div == 0 && !out), "gemm_score: ref_div > 1 needs C == 1, N % ref_div == 0, no out");
-    ADALOG_ARG_CHECK(!row_scale || (C == 1 && row_bias), "gemm_score: per-row scale needs C == 1 and a row_bias vector");
-    ADALOG_ARG_CHECK(!(partial && out), "gemm_score: either score against ref or store out, not both");
-    const Layout L = layout_of(M, N, C, G, gmod, ref_div, reduce_cols, out == nullptr, (k_valid > 0 ? k_valid : Kp) * esz, Kp * esz,
-                               ldr == 1 && ref != nullptr, dtype);
-    GemmArgs p{};
-    p.A = (const uint8_t*)A; p.B = (const uint8_t*)B;
-    p.sAc = sAc * esz; p.sAg = sAg * esz; p.sBc = sBc * esz; p.sBg = sBg * esz;
+    ADALOG_ARG_CHECK((c.partial != nullptr) == (c.ref != nullptr), "gemm_score: partial and ref go together");
+    ADALOG_ARG_CHECK(c.partial || c.out, "gemm_score: nothing to produce");
+    ADALOG_ARG_CHECK(c.order >= 0 && c.order <= 2, "gemm_score: order must be 0, 1 or 2");
+    ADALOG_ARG_CHECK(ref_div == 1 || (C == 1 && N % ref_div == 0 && !c.out), "gemm_score: ref_div > 1 needs C == 1, N % ref_div == 0, no out");
+    ADALOG_ARG_CHECK(!c.row_scale || (C == 1 && c.row_bias), "gemm_score: per-row scale needs C == 1 and a row_bias vector");
+    ADALOG_ARG_CHECK(!(c.partial && c.out), "gemm_score: either score against ref or store out, not both");
+    const Layout L = call_layout(c, c.ldr == 1 && c.ref != nullptr);
     ADALOG_ARG_CHECK(k_valid >= 0 && k_valid <= Kp, "gemm_score: k_valid must be in [0, Kp]");
-    p.M = M; p.N = N; p.Kb = Kp * esz; p.Kvb = (k_valid > 0 ? k_valid : Kp) * esz; p.C = C; p.G = G; p.gmod = gmod;
-    p.ref = ref; p.ldr = ldr; p.sRg = sRg; p.ref_cs = ref_cs; p.ref_div = ref_div;
-    ADALOG_ARG_CHECK(!ref || ((int64_t)(M - 1) * ldr + (int64_t)(L.n_eff - 1) * (ref_cs > 0 ? ref_cs : 1) < ((int64_t)1 << 31)),
+    ADALOG_ARG_CHECK(!c.ref || ((int64_t)(M - 1) * c.ldr + (int64_t)(L.n_eff - 1) * (c.ref_cs > 0 ? c.ref_cs : 1) < ((int64_t)1 << 31)),
                      "gemm_score: reference group exceeds 32-bit addressing");
-    p.sa = sa; p.sa_c = sa_c; p.sa_g = sa_g; p.sa_mul = sa_mul;
-    p.sb = sb; p.sb_c = sb_c; p.sb_g = sb_g; p.sb_n = sb_n;
-    p.bias = bias; p.bi_c = bi_c; p.bi_g = bi_g; p.bi_n = bi_n;
-    p.row_scale = row_scale; p.row_bias = row_bias;
-    p.MT = L.MT; p.NT = L.NT; p.Npad = L.Npad;
-    p.order = order; p.reduce_cols = reduce_cols && ref_div == 1; p.timeline = g_timeline;
-    p.partial = partial; p.out = out; p.ldo = ldo; p.sOc = sOc; p.sOg = sOg;
-    if (ox) { p.addend = ox->addend; p.out_gi = ox->out_gi; p.sOo = ox->sOo; }
-    if (partial) ADALOG_ARG_CHECK(partial_elems >= L.elems, "gemm_score: partial buffer too small");
-    if (L.acc) { ADALOG_ARG_CHECK(((uintptr_t)partial & 7) == 0, "gemm_score: accumulator buffer must be 8-byte aligned"); p.wg_acc = (double*)partial; }
+    if (c.partial) ADALOG_ARG_CHECK(c.partial_elems >= L.elems, "gemm_score: partial buffer too small");
+    if (L.acc) ADALOG_ARG_CHECK(((uintptr_t)c.partial & 7) == 0, "gemm_score: accumulator buffer must be 8-byte aligned");
+    GemmArgs p = gemm_args(c, L);
+    const Route route = route_of(c, L);
     if (gen) {
-        const bool win = L.stream && !out && L.acc && !L.slab && win_ok(dtype, M, N, G, gmod, ref_div, p.Kvb, bias, row_scale, sb_n, ref_cs, L.wgs);
-        const bool grpw = L.stream && !out && L.acc && !L.slab && grp_ok(dtype, M, N, G, gmod, ref_div, p.Kvb, bias, row_scale, sb_n, ref_cs) &&
-                          grpw_on() && L.wgs * 4 >= gmod && ref_cs >= M;
-        ADALOG_ARG_CHECK(win || grpw, "gemm_score_gen: not a shape of the window / wave-private group kernels (adalog_gemm_score_gen_ok)");
+        ADALOG_ARG_CHECK(route == R_WIN || route == R_GRPW, "gemm_score_gen: not a shape of the window / wave-private group kernels (adalog_gemm_score_gen_ok)");
         p.gen_x = gen->x; p.gen_ldx = gen->ldx; p.gen_sg = gen->sg; p.gen_K = (int)k_valid; p.gen_zp = gen->zp;
         p.gen_qmax = (float)((1 << gen->n_bits) - 1);
         const float tie = 6e-7f * (float)(1 << gen->n_bits);
@@ -470,189 +507,122 @@ static int gemm_score_impl(int dtype, const void* A, const void* B, int64_t sAc,
     }
     const int64_t nwg = (int64_t)L.MT * L.NT * G * C;
     ADALOG_ARG_CHECK(nwg < (int64_t)1 << 31, "gemm_score: grid too large");
-    hipStream_t st = (hipStream_t)stream;
-    dim3 grid((unsigned)nwg);
-    static const int use_glds = getenv("ADALOG_GEMM_GLDS") ? atoi(getenv("ADALOG_GEMM_GLDS")) : 1;   // LDS-DMA pipeline (default on)
-    ADALOG_ARG_CHECK((Kp * esz) % BK2 == 0 || (L.stream && !out),
+    const unsigned grid = (unsigned)nwg, wgs = (unsigned)L.wgs;
+    ADALOG_ARG_CHECK((Kp * esz) % BK2 == 0 || (L.stream && !c.out),
                      "gemm_score: rows padded to 64 (not 128) bytes are taken by the streaming search kernel only");
-    ADALOG_ARG_CHECK((Kp * esz) % BK3 == 0 || (L.stream && !out && L.acc && win_ok(dtype, M, N, G, gmod, ref_div, p.Kvb, bias, row_scale, sb_n, ref_cs, L.wgs)),
-                     "gemm_score: 32-byte rows are taken by the window kernel only (adalog_gemm_win_ok)");
-    ADALOG_ARG_CHECK(dtype != 3 || (L.stream && !out), "gemm_score: fp8 operands are taken by the streaming search kernel only (ref_div 64/128/256, transposed reference)");
-    if (L.slab && !out) {
+    ADALOG_ARG_CHECK((Kp * esz) % BK3 == 0 || route == R_WIN, "gemm_score: 32-byte rows are taken by the window kernel only (adalog_gemm_win_ok)");
+    ADALOG_ARG_CHECK(dtype != 3 || (L.stream && !c.out), "gemm_score: fp8 operands are taken by the streaming search kernel only (ref_div 64/128/256, transposed reference)");
+    const int n_eff = N / ref_div;
+    const size_t acc_lds = (size_t)gmod * 256 * 8;                    // per-head fp64 sums of the group / window kernels
+    int e = 0;
+    switch (route) {
+    case R_SLAB: {
         // slab kernel: one workgroup per CU, each takes a contiguous range of (slab, unit) pairs
-        p.MT = L.MT; p.NT = L.NT; p.slab_U = L.slab_U; p.slab_R = L.slab_R;
-        const int nk = (int)((p.Kvb + BK3 - 1) / BK3);
-        const int SBN = 32 * L.slab_nb;
-        const size_t shm = (size_t)nk * SBN * BK3 + 8 * 3 * 32 * BK3 + 8 * 192 * 4 + 8 * SBN * 4;
+        p.slab_U = L.slab_U; p.slab_R = L.slab_R;
+        const size_t shm = slab_lds(p.Kvb, L.slab_nb);
         // a slab that is not cut has unused pieces: they must read as zero
         if (!L.acc) {
-            const hipError_t me = hipMemsetAsync(partial, 0, (size_t)L.elems * sizeof(float), st);
+            const hipError_t me = hipMemsetAsync(c.partial, 0, (size_t)L.elems * sizeof(float), st);
             if (me != hipSuccess) { adalog_set_error("adalog_gemm_score (clear partials)", me); return (int)me; }
         }
-        const int nref = SBN / ref_div;
-#define LAUNCH_SLAB(NREFV, ROWSV, DTV, NBV)                                                                       \
-        do {                                                                                                      \
-            static unsigned long long attr_dev = 0; \
-            { hipError_t ea__ = adalog_max_lds(reinterpret_cast<const void*>(&k_gemm_slab<NREFV, ROWSV, DTV, NBV>), (int)(160 * 1024), &attr_dev); \
-              if (ea__ != hipSuccess) { adalog_set_error("hipFuncSetAttribute", ea__); return (int)ea__; } } \
-            adalog_note_kernel(DTV == 3 ? (NBV == 8 ? "k_gemm_slab<fp8>" : "k_gemm_slab128<fp8>") : (NBV == 8 ? "k_gemm_slab<i8>" : "k_gemm_slab128<i8>")); \
-            hipLaunchKernelGGL((k_gemm_slab<NREFV, ROWSV, DTV, NBV>), dim3((unsigned)L.wgs), dim3(512), shm, st, p); \
-        } while (0)
-#define LAUNCH_SLAB_DT(DTV)                                                                                       \
-        do {                                                                                                      \
-            if (L.slab_nb == 8) {                                                                                 \
-                if (row_scale) { if (nref == 1) LAUNCH_SLAB(1, true, DTV, 8); else if (nref == 2) LAUNCH_SLAB(2, true, DTV, 8); else LAUNCH_SLAB(4, true, DTV, 8); } \
-                else { if (nref == 1) LAUNCH_SLAB(1, false, DTV, 8); else if (nref == 2) LAUNCH_SLAB(2, false, DTV, 8); else LAUNCH_SLAB(4, false, DTV, 8); } \
-            } else {                                                                                              \
-                if (row_scale) { if (nref == 1) LAUNCH_SLAB(1, true, DTV, 4); else LAUNCH_SLAB(2, true, DTV, 4); } \
-                else { if (nref == 1) LAUNCH_SLAB(1, false, DTV, 4); else LAUNCH_SLAB(2, false, DTV, 4); }        \
-            }                                                                                                     \
-        } while (0)
-        if (dtype == 3) LAUNCH_SLAB_DT(3); else LAUNCH_SLAB_DT(0);
-#undef LAUNCH_SLAB_DT
-#undef LAUNCH_SLAB
-    } else if (L.stream && !out && L.acc && win_ok(dtype, M, N, G, gmod, ref_div, p.Kvb, bias, row_scale, sb_n, ref_cs, L.wgs)) {
+        e = with_slab(dtype, L.slab_nb, ref_div, [&](auto nr, auto dt, auto nb) {
+            constexpr int NREF = decltype(nr)::value, DT = decltype(dt)::value, NB = decltype(nb)::value;
+            return adalog_dispatch<true, false>(c.row_scale != nullptr, [&](auto rows) {
+                return adalog_launch<k_gemm_slab<NREF, decltype(rows)::value, DT, NB>>(slab_label(0, DT, NB), 160 * 1024, wgs, 512, shm, st, p);
+            });
+        });
+    } break;
+    case R_WIN: {
         // window kernel (swin attention searches): a wave per group, same accumulator layout and workgroup count
-        const int n_eff = N / ref_div;
-        const size_t ref_lds = (size_t)4 * n_eff * 64 * 4, acc_lds = (size_t)gmod * 256 * 8;
-        const size_t shm = ref_lds > acc_lds ? ref_lds : acc_lds;
-        if (const int e = with_nj(ref_div, [&](auto nj) {
-                constexpr int NJ = decltype(nj)::value;
-                if (dtype == 3)
-                    return gen ? launch_attn<k_gemm_win<NJ, 3, true>>("k_gemm_win_gen<fp8>", 80 * 1024, L.wgs, 256, shm, st, p)
-                               : launch_attn<k_gemm_win<NJ, 3>>("k_gemm_win<fp8>", 80 * 1024, L.wgs, 256, shm, st, p);
-                return gen ? launch_attn<k_gemm_win<NJ, 0, true>>("k_gemm_win_gen<i8>", 80 * 1024, L.wgs, 256, shm, st, p)
-                           : launch_attn<k_gemm_win<NJ, 0>>("k_gemm_win<i8>", 80 * 1024, L.wgs, 256, shm, st, p);
-            })) return e;
-    } else if (L.stream && !out && L.acc && grp_ok(dtype, M, N, G, gmod, ref_div, p.Kvb, bias, row_scale, sb_n, ref_cs) &&
-               grpw_on() && L.wgs * 4 >= gmod && ref_cs >= M) {
+        const size_t ref_lds = (size_t)4 * n_eff * 64 * 4, shm = ref_lds > acc_lds ? ref_lds : acc_lds;
+        e = with_nj(ref_div, [&](auto nj) {
+            constexpr int NJ = decltype(nj)::value;
+            if (dtype == 3)
+                return gen ? adalog_launch<k_gemm_win<NJ, 3, true>>("k_gemm_win_gen<fp8>", 80 * 1024, wgs, 256, shm, st, p)
+                           : adalog_launch<k_gemm_win<NJ, 3>>("k_gemm_win<fp8>", 80 * 1024, wgs, 256, shm, st, p);
+            return gen ? adalog_launch<k_gemm_win<NJ, 0, true>>("k_gemm_win_gen<i8>", 80 * 1024, wgs, 256, shm, st, p)
+                       : adalog_launch<k_gemm_win<NJ, 0>>("k_gemm_win<i8>", 80 * 1024, wgs, 256, shm, st, p);
+        });
+    } break;
+    case R_GRPW: {
         // wave-private group kernel (q.k^T searches): a wave per (group, chunk of reference columns), no barrier in the loop
-        const int n_eff = N / ref_div;
-        const int64_t waves = (int64_t)L.wgs * 4;
-        int nch = (int)cdiv(3 * waves, G);
-        nch = nch < 1 ? 1 : nch > n_eff ? n_eff : nch;
-        const int cbc = cdiv(n_eff, nch);
-        p.slab_R = cbc; p.slab_U = cdiv(n_eff, cbc);
-        const size_t ref_lds = (size_t)4 * 2 * 224 * 4, acc_lds = (size_t)gmod * 256 * 8;
-        const size_t shm = ref_lds > acc_lds ? ref_lds : acc_lds;
-        if (const int e = with_nj(ref_div, [&](auto nj) {             // (no LDS-limit call: 3.5 KiB, or gmod x 2 KiB <= 32 KiB)
-                constexpr int NJ = decltype(nj)::value;
-                if (dtype == 3)
-                    return gen ? launch_attn<k_gemm_grpw<NJ, 3, true>>("k_gemm_grpw_gen<fp8>", 0, L.wgs, 256, shm, st, p)
-                               : launch_attn<k_gemm_grpw<NJ, 3>>("k_gemm_grpw<fp8>", 0, L.wgs, 256, shm, st, p);
-                return gen ? launch_attn<k_gemm_grpw<NJ, 0, true>>("k_gemm_grpw_gen<i8>", 0, L.wgs, 256, shm, st, p)
-                           : launch_attn<k_gemm_grpw<NJ, 0>>("k_gemm_grpw<i8>", 0, L.wgs, 256, shm, st, p);
-            })) return e;
-    } else if (L.stream && !out && L.acc && grp_ok(dtype, M, N, G, gmod, ref_div, p.Kvb, bias, row_scale, sb_n, ref_cs)) {
+        wave_chunks(p, n_eff, L.wgs, G);
+        const size_t ref_lds = (size_t)4 * 2 * 224 * 4, shm = ref_lds > acc_lds ? ref_lds : acc_lds;
+        e = with_nj(ref_div, [&](auto nj) {                           // (no LDS-limit call: 3.5 KiB, or gmod x 2 KiB <= 32 KiB)
+            constexpr int NJ = decltype(nj)::value;
+            if (dtype == 3)
+                return gen ? adalog_launch<k_gemm_grpw<NJ, 3, true>>("k_gemm_grpw_gen<fp8>", 0, wgs, 256, shm, st, p)
+                           : adalog_launch<k_gemm_grpw<NJ, 3>>("k_gemm_grpw<fp8>", 0, wgs, 256, shm, st, p);
+            return gen ? adalog_launch<k_gemm_grpw<NJ, 0, true>>("k_gemm_grpw_gen<i8>", 0, wgs, 256, shm, st, p)
+                       : adalog_launch<k_gemm_grpw<NJ, 0>>("k_gemm_grpw<i8>", 0, wgs, 256, shm, st, p);
+        });
+    } break;
+    case R_GRP: {
         // group kernel (q.k^T searches): same accumulator layout and workgroup count as the streaming kernel
         grp_chunks(p, N, L.wgs, G);
-        const size_t shm = (size_t)3 * 8 * 32 * BK3 + 7 * 256 * 4 + (size_t)gmod * 256 * 8;
-        if (const int e = with_nj(ref_div, [&](auto nj) {
-                constexpr int NJ = decltype(nj)::value;
-                return dtype == 3 ? launch_attn<k_gemm_grp<NJ, 3>>("k_gemm_grp<fp8>", 96 * 1024, L.wgs, 512, shm, st, p)
-                                  : launch_attn<k_gemm_grp<NJ, 0>>("k_gemm_grp<i8>", 96 * 1024, L.wgs, 512, shm, st, p);
-            })) return e;
-    } else if (L.stream && !out && L.acc && grpk_ok(dtype, M, N, G, gmod, ref_div, p.Kvb, bias, row_scale, sb_n, ref_cs)) {
+        const size_t shm = (size_t)3 * 8 * 32 * BK3 + 7 * 256 * 4 + acc_lds;
+        e = with_nj(ref_div, [&](auto nj) {
+            constexpr int NJ = decltype(nj)::value;
+            return dtype == 3 ? adalog_launch<k_gemm_grp<NJ, 3>>("k_gemm_grp<fp8>", 96 * 1024, wgs, 512, shm, st, p)
+                              : adalog_launch<k_gemm_grp<NJ, 0>>("k_gemm_grp<i8>", 96 * 1024, wgs, 512, shm, st, p);
+        });
+    } break;
+    case R_GRPK: {
         // group kernel, 7 K-steps (softmax.v weight search)
         grp_chunks(p, N, L.wgs, G);
-        const size_t shm = (size_t)3 * 7 * 2 * 32 * BK3 + (size_t)7 * ref_div * 4 + (size_t)gmod * 256 * 8;
-        if (const int e = with_nj(ref_div, [&](auto nj) {
-                return launch_attn<k_gemm_grpk<decltype(nj)::value, 7>>("k_gemm_grpk<bf16>", 160 * 1024, L.wgs, 512, shm, st, p);
-            })) return e;
-    } else if (L.stream && !out) {
+        const size_t shm = (size_t)3 * 7 * 2 * 32 * BK3 + (size_t)7 * ref_div * 4 + acc_lds;
+        e = with_nj(ref_div, [&](auto nj) {
+            return adalog_launch<k_gemm_grpk<decltype(nj)::value, 7>>("k_gemm_grpk<bf16>", 160 * 1024, wgs, 512, shm, st, p);
+        });
+    } break;
+    case R_STREAM: {
         // persistent streaming kernel: two (wide form: one) workgroups per CU walk the tile list
-        {   // m-tiles per group: the group's A rows are re-read once per n-tile (from L2 / the 256 MiB Infinity Cache), the B
-            // tiles stream from HBM once per GROUP -- with the candidate operand at 150..600 MB per launch that stream is
-            // what must not repeat: groups of <= 8 MiB of A rows (2 MiB, half of an XCD's L2, re-read vit_base's fc2
-            // candidates 25 times: 4.16 -> 4.05 s per calibration, 3.99 at 64 MiB; deit_small -- its operand fits the
-            // Infinity Cache -- is indifferent up to 16 MiB and 2 % slower at 64)
-            static const int64_t grp_bytes = getenv("ADALOG_GEMM_GM_BYTES") ? atoll(getenv("ADALOG_GEMM_GM_BYTES")) : ((int64_t)8 << 20);
-            const int64_t a_tile = (int64_t)64 * L.tm * p.Kb;
-            int64_t gm = grp_bytes / a_tile;
-            if (const char* e = getenv("ADALOG_GEMM_GM")) gm = atoi(e);
-            p.gm = (int)(gm < 1 ? 1 : gm > L.MT ? L.MT : gm);
-        }
-        dim3 pgrid((unsigned)L.wgs);
+        p.gm = stream_gm(L, p.Kb);
         const size_t shm = (size_t)(L.wide ? 4 : 3) * (64 * L.tm + BN2) * BK3;
-#define LAUNCH_STREAM(DT, RIV, NWV, NSV)                                                                          \
-        do {                                                                                                      \
-            static unsigned long long attr_dev = 0; \
-            { hipError_t ea__ = adalog_max_lds(reinterpret_cast<const void*>(&k_gemm_stream<DT, RIV, NWV, NSV>), (int)((NSV == 4 ? 128 : 80) * 1024), &attr_dev); \
-              if (ea__ != hipSuccess) { adalog_set_error("hipFuncSetAttribute", ea__); return (int)ea__; } } \
-            adalog_note_kernel(DT == 0 ? "k_gemm_stream<i8>" : DT == 1 ? "k_gemm_stream<bf16>" : DT == 2 ? "k_gemm_stream<f32>" : "k_gemm_stream<fp8>"); \
-            hipLaunchKernelGGL((k_gemm_stream<DT, RIV, NWV, NSV>), pgrid, dim3(64 * NWV), shm, st, p);            \
-        } while (0)
-#define LAUNCH_STREAM_DT(DT)                                                                                      \
-        do {                                                                                                      \
-            if (L.wide == 4) LAUNCH_STREAM(DT, 4, 8, 4); else if (L.wide == 3) LAUNCH_STREAM(DT, 3, 8, 4);        \
-            else if (L.tm == 2) LAUNCH_STREAM(DT, 2, 4, 3); else LAUNCH_STREAM(DT, 1, 4, 3);                      \
-        } while (0)
-        if (dtype == 0) LAUNCH_STREAM_DT(0); else if (dtype == 1) LAUNCH_STREAM_DT(1); else if (dtype == 2) LAUNCH_STREAM_DT(2);
-        else LAUNCH_STREAM_DT(3);
-#undef LAUNCH_STREAM_DT
-#undef LAUNCH_STREAM
-    } else if (L.big && use_glds && !out && L.tm <= 2) {
+        // row tiles of 256 / 192 rows (wide form: 8 waves, 4 stages) or 128 / 64 rows (4 waves, 3 stages)
+        e = adalog_dispatch<0, 1, 2, 3>(dtype, [&](auto dt) {
+            return adalog_dispatch<4, 3, 2, 1>(L.wide ? L.wide : L.tm, [&](auto ri) {
+                constexpr int DT = decltype(dt)::value, RI = decltype(ri)::value, NW = RI >= 3 ? 8 : 4, NS = RI >= 3 ? 4 : 3;
+                return adalog_launch<k_gemm_stream<DT, RI, NW, NS>>(
+                    DT == 0 ? "k_gemm_stream<i8>" : DT == 1 ? "k_gemm_stream<bf16>" : DT == 2 ? "k_gemm_stream<f32>" : "k_gemm_stream<fp8>",
+                    (NS == 4 ? 128 : 80) * 1024, wgs, 64 * NW, shm, st, p);
+            });
+        });
+    } break;
+    case R_GLDS: {
         const size_t shm = (size_t)3 * (64 * L.tm + BN2) * BK2 + (512 + 256) * sizeof(float);
-#define LAUNCH_GLDS(DT, TMV)                                                                                      \
-        do {                                                                                                      \
-            static unsigned long long attr_dev = 0; \
-            { hipError_t ea__ = adalog_max_lds(reinterpret_cast<const void*>(&k_gemm_cand_glds<DT, TMV>), (int)(160 * 1024), &attr_dev); \
-              if (ea__ != hipSuccess) { adalog_set_error("hipFuncSetAttribute", ea__); return (int)ea__; } } \
-            adalog_note_kernel("k_gemm_cand_glds");                                                               \
-            hipLaunchKernelGGL((k_gemm_cand_glds<DT, TMV>), grid, dim3(512), shm, st, p);                         \
-        } while (0)
-        if (dtype == 0) { if (L.tm == 2) LAUNCH_GLDS(0, 2); else LAUNCH_GLDS(0, 1); }
-        else if (dtype == 1) { if (L.tm == 2) LAUNCH_GLDS(1, 2); else LAUNCH_GLDS(1, 1); }
-        else { if (L.tm == 2) LAUNCH_GLDS(2, 2); else LAUNCH_GLDS(2, 1); }
-#undef LAUNCH_GLDS
-    } else if (L.big) {
+        e = adalog_dispatch<0, 1, 2>(dtype, [&](auto dt) {
+            return adalog_dispatch<2, 1>(L.tm, [&](auto tm) {
+                return adalog_launch<k_gemm_cand_glds<decltype(dt)::value, decltype(tm)::value>>("k_gemm_cand_glds", 160 * 1024, grid, 512, shm, st, p);
+            });
+        });
+    } break;
+    case R_CAND: {
         const size_t shm = (size_t)(64 * L.tm + BN2) * BK2 + (512 + 256) * sizeof(float);
-#define LAUNCH_BIG(DT, TMV, ST)                                                                                   \
-        do {                                                                                                      \
-            static unsigned long long attr_dev = 0; \
-            { hipError_t ea__ = adalog_max_lds(reinterpret_cast<const void*>(&k_gemm_cand<DT, TMV, ST>), (int)(72 * 1024), &attr_dev); \
-              if (ea__ != hipSuccess) { adalog_set_error("hipFuncSetAttribute", ea__); return (int)ea__; } } \
-            adalog_note_kernel("k_gemm_cand");                                                                    \
-            hipLaunchKernelGGL((k_gemm_cand<DT, TMV, ST>), grid, dim3(512), shm, st, p);                          \
-        } while (0)
-#define LAUNCH_BIG_TM(DT, ST)                                                                                     \
-        do {                                                                                                      \
-            if (L.tm == 4) LAUNCH_BIG(DT, 4, ST); else if (L.tm == 2) LAUNCH_BIG(DT, 2, ST); else LAUNCH_BIG(DT, 1, ST); \
-        } while (0)
-#define LAUNCH_BIG_DT(ST)                                                                                         \
-        do {                                                                                                      \
-            if (dtype == 0) LAUNCH_BIG_TM(0, ST); else if (dtype == 1) LAUNCH_BIG_TM(1, ST); else LAUNCH_BIG_TM(2, ST); \
-        } while (0)
-        if (out && ox) {
-            // the STORE form with the epilogue extras (int8 / bf16 operands)
-#define LAUNCH_ADD(DT, TMV)                                                                                       \
-        do {                                                                                                      \
-            static unsigned long long attr_dev = 0;                                                               \
-            { hipError_t ea__ = adalog_max_lds(reinterpret_cast<const void*>(&k_gemm_cand<DT, TMV, true, false, true>), (int)(72 * 1024), &attr_dev); \
-              if (ea__ != hipSuccess) { adalog_set_error("hipFuncSetAttribute", ea__); return (int)ea__; } }     \
-            adalog_note_kernel("k_gemm_cand_ex");                                                                 \
-            hipLaunchKernelGGL((k_gemm_cand<DT, TMV, true, false, true>), grid, dim3(512), shm, st, p);           \
-        } while (0)
-            ADALOG_ARG_CHECK(dtype == 0 || dtype == 1, "gemm_out_ex: int8 or bf16 operands");
-            if (dtype == 0) { if (L.tm == 4) LAUNCH_ADD(0, 4); else if (L.tm == 2) LAUNCH_ADD(0, 2); else LAUNCH_ADD(0, 1); }
-            else { if (L.tm == 4) LAUNCH_ADD(1, 4); else if (L.tm == 2) LAUNCH_ADD(1, 2); else LAUNCH_ADD(1, 1); }
-#undef LAUNCH_ADD
-        } else if (out) LAUNCH_BIG_DT(true); else LAUNCH_BIG_DT(false);
-#undef LAUNCH_BIG_DT
-#undef LAUNCH_BIG_TM
-#undef LAUNCH_BIG
-    } else {
-        ADALOG_ARG_CHECK(!row_scale, "gemm_score: per-row scale is only available with C == 1");
-        dim3 block(256);
-#define LAUNCH(DT)                                                                                   \
-        do {                                                                                         \
-            adalog_note_kernel("k_gemm_score");                                                      \
-            if (out) hipLaunchKernelGGL((k_gemm_score<DT, true>), grid, block, 0, st, p);            \
-            else hipLaunchKernelGGL((k_gemm_score<DT, false>), grid, block, 0, st, p);               \
-        } while (0)
-        if (dtype == 0) LAUNCH(0); else if (dtype == 1) LAUNCH(1); else LAUNCH(2);
-#undef LAUNCH
+        if (c.out && c.ox) ADALOG_ARG_CHECK(dtype == 0 || dtype == 1, "gemm_out_ex: int8 or bf16 operands");
+        e = adalog_dispatch<4, 2, 1>(L.tm, [&](auto tm) {
+            constexpr int TM = decltype(tm)::value;
+            if (c.out && c.ox)        // the STORE form with the epilogue extras (int8 / bf16 operands)
+                return adalog_dispatch<0, 1>(dtype, [&](auto dt) {
+                    return adalog_launch<k_gemm_cand<decltype(dt)::value, TM, true, false, true>>("k_gemm_cand_ex", 72 * 1024, grid, 512, shm, st, p);
+                });
+            return adalog_dispatch<0, 1, 2>(dtype, [&](auto dt) {
+                return adalog_dispatch<true, false>(c.out != nullptr, [&](auto store) {
+                    return adalog_launch<k_gemm_cand<decltype(dt)::value, TM, decltype(store)::value>>("k_gemm_cand", 72 * 1024, grid, 512, shm, st, p);
+                });
+            });
+        });
+    } break;
+    default: {
+        ADALOG_ARG_CHECK(!c.row_scale, "gemm_score: per-row scale is only available with C == 1");
+        e = adalog_dispatch<0, 1, 2>(dtype, [&](auto dt) {
+            return adalog_dispatch<true, false>(c.out != nullptr, [&](auto store) {
+                return adalog_launch<k_gemm_score<decltype(dt)::value, decltype(store)::value>>("k_gemm_score", 0, grid, 256, 0, st, p);
+            });
+        });
+    } break;
     }
+    if (e) return e;
     ADALOG_LAUNCH_CHECK("adalog_gemm_score");
     return 0;
 }
@@ -664,9 +634,18 @@ extern "C" int adalog_gemm_score(int dtype, const void* A, const void* B, int64_
                                  const float* bias, int64_t bi_c, int64_t bi_g, int64_t bi_n, const float* row_scale,
                                  const float* row_bias, float* partial, int64_t partial_elems, float* out, int64_t ldo,
                                  int64_t sOc, int64_t sOg, int order, int reduce_cols, void* stream) {
-    return gemm_score_impl(dtype, A, B, sAc, sAg, sBc, sBg, M, N, Kp, k_valid, C, G, gmod, ref, ldr, sRg, ref_cs, ref_div, sa, sa_c, sa_g,
-                           sa_mul, sb, sb_c, sb_g, sb_n, bias, bi_c, bi_g, bi_n, row_scale, row_bias, partial, partial_elems, out, ldo,
-                           sOc, sOg, order, reduce_cols, stream, nullptr);
+    MmCall c{};
+    c.dtype = dtype; c.A = A; c.B = B; c.sAc = sAc; c.sAg = sAg; c.sBc = sBc; c.sBg = sBg;
+    c.M = M; c.N = N; c.Kp = Kp; c.k_valid = k_valid; c.C = C; c.G = G; c.gmod = gmod;
+    c.ref = ref; c.ldr = ldr; c.sRg = sRg; c.ref_cs = ref_cs; c.ref_div = ref_div;
+    c.sa = sa; c.sa_c = sa_c; c.sa_g = sa_g; c.sa_mul = sa_mul;
+    c.sb = sb; c.sb_c = sb_c; c.sb_g = sb_g; c.sb_n = sb_n;
+    c.bias = bias; c.bi_c = bi_c; c.bi_g = bi_g; c.bi_n = bi_n;
+    c.row_scale = row_scale; c.row_bias = row_bias;
+    c.partial = partial; c.partial_elems = partial_elems;
+    c.out = out; c.ldo = ldo; c.sOc = sOc; c.sOg = sOg;
+    c.order = order; c.reduce_cols = reduce_cols; c.stream = stream;
+    return gemm_score_impl(c);
 }
 
 // quant_forward product from packed operands with the epilogue extras (reference quant_layers/linear.py:46-51, matmul.py:43-45,
@@ -682,8 +661,14 @@ extern "C" int adalog_gemm_out_ex(int dtype, const void* A, const void* B, int64
                                   int64_t sOg, int out_gi, int64_t sOo, void* stream) {
     ADALOG_ARG_CHECK(out && (dtype == 0 || dtype == 1), "gemm_out_ex: int8 or bf16 operands, out required");
     const MmOutEx ox{addend, out_gi, sOo};
-    return gemm_score_impl(dtype, A, B, 0, sAg, 0, sBg, M, N, Kp, 0, 1, G, gmod, nullptr, 0, 0, 1, 1, sa, 0, sa_g, sa_mul, sb, 0, sb_g, sb_n,
-                           bias, 0, bi_g, bi_n, nullptr, nullptr, nullptr, 0, out, ldo, 0, sOg, 0, 0, stream, nullptr, &ox);
+    MmCall c{};                                                       // no candidate axis, no reference: ref_cs = ref_div = 1
+    c.dtype = dtype; c.A = A; c.B = B; c.sAg = sAg; c.sBg = sBg;
+    c.M = M; c.N = N; c.Kp = Kp; c.C = 1; c.G = G; c.gmod = gmod; c.ref_cs = 1; c.ref_div = 1;
+    c.sa = sa; c.sa_g = sa_g; c.sa_mul = sa_mul;
+    c.sb = sb; c.sb_g = sb_g; c.sb_n = sb_n;
+    c.bias = bias; c.bi_g = bi_g; c.bi_n = bi_n;
+    c.out = out; c.ldo = ldo; c.sOg = sOg; c.stream = stream; c.ox = &ox;
+    return gemm_score_impl(c);
 }
 
 // quant_forward of a uniformly quantised Linear layer / q.k^T product (reference quant_layers/linear.py:46-51, matmul.py:43-45) with
@@ -704,51 +689,44 @@ extern "C" int adalog_gemm_out_gen(const float* x, int64_t ldx, int64_t sxg, int
     return adalog_gemm_out_gen_ex(x, ldx, sxg, K, a_scale, a_zp, a_pg, n_bits, B, sBg, M, N, Kp, G, gmod, sa, sa_g, sa_mul, sb, sb_g, sb_n,
                                   bias, bi_g, bi_n, nullptr, out, ldo, sOg, stream);
 }
-static int gemm_out_gen_impl(const float* x, int64_t ldx, int64_t sxg, int K, const float* a_scale, const float* a_zp, int64_t a_pg,
-                             int n_bits, const void* B, int64_t sBg, int M, int N, int64_t Kp, int G, int gmod, const float* sa,
-                             int64_t sa_g, float sa_mul, const float* sb, int64_t sb_g, int64_t sb_n, const float* bias,
-                             int64_t bi_g, int64_t bi_n, const float* addend, float* out, int64_t ldo, int64_t sOg, const int* a_rows,
-                             const int* o_rows, int64_t period, void* stream) {
-    ADALOG_ARG_CHECK(x && a_scale && a_zp && B && sa && sb && out, "gemm_out_gen: null pointer");
+// The A side of adalog_gemm_out_gen and its relatives: the fp32 activation and its quantiser, the row maps (null = identity)
+struct MmGenA { const float* x; int64_t ldx, sxg; int K; const float *a_scale, *a_zp; int64_t a_pg; int n_bits; const int *a_rows, *o_rows; int64_t period; };
+
+// c: the store call (B, sizes, epilogue, out; addend in c.ox); g: where A comes from
+static int gemm_out_gen_impl(const MmCall& c, const MmGenA& g) {
+    const float *x = g.x, *a_scale = g.a_scale, *a_zp = g.a_zp, *addend = c.ox->addend;
+    const int64_t ldx = g.ldx, Kp = c.Kp;
+    const int K = g.K, n_bits = g.n_bits, M = c.M, N = c.N, G = c.G, gmod = c.gmod;
+    const void* B = c.B;
+    ADALOG_ARG_CHECK(x && a_scale && a_zp && B && c.sa && c.sb && c.out, "gemm_out_gen: null pointer");
     ADALOG_ARG_CHECK(M >= 1 && N >= 1 && G >= 1 && gmod >= 1 && G % gmod == 0 && K >= 16 && K % 16 == 0 && Kp >= K && Kp % BK2 == 0,
                      "gemm_out_gen: K must be a multiple of 16, Kp a multiple of 128 covering it");
-    ADALOG_ARG_CHECK(n_bits >= 2 && n_bits <= 7 && ldx >= K && ldx % 4 == 0 && sxg % 4 == 0 && (((uintptr_t)x) & 15) == 0 &&
+    ADALOG_ARG_CHECK(n_bits >= 2 && n_bits <= 7 && ldx >= K && ldx % 4 == 0 && g.sxg % 4 == 0 && (((uintptr_t)x) & 15) == 0 &&
                      (((uintptr_t)B) & 15) == 0, "gemm_out_gen: <= 7-bit quantiser, 16-byte aligned fp32 rows");
     ADALOG_ARG_CHECK((int64_t)M * ldx < ((int64_t)1 << 31) && (int64_t)N * Kp < ((int64_t)1 << 31), "gemm_out_gen: operand exceeds 32-bit addressing");
-    GemmArgs p{};
-    p.A = nullptr; p.B = (const uint8_t*)B; p.sAc = 0; p.sAg = 0; p.sBc = 0; p.sBg = sBg;
-    p.M = M; p.N = N; p.Kb = Kp; p.KbA = Kp; p.Kvb = K; p.C = 1; p.G = G; p.gmod = gmod;
-    p.ref = nullptr; p.ldr = 0; p.sRg = 0; p.ref_cs = 1; p.ref_div = 1;
-    p.sa = sa; p.sa_c = 0; p.sa_g = sa_g; p.sa_mul = sa_mul;
-    p.sb = sb; p.sb_c = 0; p.sb_g = sb_g; p.sb_n = sb_n;
-    p.bias = bias; p.bi_c = 0; p.bi_g = bi_g; p.bi_n = bi_n;
-    p.out = out; p.ldo = ldo; p.sOc = 0; p.sOg = sOg; p.addend = addend;
-    p.order = 0; p.reduce_cols = 0;
-    p.gen_x = x; p.gen_ldx = ldx; p.gen_sg = sxg; p.gen_K = K; p.gen_scale = a_scale; p.gen_zp = a_zp; p.gen_sn = a_pg;
-    p.gen_qmax = (float)((1 << n_bits) - 1);
-    const bool rowmap = a_rows || o_rows;
-    p.a_rows = a_rows; p.o_rows = o_rows; p.row_period = (int)(rowmap ? period : 1);
     // 128-row tiles while they give every CU one, else 64-row tiles (attn.proj of deit_small: 50 x 2 -> 99 x 2 tiles)
     int tmv = pick_tm_out(M, (int64_t)cdiv(N, BN2) * G);
     if (tmv > 2) tmv = 2;
-    p.MT = cdiv(M, 64 * tmv); p.NT = cdiv(N, BN2); p.Npad = p.NT * BN2;
+    Layout L{};
+    L.MT = cdiv(M, 64 * tmv); L.NT = cdiv(N, BN2); L.Npad = L.NT * BN2;
+    GemmArgs p = gemm_args(c, L);                                     // (c.k_valid = K: the valid bytes of the int8 rows)
+    p.KbA = Kp; p.timeline = nullptr;                                 // the generated rows are as long as B's; never timed in the lab
+    p.gen_x = x; p.gen_ldx = ldx; p.gen_sg = g.sxg; p.gen_K = K; p.gen_scale = a_scale; p.gen_zp = a_zp; p.gen_sn = g.a_pg;
+    p.gen_qmax = (float)((1 << n_bits) - 1);
+    const bool rowmap = g.a_rows || g.o_rows;
+    p.a_rows = g.a_rows; p.o_rows = g.o_rows; p.row_period = (int)(rowmap ? g.period : 1);
     const int64_t tiles = (int64_t)p.MT * p.NT * G;
     ADALOG_ARG_CHECK(tiles < ((int64_t)1 << 31), "gemm_out_gen: grid too large");
     const size_t shm = (size_t)(64 * tmv + BN2) * BK2 + (512 + 256) * sizeof(float);
-#define LAUNCH_GENA(TMV, ADDV, MAPV, LABEL)                                                                       \
-    do {                                                                                                          \
-        static unsigned long long attr_dev = 0;                                                                   \
-        { hipError_t ea__ = adalog_max_lds(reinterpret_cast<const void*>(&k_gemm_cand<0, TMV, true, true, ADDV, MAPV>), (int)(72 * 1024), &attr_dev); \
-          if (ea__ != hipSuccess) { adalog_set_error("hipFuncSetAttribute", ea__); return (int)ea__; } }         \
-        adalog_note_kernel(LABEL);                                                                                \
-        hipLaunchKernelGGL((k_gemm_cand<0, TMV, true, true, ADDV, MAPV>), dim3((unsigned)tiles), dim3(512), shm, (hipStream_t)stream, p); \
-    } while (0)
-    if (rowmap) {
-        if (addend) { if (tmv == 2) LAUNCH_GENA(2, true, true, "k_gemm_cand_gen_rows"); else LAUNCH_GENA(1, true, true, "k_gemm_cand_gen_rows"); }
-        else { if (tmv == 2) LAUNCH_GENA(2, false, true, "k_gemm_cand_gen_rows"); else LAUNCH_GENA(1, false, true, "k_gemm_cand_gen_rows"); }
-    } else if (addend) { if (tmv == 2) LAUNCH_GENA(2, true, false, "k_gemm_cand_gen_ex"); else LAUNCH_GENA(1, true, false, "k_gemm_cand_gen_ex"); }
-    else { if (tmv == 2) LAUNCH_GENA(2, false, false, "k_gemm_cand_gen"); else LAUNCH_GENA(1, false, false, "k_gemm_cand_gen"); }
-#undef LAUNCH_GENA
+    const char* label = rowmap ? "k_gemm_cand_gen_rows" : addend ? "k_gemm_cand_gen_ex" : "k_gemm_cand_gen";
+    if (const int e = adalog_dispatch<true, false>(rowmap, [&](auto map) {
+            return adalog_dispatch<true, false>(addend != nullptr, [&](auto add) {
+                return adalog_dispatch<2, 1>(tmv, [&](auto tm) {
+                    return adalog_launch<k_gemm_cand<0, decltype(tm)::value, true, true, decltype(add)::value, decltype(map)::value>>(
+                        label, 72 * 1024, (unsigned)tiles, 512, shm, (hipStream_t)c.stream, p);
+                });
+            });
+        })) return e;
     ADALOG_LAUNCH_CHECK("adalog_gemm_out_gen");
     return 0;
 }
@@ -758,8 +736,13 @@ extern "C" int adalog_gemm_out_gen_ex(const float* x, int64_t ldx, int64_t sxg, 
                                       int n_bits, const void* B, int64_t sBg, int M, int N, int64_t Kp, int G, int gmod, const float* sa,
                                       int64_t sa_g, float sa_mul, const float* sb, int64_t sb_g, int64_t sb_n, const float* bias,
                                       int64_t bi_g, int64_t bi_n, const float* addend, float* out, int64_t ldo, int64_t sOg, void* stream) {
-    return gemm_out_gen_impl(x, ldx, sxg, K, a_scale, a_zp, a_pg, n_bits, B, sBg, M, N, Kp, G, gmod, sa, sa_g, sa_mul, sb, sb_g, sb_n, bias,
-                             bi_g, bi_n, addend, out, ldo, sOg, nullptr, nullptr, 1, stream);
+    const MmOutEx ox{addend, 0, 0};
+    const MmGenA g{x, ldx, sxg, K, a_scale, a_zp, a_pg, n_bits, nullptr, nullptr, 1};
+    MmCall c{};
+    c.B = B; c.sBg = sBg; c.M = M; c.N = N; c.Kp = Kp; c.k_valid = K; c.C = 1; c.G = G; c.gmod = gmod; c.ref_cs = 1; c.ref_div = 1;
+    c.sa = sa; c.sa_g = sa_g; c.sa_mul = sa_mul; c.sb = sb; c.sb_g = sb_g; c.sb_n = sb_n; c.bias = bias; c.bi_g = bi_g; c.bi_n = bi_n;
+    c.out = out; c.ldo = ldo; c.sOg = sOg; c.stream = stream; c.ox = &ox;
+    return gemm_out_gen_impl(c, g);
 }
 
 // ... with the rows of one group (G = 1) remapped in periods of L rows (the tokens of one image): A row r is read from x row
@@ -772,8 +755,13 @@ extern "C" int adalog_gemm_out_gen_rows(const float* x, int64_t ldx, int K, cons
                                         const int* a_rows, const int* o_rows, int64_t period, void* stream) {
     ADALOG_ARG_CHECK(period >= 1 && M % period == 0, "gemm_out_gen_rows: M must be a multiple of the period");
     ADALOG_ARG_CHECK(ldo >= N && (int64_t)M * ldo < ((int64_t)1 << 31), "gemm_out_gen_rows: output exceeds 32-bit addressing");
-    return gemm_out_gen_impl(x, ldx, 0, K, a_scale, a_zp, 0, n_bits, B, 0, M, N, Kp, 1, 1, sa, 0, sa_mul, sb, 0, sb_n, bias, 0, bi_n, addend,
-                             out, ldo, 0, a_rows, o_rows, period, stream);
+    const MmOutEx ox{addend, 0, 0};
+    const MmGenA g{x, ldx, 0, K, a_scale, a_zp, 0, n_bits, a_rows, o_rows, period};
+    MmCall c{};                                                       // one group, per-tensor quantiser and factors
+    c.B = B; c.M = M; c.N = N; c.Kp = Kp; c.k_valid = K; c.C = 1; c.G = 1; c.gmod = 1; c.ref_cs = 1; c.ref_div = 1;
+    c.sa = sa; c.sa_mul = sa_mul; c.sb = sb; c.sb_n = sb_n; c.bias = bias; c.bi_n = bi_n;
+    c.out = out; c.ldo = ldo; c.stream = stream; c.ox = &ox;
+    return gemm_out_gen_impl(c, g);
 }
 
 // Attention searches with uniform candidates (reference quant_layers/matmul.py:135-163 / 173-201), GEN form: scores of the
@@ -789,9 +777,12 @@ extern "C" int adalog_gemm_score_gen(int dtype, const void* A, int64_t sAg, int 
                                      void* stream) {
     ADALOG_ARG_CHECK(n_bits >= 1 && n_bits <= 8 && (dtype != 3 || n_bits <= 4), "gemm_score_gen: fp8 candidates hold <= 4-bit values");
     const MmGen gen{x, ldx, sg, zp, n_bits};
-    return gemm_score_impl(dtype, A, nullptr, 0, sAg, 0, 0, M, N, Kp, k_valid, 1, G, gmod, ref, 1, sRg, M, ref_div, sa, sa_c, sa_g, sa_mul,
-                           sb, sb_c, sb_g, 0, nullptr, 0, 0, 0, nullptr, nullptr, partial, partial_elems, nullptr, 0, 0, 0, 2, 1, stream,
-                           &gen);
+    MmCall c{};                                                       // no B, no bias; transposed reference, per-workgroup sums
+    c.dtype = dtype; c.A = A; c.sAg = sAg; c.M = M; c.N = N; c.Kp = Kp; c.k_valid = k_valid; c.C = 1; c.G = G; c.gmod = gmod;
+    c.ref = ref; c.ldr = 1; c.sRg = sRg; c.ref_cs = M; c.ref_div = ref_div;
+    c.sa = sa; c.sa_c = sa_c; c.sa_g = sa_g; c.sa_mul = sa_mul; c.sb = sb; c.sb_c = sb_c; c.sb_g = sb_g;
+    c.partial = partial; c.partial_elems = partial_elems; c.order = 2; c.reduce_cols = 1; c.stream = stream; c.gen = &gen;
+    return gemm_score_impl(c);
 }
 
 // softmax.v, log-base search of the post-softmax AdaLog quantiser (reference quant_layers/matmul.py:321-351): scores of the P = 128
@@ -830,22 +821,18 @@ extern "C" int adalog_gemm_score_avq(const void* A, int64_t sAg, int M, int N, i
     p.sa = sa; p.sa_c = sa_c; p.sa_g = sa_g; p.sa_mul = sa_mul; p.sb = sb; p.sb_c = sb_c; p.sb_g = sb_g;
     p.wg_acc = (double*)partial; p.partial = partial;
     p.gen_x = x; p.gen_ldx = ldx; p.gen_sg = sg; p.gen_K = (int)k_valid; p.gen_q = q; p.gen_lut = lut; p.gen_nb = 1 << n_bits;
-    const int64_t waves = (int64_t)L.wgs * 4;
-    int nch = (int)cdiv(3 * waves, G);
-    if (nch < cdiv(N, AVQ_ROWS)) nch = cdiv(N, AVQ_ROWS);           // <= AVQ_ROWS attention rows per item (they are staged in LDS)
-    nch = nch < 1 ? 1 : nch > N ? N : nch;
-    const int cbc = cdiv(N, nch);
-    p.slab_R = cbc; p.slab_U = cdiv(N, cbc);
+    wave_chunks(p, N, L.wgs, G, cdiv(N, AVQ_ROWS));                 // <= AVQ_ROWS attention rows per item (they are staged in LDS)
     const int nks = k_valid <= 64 ? 4 : 13;
     const size_t lut_b = (((size_t)(p.gen_nb + 1) * P + 3) & ~(size_t)3) * 4;
     const size_t rows_b = (size_t)4 * ((size_t)AVQ_ROWS * (nks * 16 + 64) + 4 * 64 * 2) * 4;
     const size_t acc_b = (size_t)gmod * 256 * 8;
     const size_t shm = lut_b + rows_b > acc_b ? lut_b + rows_b : acc_b;
     hipStream_t st = (hipStream_t)stream;
-    const int e = nks == 13 ? (M > 32 ? launch_attn<k_gemm_avq<4, 13, 2>>("k_gemm_avq<13,bf16>", 80 * 1024, L.wgs, 256, shm, st, p)
-                                      : launch_attn<k_gemm_avq<4, 13, 1>>("k_gemm_avq<13,bf16>", 80 * 1024, L.wgs, 256, shm, st, p))
-                            : (M > 32 ? launch_attn<k_gemm_avq<4, 4, 2>>("k_gemm_avq<4,bf16>", 80 * 1024, L.wgs, 256, shm, st, p)
-                                      : launch_attn<k_gemm_avq<4, 4, 1>>("k_gemm_avq<4,bf16>", 80 * 1024, L.wgs, 256, shm, st, p));
+    const unsigned wgs = (unsigned)L.wgs;
+    const int e = nks == 13 ? (M > 32 ? adalog_launch<k_gemm_avq<4, 13, 2>>("k_gemm_avq<13,bf16>", 80 * 1024, wgs, 256, shm, st, p)
+                                      : adalog_launch<k_gemm_avq<4, 13, 1>>("k_gemm_avq<13,bf16>", 80 * 1024, wgs, 256, shm, st, p))
+                            : (M > 32 ? adalog_launch<k_gemm_avq<4, 4, 2>>("k_gemm_avq<4,bf16>", 80 * 1024, wgs, 256, shm, st, p)
+                                      : adalog_launch<k_gemm_avq<4, 4, 1>>("k_gemm_avq<4,bf16>", 80 * 1024, wgs, 256, shm, st, p));
     if (e) return e;
     ADALOG_LAUNCH_CHECK("adalog_gemm_score_avq");
     return 0;
@@ -854,10 +841,9 @@ extern "C" int adalog_gemm_score_avq(const void* A, int64_t sAg, int M, int N, i
 // 1 when adalog_gemm_score_gen takes this shape (M rows of the fixed operand, N = source rows x ref_div candidate columns).
 extern "C" int adalog_gemm_score_gen_ok(int dtype, int M, int N, int G, int gmod, int ref_div, int64_t k_valid, int64_t Kp) {
     if (!(dtype == 0 || dtype == 3) || k_valid < 16 || k_valid > 64 || k_valid % 16 || ref_div < 1 || N % ref_div != 0 || G % gmod) return 0;
-    const Layout L = layout_of(M, N, 1, G, gmod, ref_div, 1, true, k_valid, Kp, true, dtype);
-    if (!(L.stream && L.acc) || L.slab) return 0;
-    if (win_ok(dtype, M, N, G, gmod, ref_div, k_valid, nullptr, nullptr, 0, M, L.wgs)) return 1;
-    return (grp_ok(dtype, M, N, G, gmod, ref_div, k_valid, nullptr, nullptr, 0, M) && grpw_on() && L.wgs * 4 >= gmod) ? 1 : 0;
+    const MmCall c = shape_call(dtype, M, N, G, gmod, ref_div, k_valid, Kp, 1);
+    const Route r = route_of(c, call_layout(c, true));
+    return (r == R_WIN || r == R_GRPW) ? 1 : 0;
 }
 
 // ---- activation-candidate scoring call with the candidate operand GENERATED inside the slab kernel (k_gemm_slab<.., GEN>)
@@ -929,26 +915,11 @@ extern "C" int adalog_score_act_gen(int dtype, const void* Wp, int M, int64_t Kp
     // both clamp alike), so 6e-7 * 2^bits bounds the difference with a factor of 2.5 to spare; never narrower than 1e-5
     const float zone = 6e-7f * (float)(1 << n_bits);
     p.gen_tie = 0.5f - (zone > 1e-5f ? zone : 1e-5f);
-    const int nk = (int)((p.Kvb + BK3 - 1) / BK3);
-    const int SBN = 32 * L.slab_nb;
-    const size_t shm = (size_t)nk * SBN * BK3 + 8 * 3 * 32 * BK3 + 8 * 192 * 4 + 8 * SBN * 4;
-    const int nref = SBN / P;
-#define LAUNCH_GEN(NREFV, DTV, NBV)                                                                               \
-    do {                                                                                                          \
-        static unsigned long long attr_dev = 0; \
-        { hipError_t ea__ = adalog_max_lds(reinterpret_cast<const void*>(&k_gemm_slab<NREFV, true, DTV, NBV, true>), (int)(160 * 1024), &attr_dev); \
-          if (ea__ != hipSuccess) { adalog_set_error("hipFuncSetAttribute", ea__); return (int)ea__; } } \
-        adalog_note_kernel(DTV == 3 ? (NBV == 8 ? "k_gemm_slab_gen<fp8>" : "k_gemm_slab128_gen<fp8>") : (NBV == 8 ? "k_gemm_slab_gen<i8>" : "k_gemm_slab128_gen<i8>")); \
-        hipLaunchKernelGGL((k_gemm_slab<NREFV, true, DTV, NBV, true>), dim3((unsigned)L.wgs), dim3(512), shm, st, p); \
-    } while (0)
-#define LAUNCH_GEN_DT(DTV)                                                                                        \
-    do {                                                                                                          \
-        if (L.slab_nb == 8) { if (nref == 1) LAUNCH_GEN(1, DTV, 8); else if (nref == 2) LAUNCH_GEN(2, DTV, 8); else LAUNCH_GEN(4, DTV, 8); } \
-        else { if (nref == 1) LAUNCH_GEN(1, DTV, 4); else LAUNCH_GEN(2, DTV, 4); }                                \
-    } while (0)
-    if (dtype == 3) LAUNCH_GEN_DT(3); else LAUNCH_GEN_DT(0);
-#undef LAUNCH_GEN_DT
-#undef LAUNCH_GEN
+    const size_t shm = slab_lds(p.Kvb, L.slab_nb);
+    if (const int e = with_slab(dtype, L.slab_nb, P, [&](auto nr, auto dt, auto nb) {
+            constexpr int NREF = decltype(nr)::value, DT = decltype(dt)::value, NB = decltype(nb)::value;
+            return adalog_launch<k_gemm_slab<NREF, true, DT, NB, true>>(slab_label(1, DT, NB), 160 * 1024, (unsigned)L.wgs, 512, shm, st, p);
+        })) return e;
     ADALOG_LAUNCH_CHECK("adalog_score_act_gen");
     // fixed-order fp64 finish of the per-workgroup accumulators [wgs][1][256] (scores == null: left to the caller, who hands the
     // accumulators -- the start of the workspace -- to adalog_finish_scores / adalog_finish_topk_next with MT = adalog_score_act_gen_wgs)
@@ -1001,30 +972,15 @@ extern "C" int adalog_score_w_gen(int dtype, const void* Xp, int T, int64_t Kp, 
     p.gen_qmax = (float)((1 << n_bits) - 1);
     const float zone = 6e-7f * (float)(1 << n_bits);
     p.gen_tie = 0.5f - (zone > 1e-5f ? zone : 1e-5f);
-    const int nk = (int)((p.Kvb + BK3 - 1) / BK3);
-    const int SBN = 32 * L.slab_nb;
-    const size_t shm = (size_t)nk * SBN * BK3 + 8 * 3 * 32 * BK3 + 8 * 192 * 4 + 8 * SBN * 4;
-    const int nref = SBN / P;
+    const size_t shm = slab_lds(p.Kvb, L.slab_nb);
     {   // a slab that is not cut has unused pieces: they must read as zero
         const hipError_t me = hipMemsetAsync(partial, 0, (size_t)L.elems * sizeof(float), st);
         if (me != hipSuccess) { adalog_set_error("adalog_score_w_gen (clear partials)", me); return (int)me; }
     }
-#define LAUNCH_WGEN(NREFV, DTV, NBV)                                                                              \
-    do {                                                                                                          \
-        static unsigned long long attr_dev = 0; \
-        { hipError_t ea__ = adalog_max_lds(reinterpret_cast<const void*>(&k_gemm_slab<NREFV, false, DTV, NBV, true>), (int)(160 * 1024), &attr_dev); \
-          if (ea__ != hipSuccess) { adalog_set_error("hipFuncSetAttribute", ea__); return (int)ea__; } } \
-        adalog_note_kernel(DTV == 3 ? (NBV == 8 ? "k_gemm_slab_wgen<fp8>" : "k_gemm_slab128_wgen<fp8>") : (NBV == 8 ? "k_gemm_slab_wgen<i8>" : "k_gemm_slab128_wgen<i8>")); \
-        hipLaunchKernelGGL((k_gemm_slab<NREFV, false, DTV, NBV, true>), dim3((unsigned)L.wgs), dim3(512), shm, st, p); \
-    } while (0)
-#define LAUNCH_WGEN_DT(DTV)                                                                                       \
-    do {                                                                                                          \
-        if (L.slab_nb == 8) { if (nref == 1) LAUNCH_WGEN(1, DTV, 8); else if (nref == 2) LAUNCH_WGEN(2, DTV, 8); else LAUNCH_WGEN(4, DTV, 8); } \
-        else { if (nref == 1) LAUNCH_WGEN(1, DTV, 4); else LAUNCH_WGEN(2, DTV, 4); }                              \
-    } while (0)
-    if (dtype == 3) LAUNCH_WGEN_DT(3); else LAUNCH_WGEN_DT(0);
-#undef LAUNCH_WGEN_DT
-#undef LAUNCH_WGEN
+    if (const int e = with_slab(dtype, L.slab_nb, P, [&](auto nr, auto dt, auto nb) {
+            constexpr int NREF = decltype(nr)::value, DT = decltype(dt)::value, NB = decltype(nb)::value;
+            return adalog_launch<k_gemm_slab<NREF, false, DT, NB, true>>(slab_label(2, DT, NB), 160 * 1024, (unsigned)L.wgs, 512, shm, st, p);
+        })) return e;
     ADALOG_LAUNCH_CHECK("adalog_score_w_gen");
     return 0;
 }

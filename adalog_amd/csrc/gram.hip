@@ -837,32 +837,17 @@ extern "C" int adalog_gram_score_w(const float* W, int O, int K, int64_t ldw, co
     const bool big = w_bits > 4;
     hipStream_t st = (hipStream_t)stream;
     const int ncu = device_cus_gram();
-#define GRAM_LAUNCH(NJV, CBV, BIGV, WPC)                                                                          \
-    do {                                                                                                          \
-        /* every workgroup slot of the chip gets blocks (a workgroup with fewer than 4 CBV blocks runs one thin pass) */ \
-        int wgs = a.nblk < WPC * ncu ? a.nblk : WPC * ncu;                                                        \
-        const size_t shm = (size_t)4 * NJV * 1024;                                                                \
-        static unsigned long long attr_dev = 0; \
-        { hipError_t ea__ = adalog_max_lds(reinterpret_cast<const void*>(&k_gram_score<NJV, CBV, BIGV, WPC>), (int)(160 * 1024), &attr_dev); \
-          if (ea__ != hipSuccess) { adalog_set_error("hipFuncSetAttribute", ea__); return (int)ea__; } } \
-        adalog_note_kernel("k_gram_score<i8>");                                                                   \
-        hipLaunchKernelGGL((k_gram_score<NJV, CBV, BIGV, WPC>), dim3((unsigned)wgs), dim3(256), shm, st, a);      \
-    } while (0)
-#define GRAM_LAUNCH_B(NJV, CBV, WPC) do { if (big) GRAM_LAUNCH(NJV, CBV, true, WPC); else GRAM_LAUNCH(NJV, CBV, false, WPC); } while (0)
-    switch (g.NJ) {
-        case 1: GRAM_LAUNCH_B(1, 4, 2); break;
-        case 2: GRAM_LAUNCH_B(2, 4, 2); break;
-        case 3: GRAM_LAUNCH_B(3, 4, 2); break;
-        case 4: GRAM_LAUNCH_B(4, 4, 2); break;
-        case 6: GRAM_LAUNCH_B(6, 4, 2); break;
-        case 8: GRAM_LAUNCH_B(8, 2, 2); break;
-        case 12: GRAM_LAUNCH_B(12, 2, 2); break;
-        case 16: GRAM_LAUNCH_B(16, 2, 2); break;
-        case 24: GRAM_LAUNCH_B(24, 2, 1); break;
-        default: ADALOG_ARG_CHECK(false, "gram_score_w: K not instantiated");
-    }
-#undef GRAM_LAUNCH_B
-#undef GRAM_LAUNCH
+    // the NJ of nj_supported (checked above); 4 blocks per pass up to NJ = 6, then 2; two workgroups per CU, one at NJ = 24
+    const int rc = adalog_dispatch<1, 2, 3, 4, 6, 8, 12, 16, 24>(g.NJ, [&](auto nj) {
+        return adalog_dispatch<true, false>(big, [&](auto bg) {
+            constexpr int NJ = decltype(nj)::value, CB = NJ >= 8 ? 2 : 4, WPC = NJ == 24 ? 1 : 2;
+            // every workgroup slot of the chip gets blocks (a workgroup with fewer than 4 CB blocks runs one thin pass)
+            const int wgs = a.nblk < WPC * ncu ? a.nblk : WPC * ncu;
+            return adalog_launch<k_gram_score<NJ, CB, decltype(bg)::value, WPC>>("k_gram_score<i8>", 160 * 1024, (unsigned)wgs, 256,
+                                                                                 (size_t)4 * NJ * 1024, st, a);
+        });
+    });
+    if (rc) return rc;
     ADALOG_LAUNCH_CHECK("adalog_gram_score_w");
     return 0;
 }

@@ -1106,7 +1106,6 @@ extern "C" int adalog_attn_split_pack_ex(const float* qkv, int B, int N, int H, 
     ADALOG_ARG_CHECK(q_bits >= 2 && q_bits <= 7 && k_bits >= 2 && k_bits <= 7 && v_bits >= 2 && v_bits <= 7, "attn_split_pack: n_bits must be in [2,7]");
     ADALOG_ARG_CHECK(((((uintptr_t)qkv) | ((uintptr_t)qp) | ((uintptr_t)kp) | ((uintptr_t)vp)) & 15) == 0, "attn_split_pack: 16-byte aligned buffers");
     const bool qmul = q_mul != 1.0f;
-    adalog_note_kernel("k_attn_split_pack");
     for (int b0 = 0; b0 < B; b0 += 65535) {
         const int nb = B - b0 < 65535 ? B - b0 : 65535;
         const int64_t gb = (int64_t)b0 * H;
@@ -1115,18 +1114,12 @@ extern "C" int adalog_attn_split_pack_ex(const float* qkv, int B, int N, int H, 
                         reinterpret_cast<int8_t*>(qp) + gb * N * 128, reinterpret_cast<int8_t*>(kp) + gb * N * 128,
                         reinterpret_cast<unsigned short*>(vp) + gb * D * Np, Np, q_mul};
         const dim3 grid((unsigned)(Np / 64), (unsigned)H, (unsigned)nb);
-#define LAUNCH_SPLIT(QDV)                                                                                              \
-        do {                                                                                                          \
-            if (qmul) hipLaunchKernelGGL((k_attn_split_pack<QDV, true>), grid, dim3(256), 0, (hipStream_t)stream, a);  \
-            else hipLaunchKernelGGL((k_attn_split_pack<QDV, false>), grid, dim3(256), 0, (hipStream_t)stream, a);      \
-        } while (0)
-        switch (D / 16) {
-            case 1: LAUNCH_SPLIT(1); break;
-            case 2: LAUNCH_SPLIT(2); break;
-            case 3: LAUNCH_SPLIT(3); break;
-            default: LAUNCH_SPLIT(4); break;
-        }
-#undef LAUNCH_SPLIT
+        adalog_dispatch<1, 2, 3, 4>(D / 16, [&](auto qd) {
+            return adalog_dispatch<true, false>(qmul, [&](auto qm) {
+                return adalog_launch<k_attn_split_pack<decltype(qd)::value, decltype(qm)::value>>("k_attn_split_pack", 0, grid, 256, 0,
+                                                                                                  (hipStream_t)stream, a);
+            });
+        });
         ADALOG_LAUNCH_CHECK("adalog_attn_split_pack");
     }
     return 0;

@@ -229,23 +229,14 @@ extern "C" int adalog_score_self_sorted_tail(const float* sorted, const double* 
     const float qmax = (float)((1 << n_bits) - 1);
     const int G = 1 << n_bits;
     hipStream_t st = (hipStream_t)stream;
-    adalog_note_kernel("k_score_sorted");
     const int64_t pairs = (int64_t)P * S;
     const int gpb = 256 / G;
     const int64_t blocks = (pairs + gpb - 1) / gpb;
     ADALOG_ARG_CHECK(blocks < ((int64_t)1 << 31), "score_self_sorted: grid too large");
-#define LAUNCH_SS(GV) hipLaunchKernelGGL((k_score_sorted<GV>), dim3((unsigned)blocks), dim3(256), 0, st, sorted, (const d2*)prefix, S, n, scale, zp, P, qmax, norm, scores)
-    switch (n_bits) {
-        case 1: LAUNCH_SS(2); break;
-        case 2: LAUNCH_SS(4); break;
-        case 3: LAUNCH_SS(8); break;
-        case 4: LAUNCH_SS(16); break;
-        case 5: LAUNCH_SS(32); break;
-        case 6: LAUNCH_SS(64); break;
-        case 7: LAUNCH_SS(128); break;
-        default: LAUNCH_SS(256); break;
-    }
-#undef LAUNCH_SS
+    adalog_dispatch<1, 2, 3, 4, 5, 6, 7, 8>(n_bits, [&](auto nb) {
+        return adalog_launch<k_score_sorted<(1 << decltype(nb)::value)>>("k_score_sorted", 0, (unsigned)blocks, 256, 0, st, sorted, (const d2*)prefix,
+                                                                          S, n, scale, zp, P, qmax, norm, scores);
+    });
     ADALOG_LAUNCH_CHECK("adalog_score_self_sorted");
     // the FPCS step's tail: a second launch.  Measured and not kept (round 6, same-box A/Bs): a ticket per segment with the last
     // arrival ranking it (126 us against 32 + 11: the last blocks serialise the columns' tails), and a workgroup of 1 024 threads per

@@ -316,6 +316,8 @@ def test_gemm_mixed_streaming_weight_search(ops, M, K, O_, bits, with_bias):
         res[name] = mod.gemm_score(mod.BF16_FP8 if name == "mixed" else mod.BF16, xp, wp, M, O_, P, 1, 1, ref.to(dev),
                                    mod.Strided(one.to(dev)), mod.Strided(sc.to(dev), c=O_, n=1), b, False, True, 1.0 / 197,
                                    sa_mul=0.5, ref_div=P, order=2, ref_transposed=True).cpu()
+        if name != "cpu":
+            assert _last_kernel() == ("k_gemm_stream<bf16xfp8>" if name == "mixed" else "k_gemm_stream<bf16>")
     assert res["mixed"].shape == (P, O_)
     assert rel_err(res["mixed"], res["bf16"]) <= 2e-6 and rel_err(res["mixed"], res["cpu"]) <= 2e-6
 
@@ -381,10 +383,12 @@ def test_gemm_score_vs_spec(ops, dtype, shape):
         got = ops.gemm_score(dt_o, A.to(DEV), B.to(DEV), M, N, C, G, gmod, ref.to(DEV),
                              ops.Strided(sa.to(DEV), c=gmod, g=1), ops.Strided(sb.to(DEV), g=N, n=1),
                              ops.Strided(bias.to(DEV), n=1), keep_h, keep_n, 1.0 / M, sa_mul=0.5)
+        assert _last_kernel() == "k_gemm_score"                      # candidates in a grid dimension (C > 1)
         assert got.shape == want.shape
         assert rel_err(got.cpu(), want) <= 2e-6, (keep_h, keep_n, rel_err(got.cpu(), want))
     out = ops.gemm_out(dt_o, A[:1].to(DEV), B.to(DEV), M, N, G, gmod, ops.Strided(sa[:1].to(DEV), g=1),
                        ops.Strided(sb.to(DEV), g=N, n=1), ops.Strided(bias.to(DEV), n=1), sa_mul=0.5)
+    assert _last_kernel() == "k_gemm_cand"                           # the store form
     want = CB.gemm_out(dt_c, A[:1], B, M, N, G, gmod, CB.Strided(sa[:1], g=1), CB.Strided(sb, g=N, n=1),
                        CB.Strided(bias, n=1), sa_mul=0.5)
     assert rel_err(out.cpu(), want) <= 2e-6
@@ -721,6 +725,7 @@ def test_gemm_score_candidates_in_columns(ops, dtype):
         got = ops.gemm_score(dt_o, xa, wb, M, O_, P, 1, 1, ref.to(DEV), ops.Strided(xs.to(DEV)),
                              ops.Strided(sc.to(DEV), c=O_, n=1), ops.Strided(bias.to(DEV), n=1), False, True, 1.0 / 7,
                              ref_div=P, order=order)
+        assert _last_kernel() == "k_gemm_cand_glds"                  # C = 1, reference not transposed: not a streaming shape
         assert got.shape == (P, O_) and rel_err(got.cpu(), want) <= 2e-6, order
     # candidate-batched layout gives the same numbers
     wb2 = ops.pack_uniform(W.to(DEV), sc.to(DEV), zp.to(DEV), P, O_, 1, 0, 1, bits, dt_o)
@@ -728,6 +733,7 @@ def test_gemm_score_candidates_in_columns(ops, dtype):
         got2 = ops.gemm_score(dt_o, xa, wb2, M, O_, P, 1, 1, ref.to(DEV), ops.Strided(xs.to(DEV)),
                               ops.Strided(sc.to(DEV), c=O_, n=1), ops.Strided(bias.to(DEV), n=1), False, True, 1.0 / 7,
                               order=order)
+        assert _last_kernel() == "k_gemm_score"
         assert rel_err(got2.cpu(), want) <= 2e-6
 
 
@@ -869,6 +875,7 @@ def test_gemm_stream_kernel_variants(ops, dtype, P):
                                          ops.Strided(sb.to(DEV), c=Ncols, n=1), ob, False, True, 0.01, ref_div=P, order=2,
                                          ref_transposed=True, row_scale=rs.to(DEV) if rows else None,
                                          row_bias=rb.to(DEV) if rows else None)
+                    assert _last_kernel() == "k_gemm_stream<%s>" % dtype         # narrow and wide form alike
                     assert got.shape == want.shape
                     assert rel_err(got.cpu(), want) <= 3e-6, (M, Ncols, K, bias_kind, rows, kv, rel_err(got.cpu(), want))
 
@@ -1835,8 +1842,10 @@ def test_gemm_out_gen_equals_pack_then_gemm(ops, bits, M, N, K):
     sa_, sb_, bi_ = ops.Strided(scale.to(DEV)), ops.Strided(sb.to(DEV), n=1), ops.Strided(bias.to(DEV), n=1)
     assert ops.gemm_out_gen_ok(xd, Kp, bits)
     got = ops.gemm_out_gen(xd, scale.to(DEV), zp.to(DEV), bits, wd, N, 1, sa_, sb_, bi_)
+    assert _last_kernel() == "k_gemm_cand_gen"
     xp = ops.pack_uniform(xd, scale.to(DEV), zp.to(DEV), 1, 0, 1, 0, 0, bits, ops.I8)
     want = ops.gemm_out(ops.I8, xp, wd, M, N, 1, 1, sa_, sb_, bi_)
+    assert _last_kernel() == "k_gemm_cand"
     assert got.shape == want.shape == (1, M, N)
     assert torch.equal(got, want), (got - want).abs().max().item()
     # a row-strided view (the class token x[:, 0] in front of the head) is read in place
@@ -1847,6 +1856,7 @@ def test_gemm_out_gen_equals_pack_then_gemm(ops, bits, M, N, K):
     # the residual stream added in the epilogue (adalog_gemm_out_gen_ex): bit for bit the separate add
     add = torch.randn(1, M, N, generator=gen).to(DEV)
     assert torch.equal(ops.gemm_out_gen(xd, scale.to(DEV), zp.to(DEV), bits, wd, N, 1, sa_, sb_, bi_, addend=add), want + add)
+    assert _last_kernel() == "k_gemm_cand_gen_ex"
     # the packed codes are the oracle's: round-half-even of x / scale + zp, clamped, minus the zero point
     _, q = O.uniform_fake_quant(x[0], scale, zp, bits)
     assert torch.equal(xp[0, 0, :, :K].cpu().float(), q - zp)
@@ -1937,13 +1947,16 @@ def test_gemm_out_addend_and_heads_last(ops, dt):
     sa = (torch.rand(H, generator=gen) * 0.1 + 0.01).to(DEV); sb = (torch.rand(H, generator=gen) * 0.1 + 0.01).to(DEV)
     Ad, Bd = A.to(DEV), Bm.to(DEV)
     plain = ops.gemm_out(dto, Ad, Bd, M, N, B * H, H, ops.Strided(sa, g=1), ops.Strided(sb, g=1), None)
+    assert _last_kernel() == "k_gemm_cand"
     hl = ops.gemm_out(dto, Ad, Bd, M, N, B * H, H, ops.Strided(sa, g=1), ops.Strided(sb, g=1), None, heads_last=H)
+    assert _last_kernel() == "k_gemm_cand_ex"
     assert hl.shape == (B, M, H, N)
     assert torch.equal(hl, plain.view(B, H, M, N).permute(0, 2, 1, 3).contiguous())
     add = torch.randn(B * H, M, N, generator=gen).to(DEV)
     bias = torch.randn(N, generator=gen).to(DEV)
     base = ops.gemm_out(dto, Ad, Bd, M, N, B * H, H, ops.Strided(sa, g=1), ops.Strided(sb, g=1), ops.Strided(bias, n=1))
     got = ops.gemm_out(dto, Ad, Bd, M, N, B * H, H, ops.Strided(sa, g=1), ops.Strided(sb, g=1), ops.Strided(bias, n=1), addend=add)
+    assert _last_kernel() == "k_gemm_cand_ex"
     assert torch.equal(got, base + add)
 
 

@@ -142,6 +142,7 @@ def test_gemm_out_gen_rows_equals_gather_and_scatter(ops, L, images, K, N, bits)
     """adalog_gemm_out_gen_rows against gemm_out_gen on the gathered rows x[P] (qkv behind roll + window partition) and against the
     scattered store + separate add (proj in front of window reverse + roll back + the residual add), bit for bit; M not a multiple of
     the row tile, several images per launch, both row-tile forms (64-row tiles for small M, 128-row tiles at 34 300 rows)."""
+    from adalog_amd import _lib
     from adalog_amd.utils import models as M
     side = int(round(L ** 0.5))
     ws = 7 if side % 7 == 0 else 4
@@ -164,11 +165,13 @@ def test_gemm_out_gen_rows_equals_gather_and_scatter(ops, L, images, K, N, bits)
     sa_, sb_, bi_ = ops.Strided(sc), ops.Strided(sb.to(DEV), n=1), ops.Strided(bias.to(DEV), n=1)
     plain = ops.gemm_out_gen(xd[src].unsqueeze(0), sc, z, bits, wd, N, 1, sa_, sb_, bi_)[0]
     got = ops.gemm_out_gen_rows(xd, sc, z, bits, wd, N, sa_, sb_, bi_, a_rows=rows, period=L)
+    assert _lib.load().adalog_last_kernel().decode() == "k_gemm_cand_gen_rows"
     assert torch.equal(got, plain), (got - plain).abs().max().item()
     y = ops.gemm_out_gen(xd.unsqueeze(0), sc, z, bits, wd, N, 1, sa_, sb_, bi_)[0]
     want = torch.empty_like(y)
     want[src] = y + add[src]
     got = ops.gemm_out_gen_rows(xd, sc, z, bits, wd, N, sa_, sb_, bi_, o_rows=rows, period=L, addend=add)
+    assert _lib.load().adalog_last_kernel().decode() == "k_gemm_cand_gen_rows"
     assert torch.equal(got, want), (got - want).abs().max().item()
     want2 = torch.empty_like(y)
     want2[src] = plain + add[src]                                      # both maps at once (the identity of the Swin block's two GEMMs)
