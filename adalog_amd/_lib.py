@@ -143,6 +143,9 @@ SIGNATURES = {
     "adalog_shift_fold": (i32, [p, p, p, p, i32, i32, p, p]),
     "adalog_minmax_rows": (i32, [p, i32, i32, i32, p, p, p]),
     "adalog_absminmax_cols": (i32, [p, i64, i32, i32, p, p, p]),
+    "adalog_packed_row_words": (i64, [i64, i32]),
+    "adalog_pack_codes_f32": (i32, [p, i64, i64, i64, p, p, i32, i32, p, p]),
+    "adalog_unpack_codes": (i32, [p, i64, i64, p, p, i32, i32, i32, p, i64, p]),
 }
 
 class FpcsTail(C.Structure):

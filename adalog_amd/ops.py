@@ -210,6 +210,66 @@ def pack_split3(x3, k_align: int = 128):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ packed weight codes
+def packed_row_words(K: int, n_bits: int) -> int:
+    """32-bit words of one packed row of K codes of ``n_bits`` bits: n_bits * ceil(K / 32) (format adalog-packed-v1)."""
+    n = _lib.load().adalog_packed_row_words(int(K), int(n_bits))
+    if n < 0:
+        raise ValueError(f"packed_row_words: K = {K} must be >= 1 and n_bits = {n_bits} in [2, 8]")
+    return int(n)
+
+
+def _codes_params(scale, zero_point, R: int):
+    scale, zero_point = _f32c(scale, "scale").reshape(-1), _f32c(zero_point, "zero_point").reshape(-1)
+    if scale.numel() != zero_point.numel() or scale.numel() not in (1, R):
+        raise ValueError(f"scale / zero_point must both have 1 or {R} (one per row) elements, got {scale.numel()} / {zero_point.numel()}")
+    return scale, zero_point, int(scale.numel() == R and R > 1)
+
+
+def pack_codes(w2, scale, zero_point, n_bits: int):
+    """fp32 [R, K] -> int32 [R, n_bits * ceil(K / 32)]: the codes clamp(rne(w / s) + rne(z), 0, 2^n_bits - 1) of uniform_fake_quant,
+    32 per group of n_bits words (include/adalog_hip.h).  scale / zero_point: one element, or one per row."""
+    if w2.dim() != 2:
+        raise ValueError("pack_codes: the weight must be viewed as [rows, cols]")
+    w2 = _f32c(w2, "w2")
+    R, K = w2.shape
+    scale, zero_point, per_row = _codes_params(scale, zero_point, R)
+    out = torch.empty((R, packed_row_words(K, n_bits)), dtype=torch.int32, device=w2.device)
+    rc = _lib.load().adalog_pack_codes_f32(w2.data_ptr(), R, K, K, _ptr(scale), _ptr(zero_point), per_row, int(n_bits), out.data_ptr(),
+                                          _stream())
+    _lib.check(rc, "adalog_pack_codes_f32")
+    return out
+
+
+def unpack_codes(packed, K: int, scale, zero_point, n_bits: int, dtype: int = F32, Kp: Optional[int] = None, out=None):
+    """int32 [R, n_bits * ceil(K / 32)] -> F32: the fake-quantised weight (q - rne(z)) * s, [R, K]; I8 / BF16: the operand image
+    q - rne(z) that pack_uniform writes for the same weight, [R, Kp] with zero padding (Kp defaults to pad_k(K, dtype)).
+    ``out`` (F32 only): a contiguous fp32 [R, Kp >= K] tensor to write into; its columns beyond K are left as they are."""
+    if packed.dim() != 2 or packed.dtype != torch.int32 or not packed.is_cuda:
+        raise ValueError("unpack_codes: packed must be an int32 [rows, words] tensor on the HIP device")
+    R = packed.shape[0]
+    if packed.shape[1] != packed_row_words(K, n_bits):
+        raise ValueError(f"unpack_codes: {packed.shape[1]} words per row, expected {packed_row_words(K, n_bits)} for K = {K}, {n_bits} bits")
+    if dtype not in (I8, BF16, F32):
+        raise ValueError("unpack_codes: dtype must be I8, BF16 or F32")
+    packed = packed if packed.is_contiguous() else packed.contiguous()
+    scale, zero_point, per_row = _codes_params(scale, zero_point, R)
+    if out is not None:
+        if dtype != F32 or out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous() or out.dim() != 2 \
+                or out.shape[0] != R or out.shape[1] < K:
+            raise ValueError("unpack_codes: out must be a contiguous fp32 [rows, >= K] device tensor (F32 form only)")
+        ldo = out.shape[1]
+    else:
+        ldo = int(Kp) if Kp is not None else (K if dtype == F32 else pad_k(K, dtype))
+        if ldo < K:
+            raise ValueError(f"unpack_codes: Kp = {ldo} does not cover K = {K}")
+        out = torch.empty((R, ldo), dtype=_TORCH_DT[dtype], device=packed.device)
+    rc = _lib.load().adalog_unpack_codes(packed.data_ptr(), R, K, _ptr(scale), _ptr(zero_point), per_row, int(n_bits), dtype,
+                                        out.data_ptr(), ldo, _stream())
+    _lib.check(rc, "adalog_unpack_codes")
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ scoring GEMM
 class Strided:
     """A device fp32 parameter with (candidate, head, column) element strides for the GEMM epilogue."""

@@ -290,14 +290,18 @@ class AsymmetricallyBatchingQuantLinear(PTQSLBatchingQuantLinear):
         return be.pack_uniform(self._w2().unsqueeze(0), wq.scale.data.view(-1), wq.zero_point.data.view(-1), 1, 0, 1, 0, 1,
                                wq.n_bits, dt, want_rowsum=want_rowsum)
 
+    def _wp_cache_key(self, dt=I8, want_rowsum=False):
+        """what _pack_w_cached's image is a function of (utils/packed.py installs an image unpacked from stored codes under it)"""
+        wq = self.w_quantizer
+        return (dt, want_rowsum, wq.n_bits) + tuple((t.data_ptr(), t._version, tuple(t.shape)) for t in (self.weight, wq.scale, wq.zero_point))
+
     def _pack_w_cached(self, dt=I8, want_rowsum=False):
         """_pack_w_fixed for quant_forward (linear.py:46-51 re-quantises the weight on every call): the packed image is a pure
         function of (weight, scale, zero point), so it is kept until one of them changes (validate() runs thousands of forwards
         on unchanged weights).  The key -- storage address, in-place version and shape of each -- catches re-assigned tensors and
         autograd-visible in-place writes; writes through ``.data`` or a raw pointer do NOT bump ``_version``, so every such
         site calls invalidate_packed_weight()."""
-        wq = self.w_quantizer
-        key = (dt, want_rowsum, wq.n_bits) + tuple((t.data_ptr(), t._version, tuple(t.shape)) for t in (self.weight, wq.scale, wq.zero_point))
+        key = self._wp_cache_key(dt, want_rowsum)
         hit = self.__dict__.get("_wp_cache")
         if hit is None or hit[0] != key:
             hit = (key, self._pack_w_fixed(dt, want_rowsum))

@@ -541,6 +541,24 @@ int adalog_shift_fold(const int32_t* rowsum, const float* w_scale, const float* 
 int adalog_minmax_rows(const float* w, int rows, int I, int use_abs, float* mn, float* mx, void* stream);
 int adalog_absminmax_cols(const float* x, int64_t rows, int I, int per_channel, float* mn, float* mx, void* stream);
 
+/* ---- packed weight codes: the storage format "adalog-packed-v1" of a calibrated checkpoint (no counterpart in the reference)
+ * A weight viewed as w[R][K] is stored as 32-bit words [R][n_bits * ceil(K / 32)]: a row is cut into groups of 32 consecutive codes,
+ * a group occupies exactly n_bits words, and code i of a group (0 <= i < 32) sits at bits [i * n_bits, (i + 1) * n_bits) of the
+ * group's little-endian bit stream (stream bit j = bit j % 32 of word j / 32).  Codes beyond K are 0.  2 <= n_bits <= 8.
+ * The code is K1's bin index q = clamp(rne(w/s) + rne(zp), 0, 2L-1); scale / zero_point: [1] (per_row = 0) or [R] (per_row = 1).
+ * adalog_packed_row_words: words per packed row, n_bits * ceil(K / 32), or -1 for bad arguments (host only: no device needed).
+ * adalog_pack_codes_f32: rows of w start ldw >= K elements apart; out: [R][adalog_packed_row_words(K, n_bits)].
+ * adalog_unpack_codes: out rows start ldo >= K elements apart.
+ *   out_dtype 2: fp32 (q - rne(zp)) * s, the value K1 writes for w; columns >= K are not touched;
+ *   out_dtype 0 / 1: the int8 / bf16 operand image q - rne(zp) adalog_pack_uniform writes for w (C = G = 1, per-row parameters),
+ *   ldo its Kp, columns [K, ldo) written as zero.  The int8 image needs n_bits <= 7.
+ * All three validate their arguments before touching the device. */
+int64_t adalog_packed_row_words(int64_t K, int n_bits);
+int adalog_pack_codes_f32(const float* w, int64_t R, int64_t K, int64_t ldw, const float* scale, const float* zero_point,
+                          int per_row, int n_bits, uint32_t* out, void* stream);
+int adalog_unpack_codes(const uint32_t* in, int64_t R, int64_t K, const float* scale, const float* zero_point, int per_row,
+                        int n_bits, int out_dtype, void* out, int64_t ldo, void* stream);
+
 /* ---- K17  BRECQ / AdaRound block reconstruction: fused straight-through backward passes and AdaRound kernels
  * adalog_uniform_fq_backward: gradients of the training form y = (clamp(round_ste(x/s) + round_ste(zp), 0, 2L-1) - round_ste(zp)) * s
  *   (reference quantizers/uniform.py:29-35 + _ste.py:5-6):  gx = gy*[inside];  gscale[ch] = sum gy*((q - z) - [inside]*x/s);
