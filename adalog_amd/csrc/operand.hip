@@ -58,6 +58,104 @@ template <> __device__ __forceinline__ fp8_t cvt<fp8_t>(float v) {
 template <> __device__ __forceinline__ __hip_bfloat16 cvt<__hip_bfloat16>(float v) { return __float2bfloat16(v); }
 template <> __device__ __forceinline__ float cvt<float>(float v) { return v; }
 
+// ---- the pieces the K-contiguous packers below share
+
+// Row of the output image that (candidate c, group g, row r) writes: [c][g][r], or [g][r][c] with the candidates innermost (c_inner).
+__device__ __forceinline__ int64_t out_row(const PackArgs& a, int64_t g, int64_t r, int64_t c) {
+    return a.c_inner ? (g * a.R + r) * a.C + c : (c * a.G + g) * a.R + r;
+}
+// Elements from candidate c to candidate c + cstep of the same (g, r): what a loop over the candidates adds to its output pointer.
+__device__ __forceinline__ int64_t out_step(const PackArgs& a, int64_t cstep) {
+    return (a.c_inner ? cstep : cstep * a.G * a.R) * a.Kp;
+}
+
+// xv[0..3] = elements k0 .. k0 + 3 of a row of K elements (xp points at element k0), zeros from K on: one 16-byte load when the quad is
+// whole and aligned, otherwise only the elements below K are read.
+__device__ __forceinline__ void load_quad(const float* xp, int64_t k0, int64_t K, float* xv) {
+    if (k0 + 3 < K && ((uintptr_t)xp & 15) == 0) {
+        const float4 v = *reinterpret_cast<const float4*>(xp);
+        xv[0] = v.x; xv[1] = v.y; xv[2] = v.z; xv[3] = v.w;
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) xv[e] = (k0 + e < K) ? xp[e] : 0.0f;
+    }
+}
+
+// A uniform quantiser as the fast packers use it: {1/s, s, lo, hi} with z = rne(zero point), lo = -z, hi = qmax - z, so that
+// clamp(k + z, 0, qmax) - z == med3(k, lo, hi).
+__device__ __forceinline__ float4 uni_par(float s, float zp, float qmax) {
+    const float z = rintf(zp);
+    return make_float4(__builtin_amdgcn_rcpf(s), s, -z, qmax - z);
+}
+__device__ __forceinline__ float uni_clamp(float k, const float4& par) { return __builtin_amdgcn_fmed3f(k, par.z, par.w); }
+
+// k[e] = rne(x[e] / s), the reference's round(x / s), for N elements at the price of a multiplication each: t = x * (1/s) is within
+// 1.8e-7 * |t| of x / s, i.e. < 1e-4 wherever the clamp does not decide anyway (|t| < 555), so rne(t) is the answer unless some t lies
+// within 1e-4 of a rounding tie.  Then (rare) the IEEE quotient decides for all N: outside the tie zone both round alike.
+template <int N>
+__device__ __forceinline__ void uni_codes(const float* x, const float4& par, float* k) {
+    float dm = 0.0f;
+#pragma unroll
+    for (int e = 0; e < N; ++e) { const float t = x[e] * par.x; k[e] = rintf(t); dm = fmaxf(dm, fabsf(t - k[e])); }
+    if (__builtin_expect(dm > 0.4999f, 0)) {
+#pragma unroll
+        for (int e = 0; e < N; ++e) k[e] = rintf(x[e] / par.y);
+    }
+}
+
+// Four codes (small integers: exact in every output type) as the 32-bit word a one-byte type stores.  fp8: the hardware's e4m3
+// conversion; int8: (v + 128) saturates into a byte lane per instruction, xor 0x80 turns it into two's complement.
+template <typename T>
+__device__ __forceinline__ unsigned code_word(const float* v) {
+    static_assert(sizeof(T) == 1, "one-byte outputs");
+    if (std::is_same<T, fp8_t>::value) {
+        const int pk = __builtin_amdgcn_cvt_pk_fp8_f32(v[0], v[1], 0, false);
+        return (unsigned)__builtin_amdgcn_cvt_pk_fp8_f32(v[2], v[3], pk, true);
+    }
+    unsigned pk = 0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) pk = __builtin_amdgcn_cvt_pk_u8_f32(v[e] + 128.0f, e, pk);
+    return pk ^ 0x80808080u;
+}
+// ... and written to op in any output type: one 4-, 8- (bf16: the top halves of the fp32) or 16-byte store.
+template <typename T>
+__device__ __forceinline__ void store_quad(T* op, const float* v) {
+    if constexpr (sizeof(T) == 1) {
+        *reinterpret_cast<unsigned*>(op) = code_word<T>(v);
+    } else if constexpr (sizeof(T) == 2) {
+        const unsigned b0 = __float_as_uint(v[0]), b1 = __float_as_uint(v[1]), b2 = __float_as_uint(v[2]), b3 = __float_as_uint(v[3]);
+        *reinterpret_cast<uint2*>(op) = make_uint2((b0 >> 16) | (b1 & 0xffff0000u), (b2 >> 16) | (b3 & 0xffff0000u));
+    } else {
+        *reinterpret_cast<float4*>(op) = make_float4(v[0], v[1], v[2], v[3]);
+    }
+}
+
+// rowsum[ridx] += v over the lanes of a wave.  `wave`, the same in every lane: all 64 lanes are here and their rows are at most two
+// (lane 0's and one other) -- then each row's lanes are reduced in the wave and one lane per row adds; a lane with ridx < 0 has nothing
+// to add.  Otherwise every lane adds for itself.  (Integer sums: the order of the atomics does not show.)
+__device__ __forceinline__ void row_sum(int32_t* rowsum, int ridx, int v, bool wave) {
+    if (!wave) {
+        if (ridx >= 0 && v != 0) atomicAdd(rowsum + ridx, v);
+        return;
+    }
+    const int first = __builtin_amdgcn_readfirstlane(ridx);
+    const bool live = ridx >= 0, mine = ridx == first;
+    const int lane = threadIdx.x & 63;
+    int s1 = (live && mine) ? v : 0;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s1 += __shfl_xor(s1, o);
+    if (lane == 0 && first >= 0 && s1 != 0) atomicAdd(rowsum + first, s1);
+    const unsigned long long other = __ballot(live && !mine);
+    if (other) {                                                             // (the same in every lane)
+        int s2 = (live && !mine) ? v : 0;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s2 += __shfl_xor(s2, o);
+        const int ol = __ffsll((long long)other) - 1;
+        const int r2 = __shfl(ridx, ol);
+        if (lane == ol && s2 != 0) atomicAdd(rowsum + r2, s2);
+    }
+}
+
 template <typename T, int KIND, bool RFAST>
 __global__ __launch_bounds__(256) void k_pack(PackArgs a) {
     constexpr int EPT = Out<T>::EPT;
@@ -116,8 +214,7 @@ __global__ __launch_bounds__(256) void k_pack(PackArgs a) {
             }
             vals[e] = cvt<T>(v);
         }
-        const int64_t orow = a.c_inner ? (g * a.R + r) * a.C + c : (c * a.G + g) * a.R + r;
-        T* op = reinterpret_cast<T*>(a.out) + orow * a.Kp + ch * EPT;
+        T* op = reinterpret_cast<T*>(a.out) + out_row(a, g, r, c) * a.Kp + ch * EPT;
         *reinterpret_cast<uint4*>(op) = *reinterpret_cast<const uint4*>(vals);
         if (KIND == KIND_UNIFORM && a.rowsum) atomicAdd(a.rowsum + (c * a.G + g) * a.R + r, isum);
     }
@@ -128,49 +225,16 @@ __global__ __launch_bounds__(256) void k_pack(PackArgs a) {
 // instruction of a wave writes one contiguous 256 B / 512 B / 1 KiB run.
 template <typename T, int KIND>
 __global__ __launch_bounds__(256) void k_pack_kfast(PackArgs a) {
-    constexpr bool FP8OUT = sizeof(T) == 1 && !std::is_same<T, int8_t>::value;
+    static_assert(KIND == KIND_UNIFORM || KIND == KIND_RAW, "AdaLog operands: k_pack_adalog_fast, or k_pack");
     const int64_t nq = a.Kp >> 2;
     const int64_t total = a.G * a.R * nq;
-    // AdaLog: per-candidate value LUT  lut[c][k] = m[(k q_c) mod 37] * 2^-floor(k q_c / 37)  (bf16-exact), built once per
-    // block, so a candidate costs ~8 VALU + one LDS read per element; log2(x + shift) is taken once per element and
-    // -log2(u) = log2(s_c) - log2(x + shift) per candidate (exact path re-evaluated inside the tie zone).
-    extern __shared__ unsigned short s_lut[];
-    const float sh = (KIND == KIND_ADALOG && a.shift) ? a.shift[0] : 0.0f;
-    if (KIND == KIND_ADALOG) {
-        const int lw = a.levels2 + 1;                                        // entry [2L] = 0: masked bins
-        for (int e = threadIdx.x; e < (int)a.C * lw; e += blockDim.x) {
-            const int c = e / lw, k = e - c * lw;
-            const int kqv = k * (int)a.qv[c * a.pc];
-            const int t = kqv / ADALOG_R, j = kqv - t * ADALOG_R;
-            const float v = (k == a.levels2 || t > 100) ? 0.0f : ldexpf(a.mant[j], -t);
-            s_lut[e] = (unsigned short)(__float_as_uint(v) >> 16);          // exact: <= 8 significant bits
-        }
-        __syncthreads();
-    }
-    const float NL15 = 49.828921f;                                           // -fl32(log2(1e-15f))
     for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
         const int64_t kq = idx % nq;
         const int64_t t0 = idx / nq;
         const int64_t r = t0 % a.R, g = t0 / a.R;
         const int64_t k0 = kq << 2;
-        const float* xp = a.x + g * a.sxg + r * a.sxr + k0;
         float xv[4];
-        if (k0 + 3 < a.K && ((uintptr_t)xp & 15) == 0) {
-            const float4 v = *reinterpret_cast<const float4*>(xp);
-            xv[0] = v.x; xv[1] = v.y; xv[2] = v.z; xv[3] = v.w;
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) xv[e] = (k0 + e < a.K) ? xp[e] : 0.0f;
-        }
-        float lx[4] = {0.f, 0.f, 0.f, 0.f};
-        if (KIND == KIND_ADALOG) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                if (a.shift) xv[e] += sh;
-                lx[e] = __log2f(xv[e]);                                       // -inf for 0, NaN for negatives
-                if (a.clamp_u && !(lx[e] == lx[e])) lx[e] = -__builtin_inff(); // negatives clamp to u = 1e-15 like zeros
-            }
-        }
+        load_quad(a.x + g * a.sxg + r * a.sxr + k0, k0, a.K, xv);
         const bool full = k0 + 3 < a.K;
         const int64_t pbase = (g % a.gmod) * a.pg + r * a.pr;
         // (uniform: the next candidate's scale and zero point are fetched under the current one's arithmetic -- with per-row
@@ -178,91 +242,25 @@ __global__ __launch_bounds__(256) void k_pack_kfast(PackArgs a) {
         float s_nx = 1.0f, z_nx = 0.0f;
         if (KIND == KIND_UNIFORM && (int64_t)blockIdx.y < a.C) { s_nx = a.scale[blockIdx.y * a.pc + pbase]; z_nx = a.zp[blockIdx.y * a.pc + pbase]; }
         for (int64_t c = blockIdx.y; c < a.C; c += gridDim.y) {
-            alignas(16) T vals[4];
-            int isum = 0;
+            float v[4];
             if (KIND == KIND_RAW) {
 #pragma unroll
-                for (int e = 0; e < 4; ++e) vals[e] = cvt<T>(xv[e]);
-            } else if (KIND == KIND_UNIFORM) {
-                // per element: mul, rint, sub, cmp (tie zone -> exact divide, rare), med3 [, add, cvt_pk_u8]
-                const float s = s_nx, z = rintf(z_nx);
-                if (c + gridDim.y < a.C) { s_nx = a.scale[(c + gridDim.y) * a.pc + pbase]; z_nx = a.zp[(c + gridDim.y) * a.pc + pbase]; }
-                const float inv_s = __builtin_amdgcn_rcpf(s);
-                const float lo = -z, hi = a.qmax - z;                     // clamp(k + z, 0, qmax) - z == med3(k, -z, qmax - z)
-                float v[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float t = xv[e] * inv_s;
-                    float k = rintf(t);
-                    // tie zone: the reciprocal path is within 1.8e-7 * |t| of x/s, i.e. < 1e-4 wherever the clamp does not
-                    // decide anyway (|t| < 555), so only |frac - 0.5| < 1e-4 needs the exact quotient
-                    if (__builtin_expect(fabsf(t - k) > 0.4999f, 0)) k = rintf(xv[e] / s);
-                    v[e] = __builtin_amdgcn_fmed3f(k, lo, hi);
-                    if (!full && !(k0 + e < a.K)) v[e] = 0.0f;
-                }
-                if (a.rowsum) isum = (int)((v[0] + v[1]) + (v[2] + v[3]));    // small integers: exact in fp32
-                if (FP8OUT) {
-                    int pk = __builtin_amdgcn_cvt_pk_fp8_f32(v[0], v[1], 0, false);
-                    pk = __builtin_amdgcn_cvt_pk_fp8_f32(v[2], v[3], pk, true);
-                    *reinterpret_cast<int*>(vals) = pk;
-                } else if (sizeof(T) == 1) {
-                    // (v + 128) saturates into a byte lane per instruction; xor 0x80 turns it into two's complement
-                    unsigned pk = 0;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) pk = __builtin_amdgcn_cvt_pk_u8_f32(v[e] + 128.0f, e, pk);
-                    *reinterpret_cast<unsigned*>(vals) = pk ^ 0x80808080u;
-                } else {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) vals[e] = cvt<T>(v[e]);
-                }
+                for (int e = 0; e < 4; ++e) v[e] = xv[e];
             } else {
-                // per element: fma, med3, rint, sub, cmp (tie zone -> exact path, rare), min, cvt, LDS read
-                const float s = a.scale[c * a.pc + pbase];
-                const float qf = a.qv[c * a.pc];
-                const float rq37 = 37.0f / qf, lsr = __log2f(s) * rq37;
-                const float tmax = NL15 * rq37, lvl1 = (float)a.levels2 + 1.0f;
-                const unsigned short* lut = s_lut + c * (a.levels2 + 1);
-                unsigned short hv[4];
+                // per element: mul, rint, sub, max, med3 [, add, cvt_pk_u8]
+                const float4 par = uni_par(s_nx, z_nx, a.qmax);
+                if (c + gridDim.y < a.C) { s_nx = a.scale[(c + gridDim.y) * a.pc + pbase]; z_nx = a.zp[(c + gridDim.y) * a.pc + pbase]; }
+                float k[4];
+                uni_codes<4>(xv, par, k);
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    float t = lsr - lx[e] * rq37;                             // (log2 s - log2 x) * 37 / q
-                    if (a.clamp_u) t = __builtin_amdgcn_fmed3f(t, 0.0f, tmax); // u clamped to [1e-15, 1]  (lx = -inf for x <= 0)
-                    float kk = rintf(t);
-                    // tie zone: for t < 2L + 1 (larger bins are masked to 0 whatever they round to) the fast t is within ~1e-5
-                    // of the reference's fp32 pipeline, so |frac - 0.5| < 1e-4 is where the exact path (fp64 log2) decides.
-                    // Any lane taking it stalls its whole wave: the margin is kept as narrow as the error bound allows.
-                    if (__builtin_expect(fabsf(t - kk) > 0.4999f && t < lvl1 && t > -1.0f, 0)) {
-                        float ue = xv[e] / s;
-                        if (a.clamp_u) ue = fminf(fmaxf(ue, 1e-15f), 1.0f);
-                        kk = adalog_k(ue, qf);
-                    }
-                    // bins >= 2L are masked: LUT entry [2L] is 0.  NaN (x < 0 without the clamp) -> 0 as well.
-                    const float kc = fminf(fmaxf(kk, 0.0f), (float)a.levels2);
-                    unsigned short h = lut[(int)kc];
-                    if (!a.clamp_u && !(kk == kk)) h = 0;
-                    if (!full && !(k0 + e < a.K)) h = 0;
-                    hv[e] = h;
-                }
-                *reinterpret_cast<uint2*>(vals) = make_uint2((unsigned)hv[0] | ((unsigned)hv[1] << 16),
-                                                              (unsigned)hv[2] | ((unsigned)hv[3] << 16));
+                for (int e = 0; e < 4; ++e) v[e] = (full || k0 + e < a.K) ? uni_clamp(k[e], par) : 0.0f;
             }
-            const int64_t orow = a.c_inner ? (g * a.R + r) * a.C + c : (c * a.G + g) * a.R + r;
-            T* op = reinterpret_cast<T*>(a.out) + orow * a.Kp + k0;
-            if (sizeof(T) == 1) *reinterpret_cast<uint32_t*>(op) = *reinterpret_cast<const uint32_t*>(vals);
-            else if (sizeof(T) == 2) *reinterpret_cast<uint2*>(op) = *reinterpret_cast<const uint2*>(vals);
-            else *reinterpret_cast<uint4*>(op) = *reinterpret_cast<const uint4*>(vals);
+            store_quad<T>(reinterpret_cast<T*>(a.out) + out_row(a, g, r, c) * a.Kp + k0, v);
             if (KIND == KIND_UNIFORM && a.rowsum) {
                 // one atomic per wavefront when all 64 lanes work on the same row (the common case: Kp/4 >= 64)
-                const int64_t ridx = (c * a.G + g) * a.R + r;
-                const int64_t first = __builtin_amdgcn_readfirstlane((int)ridx);
-                if (__all((int)ridx == (int)first) && __popcll(__ballot(1)) == 64) {
-                    int v = isum;
-#pragma unroll
-                    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-                    if ((threadIdx.x & 63) == 0 && v != 0) atomicAdd(a.rowsum + ridx, v);
-                } else if (isum != 0) {
-                    atomicAdd(a.rowsum + ridx, isum);
-                }
+                const int ridx = (int)((c * a.G + g) * a.R + r);
+                const bool one_row = __all(ridx == __builtin_amdgcn_readfirstlane(ridx)) && __popcll(__ballot(1)) == 64;
+                row_sum(a.rowsum, ridx, (int)((v[0] + v[1]) + (v[2] + v[3])), one_row);   // small integers: exact in fp32
             }
         }
     }
@@ -308,14 +306,7 @@ __global__ __launch_bounds__(256) void k_pack_adalog_fast(PackArgs a) {
         const int nlive = (int)min((int64_t)4, max((int64_t)0, a.K - k0));   // data elements of this quad (rest: zero padding)
         const bool live = nlive > 0;
         if (live) {
-            const float* xp = a.x + g * a.sxg + r * a.sxr + k0;
-            if (nlive == 4 && ((uintptr_t)xp & 15) == 0) {
-                const float4 v = *reinterpret_cast<const float4*>(xp);
-                xv[0] = v.x; xv[1] = v.y; xv[2] = v.z; xv[3] = v.w;
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) if (e < nlive) xv[e] = xp[e];
-            }
+            load_quad(a.x + g * a.sxg + r * a.sxr + k0, k0, a.K, xv);
             if (a.pre == 1) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) xv[e] = gelu_erf(xv[e]);
@@ -330,9 +321,8 @@ __global__ __launch_bounds__(256) void k_pack_adalog_fast(PackArgs a) {
             if (!(lx[e] == lx[e])) lx[e] = -__builtin_inff();                // x < 0: u clamps to 1e-15 / bin masked, like x = 0
         }
         const int64_t c0 = blockIdx.y;
-        const int64_t orow = a.c_inner ? (g * a.R + r) * a.C + c0 : (c0 * a.G + g) * a.R + r;
-        const int64_t ostep = (a.c_inner ? cstep : cstep * a.G * a.R) * a.Kp;   // elements between this thread's candidates
-        __hip_bfloat16* op = reinterpret_cast<__hip_bfloat16*>(a.out) + orow * a.Kp + k0;
+        const int64_t ostep = out_step(a, cstep);
+        __hip_bfloat16* op = reinterpret_cast<__hip_bfloat16*>(a.out) + out_row(a, g, r, c0) * a.Kp + k0;
         for (int64_t c = c0; c < a.C; c += cstep, op += ostep) {
             uint2 pk = make_uint2(0u, 0u);
             if (live) {
@@ -367,7 +357,7 @@ __global__ __launch_bounds__(256) void k_pack_adalog_fast(PackArgs a) {
 }
 
 // Uniform int8 packing with per-tensor candidates (pg == pr == 0: the activation searches, 0.3-1.2 GB per call): the
-// candidate's reciprocal scale and clamp bounds come from LDS; per element  mul, rndne, sub, cmp(tie zone), med3, add,
+// candidate's reciprocal scale and clamp bounds come from LDS; per element  mul, rndne, sub, max (tie zone), add, med3,
 // cvt_pk_u8;  the output pointer advances by a constant per candidate.
 template <bool FP8>
 __global__ __launch_bounds__(256) void k_pack_uniform_i8_fast(PackArgs a) {
@@ -379,8 +369,9 @@ __global__ __launch_bounds__(256) void k_pack_uniform_i8_fast(PackArgs a) {
     const bool per_group = a.pg != 0;
     const int64_t pgo = per_group ? ((int64_t)blockIdx.z % a.gmod) * a.pg : 0;
     for (int c = threadIdx.x; c < (int)a.C; c += blockDim.x) {
-        const float s = a.scale[c * a.pc + pgo], z = rintf(a.zp[c * a.pc + pgo]);
-        s_par[c] = make_float4(__builtin_amdgcn_rcpf(s), s, vbias - z, vbias + (a.qmax - z));
+        float4 par = uni_par(a.scale[c * a.pc + pgo], a.zp[c * a.pc + pgo], a.qmax);
+        par.z += vbias; par.w += vbias;
+        s_par[c] = par;
     }
     __syncthreads();
     const int64_t nq = a.Kp >> 2;
@@ -392,39 +383,26 @@ __global__ __launch_bounds__(256) void k_pack_uniform_i8_fast(PackArgs a) {
         const int64_t t0 = idx / nq;
         const int64_t r = t0 % a.R, g = per_group ? (int64_t)blockIdx.z : t0 / a.R;
         const int64_t k0 = kq << 2;
-        float xv[4] = {0.f, 0.f, 0.f, 0.f};
+        float xv[4];
         const int nlive = (int)min((int64_t)4, max((int64_t)0, a.K - k0));
         const bool live = nlive > 0;
-        if (live) {
-            const float* xp = a.x + g * a.sxg + r * a.sxr + k0;
-            if (nlive == 4 && ((uintptr_t)xp & 15) == 0) {
-                const float4 v = *reinterpret_cast<const float4*>(xp);
-                xv[0] = v.x; xv[1] = v.y; xv[2] = v.z; xv[3] = v.w;
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) if (e < nlive) xv[e] = xp[e];
-            }
-        }
+        load_quad(a.x + g * a.sxg + r * a.sxr + k0, k0, a.K, xv);
         const int64_t c0 = blockIdx.y;
-        const int64_t orow = a.c_inner ? (g * a.R + r) * a.C + c0 : (c0 * a.G + g) * a.R + r;
-        const int64_t ostep = (a.c_inner ? cstep : cstep * a.G * a.R) * a.Kp;
-        int8_t* op = reinterpret_cast<int8_t*>(a.out) + orow * a.Kp + k0;
+        const int64_t ostep = out_step(a, cstep);
+        int8_t* op = reinterpret_cast<int8_t*>(a.out) + out_row(a, g, r, c0) * a.Kp + k0;
         for (int64_t c = c0; c < a.C; c += cstep, op += ostep) {
             unsigned pk = FP8 ? 0u : 0x80808080u;                             // (biased) zeros
             if (live) {
                 const float4 pr = s_par[c];
-                float vb[4];
+                float k[4], vb[4];
+                uni_codes<4>(xv, pr, k);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const float t = xv[e] * pr.x;
-                    float k = rintf(t);
-                    if (__builtin_expect(fabsf(t - k) > 0.4999f, 0)) k = rintf(xv[e] / pr.y);   // see k_pack_kfast
-                    vb[e] = __builtin_amdgcn_fmed3f(k + vbias, pr.z, pr.w);                     // int8: (q - z) + 128 in [1, 255]
+                    vb[e] = uni_clamp(k[e] + vbias, pr);                      // int8: (q - z) + 128 in [1, 255]
                     if (ragged && e >= nlive) vb[e] = vbias;
                 }
                 if (FP8) {
-                    int q = __builtin_amdgcn_cvt_pk_fp8_f32(vb[0], vb[1], 0, false);
-                    pk = (unsigned)__builtin_amdgcn_cvt_pk_fp8_f32(vb[2], vb[3], q, true);
+                    pk = code_word<fp8_t>(vb);
                 } else {
                     pk = 0;
 #pragma unroll
@@ -440,16 +418,19 @@ __global__ __launch_bounds__(256) void k_pack_uniform_i8_fast(PackArgs a) {
 // point) per candidate and output channel).  k_pack_kfast fetches the two parameters of every (candidate, row) from global
 // memory inside the candidate loop; even fetched one candidate ahead that is an L2 round trip per iteration, and the fc2
 // weight candidates (128 x 384 x 1536 bf16 = 151 MB) were written at 1.05 TB/s.  Here a block owns 256 consecutive k-quads
-// (at most RT rows), stages {1/s, s, -z, qmax - z} of those rows for ALL candidates in LDS once, and its loop over the
-// candidates touches global memory only to store.  The tie zone is tested once per quad, and bf16 comes from the top half of
-// the fp32 (the values are small integers: exact).
+// (at most TAB_ROWS rows), stages {1/s, s, -z, qmax - z} of those rows for ALL candidates in LDS once, and its loop over the
+// candidates touches global memory only to store.  The tie zone is tested once per thread and candidate.
+// W = 4 k per thread: any output type, ragged K.  W = 16, one-byte outputs only: one 16-byte store per lane and candidate (1 KiB per
+// wave-store; 4-byte stores wrote the fc2 weight candidates -- 75 MB of fp8 per launch -- at 1.4 TB/s); needs K % 16 == 0 == Kp % 16 (a
+// thread's 16 are all data or all padding) and 16-byte aligned rows.  Both need Kp / W >= 64: a wave then spans at most two rows, whose
+// sums are reduced per row inside the wave, and a block at most 256 / (Kp / W) + 2 <= TAB_ROWS.
 constexpr int TAB_ROWS = 6;
-template <typename T>
+template <typename T, int W>
 __global__ __launch_bounds__(256) void k_pack_uniform_tab(PackArgs a) {
-    constexpr bool FP8OUT = std::is_same<T, fp8_t>::value;
+    static_assert(W == 4 || (W == 16 && sizeof(T) == 1), "16 k per thread: one-byte outputs");
     extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
     float4* s_tab = reinterpret_cast<float4*>(s_raw);                       // [rows of this block][C]
-    const int64_t nq = a.Kp >> 2;
+    const int64_t nq = a.Kp / W;                                             // W-element pieces per row
     const int64_t total = a.G * a.R * nq;
     const int64_t q0 = (int64_t)blockIdx.x * 256;
     const int64_t row0 = q0 / nq;                                            // flattened (g, r) row
@@ -460,166 +441,45 @@ __global__ __launch_bounds__(256) void k_pack_uniform_tab(PackArgs a) {
         const int rl = e / C, c = e - rl * C;
         const int64_t gr = row0 + rl, g = gr / a.R, r = gr - g * a.R;
         const int64_t pidx = c * a.pc + (g % a.gmod) * a.pg + r * a.pr;
-        const float sc = a.scale[pidx], z = rintf(a.zp[pidx]);
-        s_tab[e] = make_float4(__builtin_amdgcn_rcpf(sc), sc, -z, a.qmax - z);
+        s_tab[e] = uni_par(a.scale[pidx], a.zp[pidx], a.qmax);
     }
     __syncthreads();
-    const int64_t idx = q0 + threadIdx.x;
-    if (idx >= total) return;
-    const int64_t gr = idx / nq, kq = idx - gr * nq;
-    const int64_t g = gr / a.R, r = gr - g * a.R;
-    const int64_t k0 = kq << 2;
-    const float* xp = a.x + g * a.sxg + r * a.sxr + k0;
-    float xv[4];
-    const bool full = k0 + 3 < a.K;
-    if (full && ((uintptr_t)xp & 15) == 0) {
-        const float4 v = *reinterpret_cast<const float4*>(xp);
-        xv[0] = v.x; xv[1] = v.y; xv[2] = v.z; xv[3] = v.w;
-    } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) xv[e] = (k0 + e < a.K) ? xp[e] : 0.0f;
-    }
-    const float4* tab = s_tab + (int)(gr - row0) * C;
-    for (int64_t c = blockIdx.y; c < a.C; c += gridDim.y) {
-        const float4 pr = tab[c];
-        float t[4], k[4], dm = 0.0f;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { t[e] = xv[e] * pr.x; k[e] = rintf(t[e]); dm = fmaxf(dm, fabsf(t[e] - k[e])); }
-        if (__builtin_expect(dm > 0.4999f, 0)) {                             // tie zone (see k_pack_kfast): the IEEE quotient decides
-#pragma unroll
-            for (int e = 0; e < 4; ++e) k[e] = rintf(xv[e] / pr.y);
-        }
-        float v[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            v[e] = __builtin_amdgcn_fmed3f(k[e], pr.z, pr.w);                // clamp(k + z, 0, qmax) - z
-            if (!full && !(k0 + e < a.K)) v[e] = 0.0f;
-        }
-        const int64_t orow = a.c_inner ? (g * a.R + r) * a.C + c : (c * a.G + g) * a.R + r;
-        T* op = reinterpret_cast<T*>(a.out) + orow * a.Kp + k0;
-        if (FP8OUT) {
-            int pk = __builtin_amdgcn_cvt_pk_fp8_f32(v[0], v[1], 0, false);
-            pk = __builtin_amdgcn_cvt_pk_fp8_f32(v[2], v[3], pk, true);
-            *reinterpret_cast<int*>(op) = pk;
-        } else if (sizeof(T) == 1) {
-            unsigned pk = 0;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) pk = __builtin_amdgcn_cvt_pk_u8_f32(v[e] + 128.0f, e, pk);
-            *reinterpret_cast<unsigned*>(op) = pk ^ 0x80808080u;
-        } else if (sizeof(T) == 2) {
-            const unsigned b0 = __float_as_uint(v[0]), b1 = __float_as_uint(v[1]), b2 = __float_as_uint(v[2]), b3 = __float_as_uint(v[3]);
-            *reinterpret_cast<uint2*>(op) = make_uint2((b0 >> 16) | (b1 & 0xffff0000u), (b2 >> 16) | (b3 & 0xffff0000u));
-        } else {
-            *reinterpret_cast<float4*>(op) = make_float4(v[0], v[1], v[2], v[3]);
-        }
-        if (a.rowsum) {
-            // one atomic per wavefront when all 64 lanes work on the same row (the common case: Kp/4 >= 64)
-            int isum = (int)((v[0] + v[1]) + (v[2] + v[3]));                 // small integers: exact in fp32
-            const int64_t ridx = (c * a.G + g) * a.R + r;
-            const int64_t first = __builtin_amdgcn_readfirstlane((int)ridx);
-            if (__all((int)ridx == (int)first) && __popcll(__ballot(1)) == 64) {
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) isum += __shfl_xor(isum, o);
-                if ((threadIdx.x & 63) == 0 && isum != 0) atomicAdd(a.rowsum + ridx, isum);
-            } else if (isum != 0) {
-                atomicAdd(a.rowsum + ridx, isum);
-            }
-        }
-    }
-}
-
-// The same packer for ONE-BYTE outputs (fp8 / int8) with 16 consecutive k per thread: one 16-byte store per lane and candidate
-// (1 KiB per wave-store; the 4-byte stores of k_pack_uniform_tab wrote the fc2 weight candidates -- 75 MB of fp8 per launch -- at
-// 1.4 TB/s).  Needs K % 16 == 0 == Kp % 16, 16-byte aligned source rows and Kp / 16 >= 64 (a wave then spans at most two rows: the
-// row sums are reduced per row inside the wave).
-template <typename T>
-__global__ __launch_bounds__(256) void k_pack_uniform_tab16(PackArgs a) {
-    constexpr bool FP8OUT = std::is_same<T, fp8_t>::value;
-    static_assert(sizeof(T) == 1, "one-byte outputs");
-    extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
-    float4* s_tab = reinterpret_cast<float4*>(s_raw);                       // [rows of this block][C]
-    const int64_t nq = a.Kp >> 4;                                            // 16-element groups per row
-    const int64_t total = a.G * a.R * nq;
-    const int64_t q0 = (int64_t)blockIdx.x * 256;
-    const int64_t row0 = q0 / nq;
-    const int64_t rowN = min((q0 + 255) / nq, a.G * a.R - 1);
-    const int nrows = (int)(rowN - row0 + 1);
-    const int C = (int)a.C;
-    for (int e = threadIdx.x; e < nrows * C; e += 256) {
-        const int rl = e / C, c = e - rl * C;
-        const int64_t gr = row0 + rl, g = gr / a.R, r = gr - g * a.R;
-        const int64_t pidx = c * a.pc + (g % a.gmod) * a.pg + r * a.pr;
-        const float sc = a.scale[pidx], z = rintf(a.zp[pidx]);
-        s_tab[e] = make_float4(__builtin_amdgcn_rcpf(sc), sc, -z, a.qmax - z);
-    }
-    __syncthreads();
+    // the last block's threads beyond the operand stay (the row sums are reduced by whole waves): no data, no store
     const int64_t idx = q0 + threadIdx.x;
     const bool live = idx < total;
     const int64_t gr = live ? idx / nq : row0, kq = live ? idx - gr * nq : 0;
     const int64_t g = gr / a.R, r = gr - g * a.R;
-    const int64_t k0 = kq << 4;
-    float xv[16];
-    const bool in_k = live && k0 < a.K;                                      // (K % 16 == 0: a group is all valid or all padding)
-    if (in_k) {
-        const float4* xp = reinterpret_cast<const float4*>(a.x + g * a.sxg + r * a.sxr + k0);
+    const int64_t k0 = kq * W, K = live ? a.K : 0;
+    const float* xp = a.x + g * a.sxg + r * a.sxr + k0;
+    const bool full = k0 + W <= K;
+    float xv[W];
+    if constexpr (W == 16) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) { const float4 v = xp[j]; xv[4 * j] = v.x; xv[4 * j + 1] = v.y; xv[4 * j + 2] = v.z; xv[4 * j + 3] = v.w; }
+        for (int j = 0; j < 4; ++j) {
+            const float4 x4 = full ? reinterpret_cast<const float4*>(xp)[j] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            xv[4 * j] = x4.x; xv[4 * j + 1] = x4.y; xv[4 * j + 2] = x4.z; xv[4 * j + 3] = x4.w;
+        }
     } else {
-#pragma unroll
-        for (int e = 0; e < 16; ++e) xv[e] = 0.0f;
+        load_quad(xp, k0, K, xv);
     }
     const float4* tab = s_tab + (int)(gr - row0) * C;
-    for (int64_t c = blockIdx.y; c < a.C; c += gridDim.y) {
-        const float4 pr = tab[c];
-        float k[16], dm = 0.0f;
+    const int64_t cstep = gridDim.y;
+    T* op = reinterpret_cast<T*>(a.out) + out_row(a, g, r, blockIdx.y) * a.Kp + k0;
+    for (int64_t c = blockIdx.y; c < a.C; c += cstep, op += out_step(a, cstep)) {
+        const float4 par = tab[c];
+        float k[W], v[W];
+        uni_codes<W>(xv, par, k);
 #pragma unroll
-        for (int e = 0; e < 16; ++e) { const float t = xv[e] * pr.x; k[e] = rintf(t); dm = fmaxf(dm, fabsf(t - k[e])); }
-        if (__builtin_expect(dm > 0.4999f, 0)) {                             // tie zone (see k_pack_kfast): the IEEE quotient decides
-#pragma unroll
-            for (int e = 0; e < 16; ++e) k[e] = rintf(xv[e] / pr.y);
-        }
-        float v[16];
-        float fs = 0.0f;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            v[e] = in_k ? __builtin_amdgcn_fmed3f(k[e], pr.z, pr.w) : 0.0f;   // clamp(k + z, 0, qmax) - z
-            fs += v[e];                                                      // small integers: exact in fp32
-        }
+        for (int e = 0; e < W; ++e) v[e] = (full || (W == 4 && k0 + e < K)) ? uni_clamp(k[e], par) : 0.0f;
         if (live) {
-            const int64_t orow = a.c_inner ? (g * a.R + r) * a.C + c : (c * a.G + g) * a.R + r;
-            T* op = reinterpret_cast<T*>(a.out) + orow * a.Kp + k0;
-            uint4 o;
-            unsigned* ow = reinterpret_cast<unsigned*>(&o);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                if (FP8OUT) {
-                    int pk = __builtin_amdgcn_cvt_pk_fp8_f32(v[4 * j], v[4 * j + 1], 0, false);
-                    pk = __builtin_amdgcn_cvt_pk_fp8_f32(v[4 * j + 2], v[4 * j + 3], pk, true);
-                    ow[j] = (unsigned)pk;
-                } else {
-                    unsigned pk = 0;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) pk = __builtin_amdgcn_cvt_pk_u8_f32(v[4 * j + e] + 128.0f, e, pk);
-                    ow[j] = pk ^ 0x80808080u;
-                }
-            }
-            *reinterpret_cast<uint4*>(op) = o;
+            if constexpr (W == 16) *reinterpret_cast<uint4*>(op) = make_uint4(code_word<T>(v), code_word<T>(v + 4), code_word<T>(v + 8), code_word<T>(v + 12));
+            else store_quad<T>(op, v);
         }
         if (a.rowsum) {
-            // a wave spans at most two rows (Kp / 16 >= 64): reduce each row's lanes, one atomic per (row, wave)
-            const int ridx = live ? (int)((c * a.G + g) * a.R + r) : -1;
-            const int first = __builtin_amdgcn_readfirstlane(ridx);
-            const bool mine = ridx == first;
-            int s1 = (live && mine) ? (int)fs : 0, s2 = (live && !mine) ? (int)fs : 0;
+            float fs = v[0];                                                 // small integers: exact in fp32
 #pragma unroll
-            for (int o2 = 32; o2 > 0; o2 >>= 1) { s1 += __shfl_xor(s1, o2); s2 += __shfl_xor(s2, o2); }
-            const unsigned long long other = __ballot(live && !mine);
-            if ((threadIdx.x & 63) == 0 && first >= 0 && s1 != 0) atomicAdd(a.rowsum + first, s1);
-            if (other) {
-                const int lane = threadIdx.x & 63, ol = __ffsll((long long)other) - 1;
-                const int r2 = __shfl(ridx, ol);
-                if (lane == ol && s2 != 0) atomicAdd(a.rowsum + r2, s2);
-            }
+            for (int e = 1; e < W; ++e) fs += v[e];
+            row_sum(a.rowsum, live ? (int)((c * a.G + g) * a.R + r) : -1, (int)fs, true);
         }
     }
 }
@@ -791,76 +651,70 @@ __global__ __launch_bounds__(256) void k_attn_split_pack(AttnSplitArgs a) {
     }
 }
 
+// Candidate groups along grid.y: doubled until `blocks` x groups reach `fill` blocks (enough to fill the chip when the source is small:
+// weights) or every candidate has a group of its own; a thread then loops over the candidates of its group.
+int64_t candidate_groups(int64_t blocks, int64_t fill, int64_t C) {
+    int64_t by = 1;
+    while (blocks * by < fill && by < C) by *= 2;
+    return by;
+}
+
 template <typename T, int KIND>
 int launch_pack(const PackArgs& a, hipStream_t st) {
     constexpr int EPT = Out<T>::EPT;
+    const bool generic = getenv("ADALOG_PACK_GENERIC") != nullptr;           // read per call: the tests switch it
     if (a.sxk == 1) {
         const int64_t total = a.G * a.R * (a.Kp >> 2);
         int64_t gx = (total + 255) / 256;
         if (gx > 16384) gx = 16384;
         if (gx < 1) gx = 1;
-        // enough candidate groups to fill the chip when the source is small (weights), all candidates per thread otherwise
-        int64_t gy = 1;
-        while (gx * gy < 2048 && gy < a.C) gy *= 2;
+        const int64_t gy = candidate_groups(gx, 2048, a.C);
         static const int use_tab = getenv("ADALOG_PACK_TAB") ? atoi(getenv("ADALOG_PACK_TAB")) : 1;
-        if (KIND == KIND_UNIFORM && a.pr != 0 && use_tab && (a.Kp >> 2) >= 64 && a.C * TAB_ROWS * sizeof(float4) <= 64 * 1024 &&
-            !getenv("ADALOG_PACK_GENERIC")) {
+        if (KIND == KIND_UNIFORM && a.pr != 0 && use_tab && (a.Kp >> 2) >= 64 && a.C * TAB_ROWS * sizeof(float4) <= 64 * 1024 && !generic) {
             // per-row parameters (weight candidates): parameters staged in LDS per block, exact grid (no grid-stride loop)
+            const size_t shm = (size_t)a.C * TAB_ROWS * sizeof(float4);
             if constexpr (sizeof(T) == 1) {
                 // one-byte outputs, long aligned rows: 16 k per thread, 16-byte stores
                 static const int use16 = getenv("ADALOG_PACK_TAB16") ? atoi(getenv("ADALOG_PACK_TAB16")) : 1;
                 if (use16 && (a.K & 15) == 0 && (a.Kp & 15) == 0 && (a.Kp >> 4) >= 64 && (a.sxr & 3) == 0 && (a.sxg & 3) == 0 &&
                     ((uintptr_t)a.x & 15) == 0 && ((uintptr_t)a.out & 15) == 0) {
-                    const int64_t t16 = a.G * a.R * (a.Kp >> 4);
-                    const int64_t bx16 = (t16 + 255) / 256;
-                    int64_t by16 = 1;
-                    while (bx16 * by16 < 1024 && by16 < a.C) by16 *= 2;
-                    // a block of 256 threads covers 256 * 16 k: at most 256 / (Kp / 16) + 2 <= TAB_ROWS rows
+                    const int64_t bx16 = (a.G * a.R * (a.Kp >> 4) + 255) / 256;
                     if (bx16 < ((int64_t)1 << 31)) {
-                        hipLaunchKernelGGL((k_pack_uniform_tab16<T>), dim3((unsigned)bx16, (unsigned)by16), dim3(256),
-                                           (size_t)a.C * TAB_ROWS * sizeof(float4), st, a);
+                        hipLaunchKernelGGL((k_pack_uniform_tab<T, 16>), dim3((unsigned)bx16, (unsigned)candidate_groups(bx16, 1024, a.C)),
+                                           dim3(256), shm, st, a);
                         return 0;
                     }
                 }
             }
             const int64_t bx = (total + 255) / 256;
-            int64_t by = 1;
-            while (bx * by < 1024 && by < a.C) by *= 2;
             if (bx < ((int64_t)1 << 31)) {
-                hipLaunchKernelGGL((k_pack_uniform_tab<T>), dim3((unsigned)bx, (unsigned)by), dim3(256),
-                                   (size_t)a.C * TAB_ROWS * sizeof(float4), st, a);
+                hipLaunchKernelGGL((k_pack_uniform_tab<T, 4>), dim3((unsigned)bx, (unsigned)candidate_groups(bx, 1024, a.C)), dim3(256), shm,
+                                   st, a);
                 return 0;
             }
         }
-        if (KIND == KIND_UNIFORM && sizeof(T) == 1 && a.pr == 0 && (a.pg == 0 || a.G <= 65535) && !a.rowsum && a.C <= 2048 &&
-            !getenv("ADALOG_PACK_GENERIC")) {
+        if (KIND == KIND_UNIFORM && sizeof(T) == 1 && a.pr == 0 && (a.pg == 0 || a.G <= 65535) && !a.rowsum && a.C <= 2048 && !generic) {
             // per-tensor parameters: one grid over all groups; per-group (per-head) parameters: grid.z = groups
             int64_t fx = gx, fy = gy, fz = 1;
             if (a.pg != 0) {
                 fz = a.G;
                 fx = (a.R * (a.Kp >> 2) + 255) / 256;
                 if (fx > 16384) fx = 16384;
-                fy = 1;
-                while (fx * fy * fz < 2048 && fy < a.C) fy *= 2;
+                fy = candidate_groups(fx * fz, 2048, a.C);
             }
-            if (std::is_same<T, int8_t>::value)
-                hipLaunchKernelGGL(k_pack_uniform_i8_fast<false>, dim3((unsigned)fx, (unsigned)fy, (unsigned)fz), dim3(256),
-                                   (size_t)a.C * sizeof(float4), st, a);
-            else
-                hipLaunchKernelGGL(k_pack_uniform_i8_fast<true>, dim3((unsigned)fx, (unsigned)fy, (unsigned)fz), dim3(256),
-                                   (size_t)a.C * sizeof(float4), st, a);
+            hipLaunchKernelGGL((k_pack_uniform_i8_fast<std::is_same<T, fp8_t>::value>), dim3((unsigned)fx, (unsigned)fy, (unsigned)fz), dim3(256),
+                               (size_t)a.C * sizeof(float4), st, a);
             return 0;
         }
-        if (KIND == KIND_ADALOG && a.pg == 0 && !getenv("ADALOG_PACK_GENERIC")) {
+        if constexpr (KIND == KIND_ADALOG) {
+            // per-tensor scale and a table that fits in LDS; anything else (and ADALOG_PACK_GENERIC): k_pack, the exact path per element
             const size_t shm2 = (size_t)a.C * (sizeof(float4) + (size_t)(a.levels2 + 2) * sizeof(unsigned short));
-            if (shm2 <= 64 * 1024) {
+            if (a.pg == 0 && !generic && shm2 <= 64 * 1024) {
                 hipLaunchKernelGGL(k_pack_adalog_fast, dim3((unsigned)gx, (unsigned)gy), dim3(256), shm2, st, a);
                 return 0;
             }
-        }
-        const size_t shm = (KIND == KIND_ADALOG) ? (size_t)a.C * (a.levels2 + 1) * sizeof(unsigned short) : 0;
-        if (KIND != KIND_ADALOG || (a.pg == 0 && shm <= 64 * 1024)) {
-            hipLaunchKernelGGL((k_pack_kfast<T, KIND>), dim3((unsigned)gx, (unsigned)gy), dim3(256), shm, st, a);
+        } else {
+            hipLaunchKernelGGL((k_pack_kfast<T, KIND>), dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, st, a);
             return 0;
         }
     }
@@ -899,6 +753,7 @@ extern "C" int adalog_pack_uniform(const float* x, int64_t G, int64_t R, int64_t
                          "pack_uniform: Kp must cover K and be a multiple of 64 bytes (128 for anything but the search kernels; fp8: of 16 bytes)");
     }
     ADALOG_ARG_CHECK(n_bits >= 2 && n_bits <= 7, "pack_uniform: n_bits must be in [2,7] (q - z must fit int8)");
+    ADALOG_ARG_CHECK(!rowsum || C * G * R <= (int64_t)0x7fffffff, "pack_uniform: the row sums are indexed with 32 bits");
     hipStream_t st = (hipStream_t)stream;
     PackArgs a{};
     a.x = x; a.G = G; a.R = R; a.K = K; a.sxg = sxg; a.sxr = sxr; a.sxk = sxk;

@@ -162,27 +162,17 @@ def pack_adalog(x3, scale, qv, C: int, pc: int, gmod: int, pg: int, n_bits: int,
     """``pre_gelu``: the operand is GELU(x3) (erf form) -- applied in the packer's loader (adalog_pack_adalog_bf16_pre)."""
     G, R, K, sg, sr, sk = _view3(x3)
     Kp = pad_k(K, BF16, k_align)
-    if pre_gelu:
+    scale, qv, mant37 = _f32c(scale, "scale"), _f32c(qv, "qv"), _f32c(mant37, "mant37")
+    shift = None if shift is None else _f32c(shift, "shift")
+    if not pre_gelu and _torch_ops.available():
+        out = _top("pack_adalog", x3, scale, qv, int(C), int(pc), int(gmod), int(pg), int(n_bits), mant37, shift, bool(clamp_u), int(Kp),
+                   bool(c_inner))
+    else:
         out = torch.empty((1, G, R * C, Kp) if c_inner else (C, G, R, Kp), dtype=torch.bfloat16, device=x3.device)
-        rc = _lib.load().adalog_pack_adalog_bf16_pre(x3.data_ptr(), G, R, K, sg, sr, sk, _ptr(_f32c(scale, "scale")),
-                                                    _ptr(_f32c(qv, "qv")), C, pc, gmod, pg, int(n_bits), _ptr(_f32c(mant37, "mant37")),
-                                                    _ptr(None if shift is None else _f32c(shift, "shift")), int(bool(clamp_u)),
-                                                    out.data_ptr(), Kp, int(bool(c_inner)), 1, _stream())
+        rc = _lib.load().adalog_pack_adalog_bf16_pre(x3.data_ptr(), G, R, K, sg, sr, sk, _ptr(scale), _ptr(qv), C, pc, gmod, pg, int(n_bits),
+                                                    _ptr(mant37), _ptr(shift), int(bool(clamp_u)), out.data_ptr(), Kp, int(bool(c_inner)),
+                                                    int(bool(pre_gelu)), _stream())
         _lib.check(rc, "adalog_pack_adalog_bf16_pre")
-        out.k_valid = K
-        return out
-    if _torch_ops.available():
-        out = _top("pack_adalog", x3, _f32c(scale, "scale"), _f32c(qv, "qv"), int(C), int(pc), int(gmod), int(pg), int(n_bits),
-                   _f32c(mant37, "mant37"), None if shift is None else _f32c(shift, "shift"), bool(clamp_u), int(Kp), bool(c_inner))
-        out.k_valid = K
-        return out
-    out = torch.empty((1, G, R * C, Kp) if c_inner else (C, G, R, Kp), dtype=torch.bfloat16, device=x3.device)
-    rc = _lib.load().adalog_pack_adalog_bf16(x3.data_ptr(), G, R, K, sg, sr, sk, _ptr(_f32c(scale, "scale")),
-                                            _ptr(_f32c(qv, "qv")), C, pc, gmod, pg, int(n_bits),
-                                            _ptr(_f32c(mant37, "mant37")),
-                                            _ptr(None if shift is None else _f32c(shift, "shift")), int(bool(clamp_u)),
-                                            out.data_ptr(), Kp, int(bool(c_inner)), _stream())
-    _lib.check(rc, "adalog_pack_adalog_bf16")
     out.k_valid = K
     return out
 

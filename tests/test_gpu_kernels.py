@@ -243,6 +243,42 @@ def test_pack_adalog_fast_vs_generic(ops, monkeypatch):
     assert (out.cpu().float() != ref.float()).sum().item() == 0
 
 
+@pytest.mark.parametrize("K,k_align,rows,dts", [
+    (1024, 128, 10, ("I8", "FP8")),                 # 16 k per thread: 64 pieces per row, every wave inside one row
+    (1088, 64, 10, ("I8", "FP8")),                  # 16 k per thread: 68 pieces per row, waves straddle two rows
+    (257, 128, 130, ("I8", "FP8", "BF16", "F32")),  # 4 k per thread (Kp / 16 < 64): ragged tail, 2-, 4- and 1-byte outputs
+])
+def test_pack_uniform_per_row_candidates(ops, monkeypatch, K, k_align, rows, dts):
+    """The LDS-table packer of the weight candidates (k_pack_uniform_tab: a (scale, zero point) per candidate and row), in its
+    16-wide one-byte form (K % 16 == 0, Kp / 16 >= 64: reached only through scoring tests at K = 1536 otherwise) and its 4-wide form,
+    against the generic kernel (bits) and the CPU specification (values), row sums included.  10 rows of 64 / 68 pieces leave the last
+    block of 256 threads partly idle; some values sit on rounding ties of a known candidate, where the exact quotient decides."""
+    gen = g(433)
+    bits, P, c_tie = 4, 128, 5
+    w = torch.randn(1, rows, K, generator=gen) * 0.1
+    sw = torch.rand(P, rows, generator=gen) * 0.02 + 0.004
+    zw = torch.randint(0, 16, (P, rows), generator=gen).float()
+    for j, k in enumerate((-3, 0, 2, 6)):                                       # (k + 0.5) * s: ties of candidate c_tie, in and out of the clamp
+        w[0, :, 17 * j + 1] = (k + 0.5) * sw[c_tie]
+    assert ((w[0] / sw[c_tie].unsqueeze(-1)).frac().abs() == 0.5).any()
+    wd, sd, zd = w.to(DEV), sw.to(DEV), zw.to(DEV)
+    for dt in dts:
+        for c_inner in (True, False):
+            args = (P, rows, 1, 0, 1, bits)
+            ref, rs_ref = CB.pack_uniform(w, sw, zw, *args, getattr(CB, dt), want_rowsum=True, c_inner=c_inner, k_align=k_align)
+            fast, rs_f = ops.pack_uniform(wd, sd, zd, *args, getattr(ops, dt), want_rowsum=True, c_inner=c_inner, k_align=k_align)
+            monkeypatch.setenv("ADALOG_PACK_GENERIC", "1")
+            slow, rs_s = ops.pack_uniform(wd, sd, zd, *args, getattr(ops, dt), want_rowsum=True, c_inner=c_inner, k_align=k_align)
+            monkeypatch.delenv("ADALOG_PACK_GENERIC", raising=False)
+            assert fast.shape == ref.shape
+            if dt == "FP8":                                                     # (values: fp8 has a -0 encoding)
+                assert torch.equal(fast.float(), slow.float()), (dt, c_inner)
+            else:
+                assert torch.equal(fast.view(torch.uint8), slow.view(torch.uint8)), (dt, c_inner)
+            assert torch.equal(fast.cpu().float(), ref.float()), (dt, c_inner)
+            assert torch.equal(rs_f, rs_s) and torch.equal(rs_f.cpu(), rs_ref), (dt, c_inner)
+
+
 def test_pack_raw(ops):
     x3 = torch.randn(1, 77, 48 * 3, generator=g(5))
     assert torch.equal(ops.pack_raw(x3.to(DEV)).cpu(), CB.pack_raw(x3))
