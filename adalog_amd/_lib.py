@@ -146,6 +146,10 @@ SIGNATURES = {
     "adalog_packed_row_words": (i64, [i64, i32]),
     "adalog_pack_codes_f32": (i32, [p, i64, i64, i64, p, p, i32, i32, p, p]),
     "adalog_unpack_codes": (i32, [p, i64, i64, p, p, i32, i32, i32, p, i64, p]),
+    "adalog_err_stats_workspace_bytes": (i64, [i64, i64, i64]),
+    "adalog_err_stats_f32": (i32, [p, p, i64, i64, i64, p, p, i64, p]),
+    "adalog_uniform_code_hist_f32": (i32, [p, i64, p, p, i64, i64, i32, p, p]),
+    "adalog_log_code_hist_f32": (i32, [p, i64, p, p, i32, p, i32, p, p]),
 }
 
 class FpcsTail(C.Structure):

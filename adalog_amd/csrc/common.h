@@ -85,9 +85,13 @@ static inline int adalog_device_cus() {
 
 // ---------------------------------------------------------------------------------------------- device math
 // asymmetric uniform bin: clamp(rne(x / s) + z, 0, qmax)       (uniform.py:29-35; z already rounded)
-__device__ __forceinline__ float uni_bin(float x, float s, float z, float qmax) {
+// ... and the code in front of the clamp, rne(x / s) + z: what the code histogram (report.hip) sorts into below / code / above
+__device__ __forceinline__ float uni_code(float x, float s, float z) {
     float xi = rintf(x / s);
-    return fminf(fmaxf(xi + z, 0.0f), qmax);
+    return xi + z;
+}
+__device__ __forceinline__ float uni_bin(float x, float s, float z, float qmax) {
+    return fminf(fmaxf(uni_code(x, s, z), 0.0f), qmax);
 }
 
 // k = rne( (-log2(u)) * 37 / q ) with u a positive float, evaluated so that it equals the fp32 pipeline
@@ -144,4 +148,16 @@ __device__ __forceinline__ float adalog_k_fast(float xs, float s, float inv_s, f
         k = rintf(t);
     }
     return k;
+}
+
+// The bin of the AdaLog / ShiftAdaLog fake-quantiser, shared by k_adalog (fakequant.hip: its ``bins`` output and its LUT index) and
+// the bin histogram (report.hip): v -> GELU(v) when ``pre`` (ATen's fp32 erf expression), + shift, k = adalog_k_fast(.., clamp_u).
+// Returns k clamped to [0, levels2 - 1]; keep = k < levels2 (otherwise the element takes the masked code 255 and the value 0).
+__device__ __forceinline__ float adalog_fq_bin(float v, float s, float inv_s, float qf, float rq37, bool has_shift, float sh, int pre,
+                                               int levels2, bool& keep) {
+    if (pre) v = (v * 0.5f) * (1.0f + erff(v * 0.70710678118654752440f));   // GELU (ATen's fp32 expression): fc2 reads fc1's output
+    const float xs = has_shift ? v + sh : v;
+    const float k = adalog_k_fast(xs, s, inv_s, qf, rq37, true);
+    keep = k < (float)levels2;
+    return fminf(fmaxf(k, 0.0f), (float)(levels2 - 1));
 }

@@ -80,17 +80,13 @@ __global__ __launch_bounds__(256) void k_adalog(const float* __restrict__ x, flo
         lut[i] = train_form ? exp2f(-1.0f * (float)i * qf / 37.0f) : ldexpf(t2[i], -(int)t1[i]);
     }
     __syncthreads();
-    const float kmax = (float)(levels2 - 1);
     // the bin through the reciprocal / v_log_f32 fast path of the operand packers (common.h adalog_k_fast: the exact IEEE sequence --
     // x / s, correctly rounded log2, / q -- decides whenever the fast value lands within 1e-3 of a rounding tie, so k is EXACTLY
     // adalog_k(clamp(xs / s), q)): the two IEEE divisions per element kept this kernel at 0.45 of the HBM rate (round 5)
     const float inv_s = 1.0f / s, rq37 = 37.0f / qf;
     auto one = [&](float v, float& out, uint8_t& b) {
-        if (pre) v = (v * 0.5f) * (1.0f + erff(v * 0.70710678118654752440f));   // GELU (ATen's fp32 expression): fc2 reads fc1's output
-        float xs = shift ? v + sh : v;
-        float k = adalog_k_fast(xs, s, inv_s, qf, rq37, true);
-        bool keep = k < (float)levels2;
-        k = fminf(fmaxf(k, 0.0f), kmax);
+        bool keep;
+        const float k = adalog_fq_bin(v, s, inv_s, qf, rq37, shift != nullptr, sh, pre, levels2, keep);   // (common.h: shared with report.hip)
         float r = lut[(int)k] * s;
         r = keep ? r : r * 0.0f;
         out = sub_shift ? r - sh : r;

@@ -127,6 +127,79 @@ def log_fake_quant(x, scale, q, table1, table2, n_bits: int, shift=None, sub_shi
     return (y, bins) if want_bins else y
 
 
+# ------------------------------------------------------------------------------------------------ report statistics (csrc/report.hip)
+def _channel_layout(n: int, n_channels: int, inner: Optional[int], what: str) -> Tuple[int, int]:
+    n_channels = int(n_channels)
+    if n_channels < 1:
+        raise ValueError(f"{what}: n_channels must be >= 1")
+    if inner is None:
+        if n % n_channels:
+            raise ValueError(f"{what}: {n} elements do not divide into {n_channels} channels")
+        inner = max(1, n // n_channels)
+    inner = int(inner)
+    if inner < 1 or n % (n_channels * inner):
+        raise ValueError(f"{what}: {n} elements are not a multiple of n_channels * inner = {n_channels} * {inner}")
+    return n_channels, inner
+
+
+def err_stats(a, b, n_channels: int = 1, inner: Optional[int] = None):
+    """-> fp64 [n_channels, 4] on the device: sum (a-b)^2, sum a^2, sum b^2, max |a-b| per channel, with ``a`` the reference and
+    channel(i) = (i // inner) % n_channels (inner defaults to numel / n_channels: one contiguous run per channel).  Squares and sums in
+    fp64, no floating-point atomics: two calls on the same input return the same bits."""
+    a, b = _f32c(a, "a"), _f32c(b, "b")
+    if a.numel() != b.numel():
+        raise ValueError(f"err_stats: a has {a.numel()} elements, b {b.numel()}")
+    n = a.numel()
+    n_channels, inner = _channel_layout(n, n_channels, inner, "err_stats")
+    lib = _lib.load()
+    out = torch.empty((n_channels, 4), dtype=torch.float64, device=a.device)
+    nbytes = lib.adalog_err_stats_workspace_bytes(n, n_channels, inner)
+    if nbytes < 0:
+        raise ValueError(f"err_stats: unsupported sizes n = {n}, n_channels = {n_channels}, inner = {inner}")
+    ws = torch.empty(max(1, nbytes // 8), dtype=torch.float64, device=a.device)
+    rc = lib.adalog_err_stats_f32(_ptr(a), _ptr(b), n, n_channels, inner, out.data_ptr(), ws.data_ptr(), ws.numel() * 8, _stream())
+    _lib.check(rc, "adalog_err_stats_f32")
+    return out
+
+
+def uniform_code_hist(x, scale, zp, n_bits: int, n_channels: int = 1, inner: Optional[int] = None):
+    """-> int64 [n_channels, 2^n_bits + 2] on the device: per channel the count of every code rne(x / s) + rne(z) in [0, 2^n_bits - 1],
+    then ``below`` and ``above`` (elements either clamp of the asymmetric uniform quantiser moves: counted there only).  No code tensor
+    is written.  Several channels need inner >= 64 (AdalogHipError otherwise)."""
+    x = _f32c(x, "x")
+    n = x.numel()
+    n_channels, inner = _channel_layout(n, n_channels, inner, "uniform_code_hist")
+    scale, zp = _f32c(scale, "scale").reshape(-1), _f32c(zp, "zero_point").reshape(-1)
+    if scale.numel() != n_channels or zp.numel() != n_channels:
+        raise ValueError(f"uniform_code_hist: {scale.numel()} scales / {zp.numel()} zero points for {n_channels} channels")
+    if not 2 <= int(n_bits) <= 8:
+        raise ValueError(f"uniform_code_hist: n_bits = {n_bits} outside [2, 8]")
+    out = torch.empty((n_channels, 2 ** int(n_bits) + 2), dtype=torch.int64, device=x.device)
+    rc = _lib.load().adalog_uniform_code_hist_f32(_ptr(x), n, _ptr(scale), _ptr(zp), n_channels, inner, int(n_bits), out.data_ptr(),
+                                                 _stream())
+    _lib.check(rc, "adalog_uniform_code_hist_f32")
+    return out
+
+
+def log_code_hist(x, scale, q, n_bits: int, shift=None, pre_gelu: bool = False):
+    """-> int64 [2^n_bits + 1] on the device: the count of every bin of the AdaLog / ShiftAdaLog quantiser (log_fake_quant's ``bins``),
+    the last entry the masked code (255 there).  ``pre_gelu``: the quantiser's input is GELU(x), applied in the kernel."""
+    x = _f32c(x, "x")
+    scale = _f32c(scale, "scale")
+    if scale.numel() != 1:
+        raise ValueError("AdaLog quantisers are per-tensor (scale must have one element)")
+    if q.dtype != torch.int64 or not q.is_cuda:
+        raise TypeError("q must be an int64 tensor on the device (the quantiser's buffer)")
+    if not 2 <= int(n_bits) <= 8:
+        raise ValueError(f"log_code_hist: n_bits = {n_bits} outside [2, 8]")
+    out = torch.empty((2 ** int(n_bits) + 1,), dtype=torch.int64, device=x.device)
+    rc = _lib.load().adalog_log_code_hist_f32(_ptr(x), x.numel(), _ptr(scale), _ptr(q), int(n_bits),
+                                             _ptr(None if shift is None else _f32c(shift, "shift")), int(bool(pre_gelu)),
+                                             out.data_ptr(), _stream())
+    _lib.check(rc, "adalog_log_code_hist_f32")
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ operand packing
 def _view3(x3: torch.Tensor):
     if x3.dim() != 3 or x3.dtype != torch.float32 or not x3.is_cuda:

@@ -559,6 +559,30 @@ int adalog_pack_codes_f32(const float* w, int64_t R, int64_t K, int64_t ldw, con
 int adalog_unpack_codes(const uint32_t* in, int64_t R, int64_t K, const float* scale, const float* zero_point, int per_row,
                         int n_bits, int out_dtype, void* out, int64_t ldo, void* stream);
 
+/* ---- measurement passes of the per-layer quantisation report (utils/report.py; no counterpart in the reference)
+ * One pass over each input, nothing of the input's size written, no host synchronisation.  Channel convention of K1:
+ * channel(i) = (i / inner) % n_channels, n a multiple of n_channels * inner, n <= 2^40 (int64 addressing throughout).
+ * err_stats: out[n_channels][4] (fp64) = sum (a-b)^2, sum a^2, sum b^2, max |a-b| per channel, a the reference.  Differences and
+ *   squares are formed in fp64 from the fp32 inputs.  No floating-point atomics: one partial per (channel, block) goes to
+ *   ``workspace`` (at least the size the query returns for the same n, n_channels, inner; 8-byte aligned) and a second small launch
+ *   adds the partials in a fixed order, so two runs on the same input give the same bits.  Layouts: one channel; several channels
+ *   with any inner >= 1 (inner = 1 walks the tensor as [rows][n_channels], a thread per channel).  n = 0: zeros.
+ * uniform_code_hist: out[n_channels][2^b + 2] (int64) = the count of every code c = rne(x/s) + rne(zp), 0 <= c <= 2^b - 1, then
+ *   ``below`` (c < 0) and ``above`` (c > 2^b - 1): clipped elements are counted there only, so a row sums to the channel's element
+ *   count.  c is the value K1 and the packers clamp (same device function).  scale / zero_point: [n_channels].  Layouts: one
+ *   channel, or several with inner >= 64 (per-row weights, per-head [N,H,S,C]); several channels with inner < 64 return -1.
+ * log_code_hist: out[2^b + 1] (int64) = the count of every bin of K2 (AdaLog / ShiftAdaLog, per-tensor scale[1], q[1] on the device,
+ *   shift[1] or NULL), the last entry the masked code (K2's 255).  The bin comes from the device function K2 takes its ``bins``
+ *   output from.  pre: the input is GELU(x), as in adalog_log_fake_quant_f32_pre.
+ * All validate their arguments before touching the device; out is zeroed by the call. */
+int64_t adalog_err_stats_workspace_bytes(int64_t n, int64_t n_channels, int64_t inner);
+int adalog_err_stats_f32(const float* a, const float* b, int64_t n, int64_t n_channels, int64_t inner, double* out,
+                         void* workspace, int64_t workspace_bytes, void* stream);
+int adalog_uniform_code_hist_f32(const float* x, int64_t n, const float* scale, const float* zero_point, int64_t n_channels,
+                                 int64_t inner, int n_bits, int64_t* out, void* stream);
+int adalog_log_code_hist_f32(const float* x, int64_t n, const float* scale, const int64_t* q, int n_bits, const float* shift,
+                             int pre, int64_t* out, void* stream);
+
 /* ---- K17  BRECQ / AdaRound block reconstruction: fused straight-through backward passes and AdaRound kernels
  * adalog_uniform_fq_backward: gradients of the training form y = (clamp(round_ste(x/s) + round_ste(zp), 0, 2L-1) - round_ste(zp)) * s
  *   (reference quantizers/uniform.py:29-35 + _ste.py:5-6):  gx = gy*[inside];  gscale[ch] = sum gy*((q - z) - [inside]*x/s);
