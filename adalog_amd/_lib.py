@@ -114,6 +114,12 @@ SIGNATURES = {
     "adalog_uniform_fq_backward_blocks": (i32, [i64, i64, i64]),
     "adalog_uniform_fq_backward": (i32, [p, p, p, i64, p, p, i64, i64, i32, i32, p, p, p, p]),
     "adalog_log_fq_backward": (i32, [p, p, p, p, i64, p, p, i32, p, i32, p, p, p]),
+    "adalog_uniform_fake_quant_drop_f32": (i32, [p, p, i64, p, p, i64, i64, i32, i32, f32, p, i32, p]),
+    "adalog_uniform_fq_backward_drop": (i32, [p, p, p, i64, p, p, i64, i64, i32, i32, p, p, p, f32, p, i32, p]),
+    "adalog_log_fake_quant_drop_f32": (i32, [p, p, i64, p, p, i32, p, i32, i32, f32, p, i32, p]),
+    "adalog_log_fq_backward_drop": (i32, [p, p, p, i64, p, p, i32, p, i32, p, p, i32, f32, p, i32, p]),
+    "adalog_qkv_split_quant_drop": (i32, [p, p, p, p, i64, i64, i32, i32, p, p, p, p, p, p, p, p]),
+    "adalog_qkv_merge_quant_backward_drop": (i32, [p, p, p, p, p, i64, i64, i32, i32, p, p, p, p, p, p, p, p, p, p]),
     "adalog_adaround": (i32, [p, p, p, p, i64, i64, p, p, i32, i32, i32, p]),
     "adalog_adaround_t": (i32, [p, p, p, p, i64, i64, p, p, i32, i32, p]),
     "adalog_alpha_step_multi": (i32, [p, p, p, p, p, p, p, p, p, p, i32, f32, p, f32, f32, f32, p, f32, p, f32, p, p, p]),

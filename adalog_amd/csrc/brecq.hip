@@ -97,17 +97,27 @@ __device__ __forceinline__ void uniform_bwd_one(float xv, float g, float s, floa
     az += inside ? 0.0f : -g * s;
 }
 
+// QDrop (common.h): a kept element takes the quantiser's gradients, a dropped one passes gy through and adds nothing to the sums
+__device__ __forceinline__ void uniform_bwd_drop_one(bool keep, float xv, float g, float s, float z, float qmin, float qmax, float& gxo,
+                                                     float& as, float& az) {
+    if (keep) uniform_bwd_one(xv, g, s, z, qmin, qmax, gxo, as, az);
+    else gxo = g;
+}
+
 // x viewed [rows][inner], channel = row % n_ch (per-tensor: rows = 1).  part_* : [rows][gridDim.x].
 // counter != null (per-tensor form only): the last block to finish reduces the partials into gscale / gzp itself.
+// DROP: the backward of k_uniform_rows<.., true> (fakequant.hip) -- the same mask, regenerated (element e = row * inner + i).
+template <bool DROP = false>
 __global__ __launch_bounds__(256) void k_uniform_bwd(const float* __restrict__ gy, const float* __restrict__ x,
                                                      float* __restrict__ gx, int64_t rows, int64_t inner,
                                                      const float* __restrict__ scale, const float* __restrict__ zp,
                                                      int64_t n_ch, float qmin, float qmax, float* __restrict__ part_s,
                                                      float* __restrict__ part_z, unsigned int* counter,
-                                                     float* __restrict__ gscale, float* __restrict__ gzp) {
+                                                     float* __restrict__ gscale, float* __restrict__ gzp, DropArgs drop = {}) {
     __shared__ float sm[4];
     __shared__ double smd[4];
-    const bool vec = (inner & 3) == 0;
+    // (DROP: tensors that are views at any element offset are taken, on the scalar path)
+    const bool vec = (inner & 3) == 0 && (!DROP || ((((uintptr_t)gy | (uintptr_t)x | (uintptr_t)gx) & 15) == 0));
     for (int64_t row = blockIdx.y; row < rows; row += gridDim.y) {
         const int64_t ch = row % n_ch;
         const float s = scale[ch];
@@ -120,6 +130,15 @@ __global__ __launch_bounds__(256) void k_uniform_bwd(const float* __restrict__ g
             for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (inner >> 2); i += (int64_t)gridDim.x * blockDim.x) {
                 const float4 xv = x4[i], g = g4[i];
                 float4 o;
+                if (DROP) {
+                    const uint4 w = drop_words(drop, ((row * inner) >> 2) + i);
+                    uniform_bwd_drop_one(drop_keep(w.x, drop.p), xv.x, g.x, s, z, qmin, qmax, o.x, as, az);
+                    uniform_bwd_drop_one(drop_keep(w.y, drop.p), xv.y, g.y, s, z, qmin, qmax, o.y, as, az);
+                    uniform_bwd_drop_one(drop_keep(w.z, drop.p), xv.z, g.z, s, z, qmin, qmax, o.z, as, az);
+                    uniform_bwd_drop_one(drop_keep(w.w, drop.p), xv.w, g.w, s, z, qmin, qmax, o.w, as, az);
+                    if (o4) o4[i] = o;
+                    continue;
+                }
                 uniform_bwd_one(xv.x, g.x, s, z, qmin, qmax, o.x, as, az);
                 uniform_bwd_one(xv.y, g.y, s, z, qmin, qmax, o.y, as, az);
                 uniform_bwd_one(xv.z, g.z, s, z, qmin, qmax, o.z, as, az);
@@ -130,7 +149,8 @@ __global__ __launch_bounds__(256) void k_uniform_bwd(const float* __restrict__ g
             for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < inner; i += (int64_t)gridDim.x * blockDim.x) {
                 const int64_t o = row * inner + i;
                 float go;
-                uniform_bwd_one(x[o], gy[o], s, z, qmin, qmax, go, as, az);
+                if (DROP) uniform_bwd_drop_one(drop_keep_at(drop, o), x[o], gy[o], s, z, qmin, qmax, go, as, az);
+                else uniform_bwd_one(x[o], gy[o], s, z, qmin, qmax, go, as, az);
                 if (gx) gx[o] = go;
             }
         }
@@ -165,12 +185,15 @@ __global__ __launch_bounds__(64) void k_param_grad_finish(const float* __restric
     if (lane == 0) out[ch] = (float)acc;
 }
 
+// DROP (QDrop, common.h): the backward of k_adalog<.., true> (fakequant.hip) -- a dropped element passes gy (times GELU' when pre)
+// through and adds nothing to the scale gradient.
+template <bool DROP = false>
 __global__ __launch_bounds__(256) void k_adalog_bwd(const float* __restrict__ gy, const float* __restrict__ x,
                                                     const float* __restrict__ y, float* __restrict__ gx, int64_t n,
                                                     const float* __restrict__ scale, const int64_t* __restrict__ q,
                                                     int levels2, const float* __restrict__ shift, int sub_shift,
                                                     float* __restrict__ part_s, unsigned int* counter,
-                                                    float* __restrict__ gscale, int pre) {
+                                                    float* __restrict__ gscale, int pre, DropArgs drop = {}) {
     __shared__ float sm[4];
     __shared__ double smd[4];
     const float s = scale[0], qf = (float)q[0];
@@ -179,7 +202,7 @@ __global__ __launch_bounds__(256) void k_adalog_bwd(const float* __restrict__ gy
     float as = 0.0f;
     // k is the forward's bin (same exact-with-fallback evaluation); the gradient factors use reciprocals: they are smooth
     // in their inputs, so a last-ulp difference from the IEEE quotients moves the gradient by ~1e-7 relative.
-    auto one = [&](float xv, float g, float& gxo) {
+    auto one = [&](float xv, float g, float& gxo, bool kept = true) {
         // pre: the quantiser saw GELU(xv); d GELU / dx = cdf + x * pdf as ATen's GeluBackward evaluates it
         float dg = 1.0f;
         if (pre) {
@@ -187,6 +210,10 @@ __global__ __launch_bounds__(256) void k_adalog_bwd(const float* __restrict__ gy
             const float pdf = expf(-0.5f * xv * xv) * 0.39894228040143267794f;
             dg = cdf + xv * pdf;
             xv = (xv * 0.5f) * (1.0f + erff(xv * 0.70710678118654752440f));
+        }
+        if (DROP && !kept) {
+            gxo = pre ? g * dg : g;
+            return;
         }
         const float xs = shift ? xv + sh : xv;
         const float ur = xs / s;
@@ -205,12 +232,19 @@ __global__ __launch_bounds__(256) void k_adalog_bwd(const float* __restrict__ gy
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
         const float4 xv = reinterpret_cast<const float4*>(x)[i], g = reinterpret_cast<const float4*>(gy)[i];
         float4 o;
-        one(xv.x, g.x, o.x); one(xv.y, g.y, o.y); one(xv.z, g.z, o.z); one(xv.w, g.w, o.w);
+        if (DROP) {
+            const uint4 w = drop_words(drop, i);
+            one(xv.x, g.x, o.x, drop_keep(w.x, drop.p)); one(xv.y, g.y, o.y, drop_keep(w.y, drop.p));
+            one(xv.z, g.z, o.z, drop_keep(w.z, drop.p)); one(xv.w, g.w, o.w, drop_keep(w.w, drop.p));
+        } else {
+            one(xv.x, g.x, o.x); one(xv.y, g.y, o.y); one(xv.z, g.z, o.z); one(xv.w, g.w, o.w);
+        }
         if (gx) reinterpret_cast<float4*>(gx)[i] = o;
     }
     for (int64_t i = (n4 << 2) + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         float o;
-        one(x[i], gy[i], o);
+        if (DROP) one(x[i], gy[i], o, drop_keep_at(drop, i));
+        else one(x[i], gy[i], o);
         if (gx) gx[i] = o;
     }
     if (part_s) {
@@ -681,9 +715,17 @@ struct QkvQuant {
     int sstride[3];                                            // 1: per head, 0: per tensor
     float qmax[3];
 };
-template <int D>
+// DROP (QDrop, common.h): part p is stream drop.stream[p] with probability drop.p[p]; the element index is the one in the part's
+// contiguous [B][H][N][D] output.
+struct QkvDrop {
+    const uint32_t* state;
+    uint32_t stream[3];
+    float p[3];
+};
+template <int D, bool DROP = false>
 __global__ __launch_bounds__(256) void k_qkv_split_quant(const float* __restrict__ src, float* __restrict__ y0, float* __restrict__ y1,
-                                                         float* __restrict__ y2, int64_t B, int64_t N, int H, QkvQuant q) {
+                                                         float* __restrict__ y2, int64_t B, int64_t N, int H, QkvQuant q,
+                                                         QkvDrop drop = {}) {
     constexpr int D4 = D / 4, RPP = 256 / D4;                  // float4 per row, rows per pass
     const int ph = blockIdx.y, pp = ph / H, h = ph % H;
     const float s = q.scale[pp][h * q.sstride[pp]], z = rintf(q.zp[pp][h * q.sstride[pp]]), qmax = q.qmax[pp];
@@ -695,15 +737,23 @@ __global__ __launch_bounds__(256) void k_qkv_split_quant(const float* __restrict
         const float4 v = reinterpret_cast<const float4*>(src + ((r * 3 + pp) * H + h) * D)[d4];
         const float q0 = fminf(fmaxf(rintf(v.x / s) + z, 0.0f), qmax), q1 = fminf(fmaxf(rintf(v.y / s) + z, 0.0f), qmax);
         const float q2 = fminf(fmaxf(rintf(v.z / s) + z, 0.0f), qmax), q3 = fminf(fmaxf(rintf(v.w / s) + z, 0.0f), qmax);
-        reinterpret_cast<float4*>(y + ((b * H + h) * N + n) * D)[d4] = make_float4((q0 - z) * s, (q1 - z) * s, (q2 - z) * s, (q3 - z) * s);
+        const int64_t yo = ((b * H + h) * N + n) * D;
+        if (DROP) {
+            const DropArgs da = {drop.state, drop.stream[pp], drop.p[pp]};
+            const uint4 w = drop_words(da, (yo >> 2) + d4);
+            reinterpret_cast<float4*>(y + yo)[d4] = make_float4(drop_keep(w.x, da.p) ? (q0 - z) * s : v.x, drop_keep(w.y, da.p) ? (q1 - z) * s : v.y,
+                                                                drop_keep(w.z, da.p) ? (q2 - z) * s : v.z, drop_keep(w.w, da.p) ? (q3 - z) * s : v.w);
+            continue;
+        }
+        reinterpret_cast<float4*>(y + yo)[d4] = make_float4((q0 - z) * s, (q1 - z) * s, (q2 - z) * s, (q3 - z) * s);
     }
 }
 
-template <int D>
+template <int D, bool DROP = false>
 __global__ __launch_bounds__(256) void k_qkv_merge_quant_bwd(const float* __restrict__ g0, const float* __restrict__ g1,
                                                              const float* __restrict__ g2, const float* __restrict__ src,
                                                              float* __restrict__ gx, int64_t B, int64_t N, int H, QkvQuant q,
-                                                             float* __restrict__ part) {
+                                                             float* __restrict__ part, QkvDrop drop = {}) {
     __shared__ float sm[4];
     constexpr int D4 = D / 4, RPP = 256 / D4;
     const int ph = blockIdx.y, pp = ph / H, h = ph % H;
@@ -716,8 +766,19 @@ __global__ __launch_bounds__(256) void k_qkv_merge_quant_bwd(const float* __rest
         const int64_t b = r / N, n = r - b * N;
         const int64_t xo = ((r * 3 + pp) * H + h) * D;
         const float4 xv = reinterpret_cast<const float4*>(src + xo)[d4];
-        const float4 g = gy ? reinterpret_cast<const float4*>(gy + ((b * H + h) * N + n) * D)[d4] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        const int64_t yo = ((b * H + h) * N + n) * D;
+        const float4 g = gy ? reinterpret_cast<const float4*>(gy + yo)[d4] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         float4 o;
+        if (DROP) {
+            const DropArgs da = {drop.state, drop.stream[pp], drop.p[pp]};
+            const uint4 w = drop_words(da, (yo >> 2) + d4);
+            uniform_bwd_drop_one(drop_keep(w.x, da.p), xv.x, g.x, s, z, 0.0f, qmax, o.x, as, az);
+            uniform_bwd_drop_one(drop_keep(w.y, da.p), xv.y, g.y, s, z, 0.0f, qmax, o.y, as, az);
+            uniform_bwd_drop_one(drop_keep(w.z, da.p), xv.z, g.z, s, z, 0.0f, qmax, o.z, as, az);
+            uniform_bwd_drop_one(drop_keep(w.w, da.p), xv.w, g.w, s, z, 0.0f, qmax, o.w, as, az);
+            if (gx) reinterpret_cast<float4*>(gx + xo)[d4] = o;
+            continue;
+        }
         uniform_bwd_one(xv.x, g.x, s, z, 0.0f, qmax, o.x, as, az);
         uniform_bwd_one(xv.y, g.y, s, z, 0.0f, qmax, o.y, as, az);
         uniform_bwd_one(xv.z, g.z, s, z, 0.0f, qmax, o.z, as, az);
@@ -928,26 +989,54 @@ extern "C" int adalog_qkv_quant_chunks(int64_t B, int64_t N, int D) { return (D 
 
 // src [B][N][3][H][D] -> y0, y1, y2 [B][H][N][D]: split and asymmetric uniform fake-quant (part p with scales[p] / zps[p]:
 // H values when per_head[p], else one).  HOST arrays of 3 pointers / flags.  D = 32 or 64.
-extern "C" int adalog_qkv_split_quant(const float* src, float* y0, float* y1, float* y2, int64_t B, int64_t N, int H, int D,
-                                      const float* const* scales, const float* const* zps, const int* per_head, const int* n_bits,
-                                      void* stream) {
+static int qkv_split_quant(const float* src, float* y0, float* y1, float* y2, int64_t B, int64_t N, int H, int D,
+                           const float* const* scales, const float* const* zps, const int* per_head, const int* n_bits,
+                           const QkvDrop* drop, void* stream) {
     if (B * N * H == 0) return 0;
     ADALOG_ARG_CHECK(src && y0 && y1 && y2 && scales && zps && per_head && n_bits && H >= 1 && (D == 32 || D == 64), "qkv_split_quant: bad arguments");
     QkvQuant q;
     ADALOG_ARG_CHECK(qkv_fill(q, scales, zps, per_head, n_bits) == 0, "qkv_split_quant: bad quantiser parameters");
     const dim3 grid((unsigned)qkv_chunks(B * N, D), (unsigned)(3 * H));
-    if (D == 64) hipLaunchKernelGGL(k_qkv_split_quant<64>, grid, dim3(256), 0, (hipStream_t)stream, src, y0, y1, y2, B, N, H, q);
-    else hipLaunchKernelGGL(k_qkv_split_quant<32>, grid, dim3(256), 0, (hipStream_t)stream, src, y0, y1, y2, B, N, H, q);
+    hipStream_t st = (hipStream_t)stream;
+    if (drop && D == 64) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_qkv_split_quant<64, true>), grid, dim3(256), 0, st, src, y0, y1, y2, B, N, H, q, *drop);
+    else if (drop) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_qkv_split_quant<32, true>), grid, dim3(256), 0, st, src, y0, y1, y2, B, N, H, q, *drop);
+    else if (D == 64) hipLaunchKernelGGL(k_qkv_split_quant<64>, grid, dim3(256), 0, st, src, y0, y1, y2, B, N, H, q);
+    else hipLaunchKernelGGL(k_qkv_split_quant<32>, grid, dim3(256), 0, st, src, y0, y1, y2, B, N, H, q);
     ADALOG_LAUNCH_CHECK("adalog_qkv_split_quant");
     return 0;
+}
+extern "C" int adalog_qkv_split_quant(const float* src, float* y0, float* y1, float* y2, int64_t B, int64_t N, int H, int D,
+                                      const float* const* scales, const float* const* zps, const int* per_head, const int* n_bits,
+                                      void* stream) {
+    return qkv_split_quant(src, y0, y1, y2, B, N, H, D, scales, zps, per_head, n_bits, nullptr, stream);
+}
+
+static int qkv_drop_fill(QkvDrop& d, const float* ps, const int32_t* drop_state, const int* drop_streams) {
+    if (!ps || !drop_state || !drop_streams) return 1;
+    d.state = reinterpret_cast<const uint32_t*>(drop_state);
+    for (int p = 0; p < 3; ++p) {
+        if (!(ps[p] >= 0.0f && ps[p] <= 1.0f)) return 1;
+        d.p[p] = ps[p]; d.stream[p] = (uint32_t)drop_streams[p];
+    }
+    return 0;
+}
+// QDrop form of adalog_qkv_split_quant: part p keeps a fake-quantised element with probability ps[p], on Philox stream
+// drop_streams[p] (HOST arrays of 3), element index = the index in the part's [B][H][N][D] output; drop_state: device int32[3]
+// {seed_lo, seed_hi, iteration}.
+extern "C" int adalog_qkv_split_quant_drop(const float* src, float* y0, float* y1, float* y2, int64_t B, int64_t N, int H, int D,
+                                           const float* const* scales, const float* const* zps, const int* per_head,
+                                           const int* n_bits, const float* ps, const int32_t* drop_state, const int* drop_streams,
+                                           void* stream) {
+    QkvDrop d;
+    ADALOG_ARG_CHECK(qkv_drop_fill(d, ps, drop_state, drop_streams) == 0, "qkv_split_quant_drop: bad drop arguments");
+    return qkv_split_quant(src, y0, y1, y2, B, N, H, D, scales, zps, per_head, n_bits, &d, stream);
 }
 
 // The gradients of adalog_qkv_split_quant: g0, g1, g2 [B][H][N][D] (null = zeros), src as above -> gx [B][N][3][H][D] (optional) and
 // gscales[p] ([H] or [1], optional per part).  workspace: 3 * H * adalog_qkv_quant_chunks(B, N, D) floats.
-extern "C" int adalog_qkv_merge_quant_backward(const float* g0, const float* g1, const float* g2, const float* src, float* gx,
-                                               int64_t B, int64_t N, int H, int D, const float* const* scales,
-                                               const float* const* zps, const int* per_head, const int* n_bits,
-                                               float* const* gscales, float* workspace, void* stream) {
+static int qkv_merge_quant_backward(const float* g0, const float* g1, const float* g2, const float* src, float* gx, int64_t B, int64_t N,
+                                    int H, int D, const float* const* scales, const float* const* zps, const int* per_head,
+                                    const int* n_bits, float* const* gscales, float* workspace, const QkvDrop* drop, void* stream) {
     if (B * N * H == 0) return 0;
     ADALOG_ARG_CHECK(src && scales && zps && per_head && n_bits && gscales && workspace && H >= 1 && (D == 32 || D == 64),
                      "qkv_merge_quant_backward: bad arguments");
@@ -956,7 +1045,11 @@ extern "C" int adalog_qkv_merge_quant_backward(const float* g0, const float* g1,
     const int nch = qkv_chunks(B * N, D);
     const dim3 grid((unsigned)nch, (unsigned)(3 * H));
     hipStream_t st = (hipStream_t)stream;
-    if (D == 64) hipLaunchKernelGGL(k_qkv_merge_quant_bwd<64>, grid, dim3(256), 0, st, g0, g1, g2, src, gx, B, N, H, q, workspace);
+    if (drop && D == 64)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_qkv_merge_quant_bwd<64, true>), grid, dim3(256), 0, st, g0, g1, g2, src, gx, B, N, H, q, workspace, *drop);
+    else if (drop)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_qkv_merge_quant_bwd<32, true>), grid, dim3(256), 0, st, g0, g1, g2, src, gx, B, N, H, q, workspace, *drop);
+    else if (D == 64) hipLaunchKernelGGL(k_qkv_merge_quant_bwd<64>, grid, dim3(256), 0, st, g0, g1, g2, src, gx, B, N, H, q, workspace);
     else hipLaunchKernelGGL(k_qkv_merge_quant_bwd<32>, grid, dim3(256), 0, st, g0, g1, g2, src, gx, B, N, H, q, workspace);
     // the scale gradients: part p per head -> H sums of nch partials; per tensor -> one sum of H * nch partials
     QkvGrads og;
@@ -964,6 +1057,23 @@ extern "C" int adalog_qkv_merge_quant_backward(const float* g0, const float* g1,
     hipLaunchKernelGGL(k_qkv_grad_finish, dim3((unsigned)(3 * H)), dim3(64), 0, st, workspace, H, nch, og);
     ADALOG_LAUNCH_CHECK("adalog_qkv_merge_quant_backward");
     return 0;
+}
+extern "C" int adalog_qkv_merge_quant_backward(const float* g0, const float* g1, const float* g2, const float* src, float* gx,
+                                               int64_t B, int64_t N, int H, int D, const float* const* scales,
+                                               const float* const* zps, const int* per_head, const int* n_bits,
+                                               float* const* gscales, float* workspace, void* stream) {
+    return qkv_merge_quant_backward(g0, g1, g2, src, gx, B, N, H, D, scales, zps, per_head, n_bits, gscales, workspace, nullptr, stream);
+}
+// The gradients of adalog_qkv_split_quant_drop (the same ps / drop_state / drop_streams regenerate its masks): a dropped element
+// passes its gradient through and adds nothing to the scale gradients.
+extern "C" int adalog_qkv_merge_quant_backward_drop(const float* g0, const float* g1, const float* g2, const float* src, float* gx,
+                                                    int64_t B, int64_t N, int H, int D, const float* const* scales,
+                                                    const float* const* zps, const int* per_head, const int* n_bits,
+                                                    float* const* gscales, float* workspace, const float* ps,
+                                                    const int32_t* drop_state, const int* drop_streams, void* stream) {
+    QkvDrop d;
+    ADALOG_ARG_CHECK(qkv_drop_fill(d, ps, drop_state, drop_streams) == 0, "qkv_merge_quant_backward_drop: bad drop arguments");
+    return qkv_merge_quant_backward(g0, g1, g2, src, gx, B, N, H, D, scales, zps, per_head, n_bits, gscales, workspace, &d, stream);
 }
 
 extern "C" int adalog_scaled_softmax(const float* x, float* y, int64_t rows, int n, float scale, void* stream) {
@@ -1009,9 +1119,9 @@ extern "C" int adalog_merge_heads(const float* p0, const float* p1, const float*
 }
 
 // gscale / gzp: [n_channels] (each optional).  workspace: 2 * rows * adalog_uniform_fq_backward_blocks floats.
-extern "C" int adalog_uniform_fq_backward(const float* gy, const float* x, float* gx, int64_t n, const float* scale,
-                                          const float* zero_point, int64_t n_channels, int64_t inner, int n_bits,
-                                          int symmetric, float* gscale, float* gzp, float* workspace, void* stream) {
+static int uniform_fq_backward(const float* gy, const float* x, float* gx, int64_t n, const float* scale, const float* zero_point,
+                               int64_t n_channels, int64_t inner, int n_bits, int symmetric, float* gscale, float* gzp,
+                               float* workspace, const DropArgs* drop, void* stream) {
     if (n == 0) return 0;
     ADALOG_ARG_CHECK(gy && x && scale && n_channels >= 1 && inner >= 1 && n % inner == 0, "uniform_fq_backward: bad arguments");
     ADALOG_ARG_CHECK(symmetric || zero_point, "uniform_fq_backward: asymmetric needs zero_point");
@@ -1027,8 +1137,12 @@ extern "C" int adalog_uniform_fq_backward(const float* gy, const float* x, float
     // per-tensor parameters: the kernel's last block reduces the partials itself (no finish launches)
     unsigned int* ticket = (ps && n_channels == 1) ? ticket_wide(stream) : nullptr;
     ADALOG_ARG_CHECK(!(ps && n_channels == 1) || ticket, "uniform_fq_backward: cannot allocate the ticket counters");
-    hipLaunchKernelGGL(k_uniform_bwd, dim3(nb, gy_), dim3(256), 0, st, gy, x, gx, rows, inner, scale,
-                       symmetric ? nullptr : zero_point, n_channels, qmin, qmax, ps, pz, ticket, gscale, gzp);
+    if (drop)
+        hipLaunchKernelGGL(k_uniform_bwd<true>, dim3(nb, gy_), dim3(256), 0, st, gy, x, gx, rows, inner, scale,
+                           symmetric ? nullptr : zero_point, n_channels, qmin, qmax, ps, pz, ticket, gscale, gzp, *drop);
+    else
+        hipLaunchKernelGGL(k_uniform_bwd<false>, dim3(nb, gy_), dim3(256), 0, st, gy, x, gx, rows, inner, scale,
+                           symmetric ? nullptr : zero_point, n_channels, qmin, qmax, ps, pz, ticket, gscale, gzp);
     ADALOG_LAUNCH_CHECK("adalog_uniform_fq_backward");
     if (!ticket) {
         if (gscale) hipLaunchKernelGGL(k_param_grad_finish, dim3((unsigned)n_channels), dim3(64), 0, st, ps, rows, nb, n_channels, gscale);
@@ -1036,6 +1150,21 @@ extern "C" int adalog_uniform_fq_backward(const float* gy, const float* x, float
         ADALOG_LAUNCH_CHECK("adalog_uniform_fq_backward/finish");
     }
     return 0;
+}
+extern "C" int adalog_uniform_fq_backward(const float* gy, const float* x, float* gx, int64_t n, const float* scale,
+                                          const float* zero_point, int64_t n_channels, int64_t inner, int n_bits,
+                                          int symmetric, float* gscale, float* gzp, float* workspace, void* stream) {
+    return uniform_fq_backward(gy, x, gx, n, scale, zero_point, n_channels, inner, n_bits, symmetric, gscale, gzp, workspace, nullptr, stream);
+}
+// The gradients of adalog_uniform_fake_quant_drop_f32 (same p / drop_state / drop_stream: the mask is regenerated): gx = gy where
+// dropped; gscale / gzp sum over kept elements only.  Workspace as for adalog_uniform_fq_backward.
+extern "C" int adalog_uniform_fq_backward_drop(const float* gy, const float* x, float* gx, int64_t n, const float* scale,
+                                               const float* zero_point, int64_t n_channels, int64_t inner, int n_bits, int symmetric,
+                                               float* gscale, float* gzp, float* workspace, float p, const int32_t* drop_state,
+                                               int drop_stream, void* stream) {
+    ADALOG_ARG_CHECK(drop_state && p >= 0.0f && p <= 1.0f, "uniform_fq_backward_drop: bad drop arguments");
+    const DropArgs d = {reinterpret_cast<const uint32_t*>(drop_state), (uint32_t)drop_stream, p};
+    return uniform_fq_backward(gy, x, gx, n, scale, zero_point, n_channels, inner, n_bits, symmetric, gscale, gzp, workspace, &d, stream);
 }
 
 // gscale: [1] optional; workspace: 1024 floats
@@ -1047,21 +1176,39 @@ extern "C" int adalog_log_fq_backward(const float* gy, const float* x, const flo
                                       float* gscale, float* workspace, void* stream) {
     return adalog_log_fq_backward_pre(gy, x, y, gx, n, scale, q, n_bits, shift, sub_shift, gscale, workspace, 0, stream);
 }
-// pre = 1: backward of adalog_log_fake_quant_f32_pre -- x is the GELU's INPUT; gx = dL/dx through the quantiser (STE) and the GELU
-extern "C" int adalog_log_fq_backward_pre(const float* gy, const float* x, const float* y, float* gx, int64_t n,
-                                          const float* scale, const int64_t* q, int n_bits, const float* shift, int sub_shift,
-                                          float* gscale, float* workspace, int pre, void* stream) {
+static int log_fq_backward(const float* gy, const float* x, const float* y, float* gx, int64_t n, const float* scale, const int64_t* q,
+                           int n_bits, const float* shift, int sub_shift, float* gscale, float* workspace, int pre,
+                           const DropArgs* drop, void* stream) {
     if (n == 0) return 0;
-    ADALOG_ARG_CHECK(gy && x && y && scale && q, "log_fq_backward: bad arguments");
+    ADALOG_ARG_CHECK(gy && x && (y || drop) && scale && q, "log_fq_backward: bad arguments");
     ADALOG_ARG_CHECK(!gscale || workspace, "log_fq_backward: the scale gradient needs a workspace");
     const int nb = grid1(n, red_cap(1024));
     hipStream_t st = (hipStream_t)stream;
     unsigned int* ticket = gscale ? ticket_wide(stream) : nullptr;
     ADALOG_ARG_CHECK(!gscale || ticket, "log_fq_backward: cannot allocate the ticket counters");
-    hipLaunchKernelGGL(k_adalog_bwd, dim3(nb), dim3(256), 0, st, gy, x, y, gx, n, scale, q, 1 << n_bits, shift, sub_shift,
-                       gscale ? workspace : nullptr, ticket, gscale, pre ? 1 : 0);
+    if (drop)
+        hipLaunchKernelGGL(k_adalog_bwd<true>, dim3(nb), dim3(256), 0, st, gy, x, y, gx, n, scale, q, 1 << n_bits, shift, sub_shift,
+                           gscale ? workspace : nullptr, ticket, gscale, pre ? 1 : 0, *drop);
+    else
+        hipLaunchKernelGGL(k_adalog_bwd<false>, dim3(nb), dim3(256), 0, st, gy, x, y, gx, n, scale, q, 1 << n_bits, shift, sub_shift,
+                           gscale ? workspace : nullptr, ticket, gscale, pre ? 1 : 0);
     ADALOG_LAUNCH_CHECK("adalog_log_fq_backward");
     return 0;
+}
+// pre = 1: backward of adalog_log_fake_quant_f32_pre -- x is the GELU's INPUT; gx = dL/dx through the quantiser (STE) and the GELU
+extern "C" int adalog_log_fq_backward_pre(const float* gy, const float* x, const float* y, float* gx, int64_t n,
+                                          const float* scale, const int64_t* q, int n_bits, const float* shift, int sub_shift,
+                                          float* gscale, float* workspace, int pre, void* stream) {
+    return log_fq_backward(gy, x, y, gx, n, scale, q, n_bits, shift, sub_shift, gscale, workspace, pre, nullptr, stream);
+}
+// The gradients of adalog_log_fake_quant_drop_f32 (same p / drop_state / drop_stream): gx = gy (times GELU'(x) when pre) where
+// dropped; gscale sums over kept elements only.  workspace: 1024 floats.
+extern "C" int adalog_log_fq_backward_drop(const float* gy, const float* x, float* gx, int64_t n, const float* scale, const int64_t* q,
+                                           int n_bits, const float* shift, int sub_shift, float* gscale, float* workspace, int pre,
+                                           float p, const int32_t* drop_state, int drop_stream, void* stream) {
+    ADALOG_ARG_CHECK(drop_state && p >= 0.0f && p <= 1.0f, "log_fq_backward_drop: bad drop arguments");
+    const DropArgs d = {reinterpret_cast<const uint32_t*>(drop_state), (uint32_t)drop_stream, p};
+    return log_fq_backward(gy, x, nullptr, gx, n, scale, q, n_bits, shift, sub_shift, gscale, workspace, pre, &d, stream);
 }
 
 extern "C" int adalog_adaround(const float* w, const float* alpha, const float* gy, float* out, int64_t rows, int64_t inner,

@@ -123,6 +123,43 @@ __device__ __forceinline__ int sdwa_rne_byte(int pk, float tc, float magic /* 12
     return pk;
 }
 
+// ---- QDrop (activation dropping inside a BRECQ iteration): element e of a quantiser's output keeps its fake-quantised value when
+// u_e < p and passes through unquantised otherwise.  u_e comes from Philox4x32-10 (Salmon et al., SC'11), a counter-based generator:
+// no mask is stored, the backward pass of an iteration regenerates the mask of its forward.
+//   key     = (seed_lo, seed_hi)
+//   counter = (e >> 2 low word, e >> 2 high word, iteration, stream)          -- one Philox block per four consecutive elements
+//   u_e     = float(word[e & 3] >> 8) * 2^-24                                 -- p = 1 keeps everything, p = 0 nothing
+// seed and iteration are read from device memory (state = {seed_lo, seed_hi, iteration}): a captured HIP graph draws a new mask
+// on every replay.  ``stream`` tells the quantisers of a block apart.
+struct DropArgs {
+    const uint32_t* state;
+    uint32_t stream;
+    float p;
+};
+
+__device__ __forceinline__ uint4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        c1 = (uint32_t)p1; c3 = (uint32_t)p0; c0 = n0; c2 = n2;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    return make_uint4(c0, c1, c2, c3);
+}
+
+// the Philox block of elements 4 * blk .. 4 * blk + 3 of this quantiser in this iteration
+__device__ __forceinline__ uint4 drop_words(const DropArgs& d, int64_t blk) {
+    return philox4x32_10((uint32_t)blk, (uint32_t)((uint64_t)blk >> 32), d.state[2], d.stream, d.state[0], d.state[1]);
+}
+__device__ __forceinline__ bool drop_keep(uint32_t word, float p) { return (float)(word >> 8) * 5.9604644775390625e-8f < p; }
+// ... of the single element e (the scalar paths: rows that are no multiple of four, unaligned tensors)
+__device__ __forceinline__ bool drop_keep_at(const DropArgs& d, int64_t e) {
+    const uint4 w = drop_words(d, e >> 2);
+    const int j = (int)(e & 3);
+    return drop_keep(j == 0 ? w.x : (j == 1 ? w.y : (j == 2 ? w.z : w.w)), d.p);
+}
+
 // ---- fast forms used by the operand-packing kernels (hundreds of millions of elements per scoring call).
 // Both evaluate with a reciprocal multiply first and fall back to the exact IEEE sequence above only when the result
 // lands within 1e-3 of a rounding tie, so they return EXACTLY the same integer as the exact forms (the reciprocal path

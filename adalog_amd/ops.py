@@ -1610,6 +1610,78 @@ def log_fake_quant_backward(gy, x, y, scale, q, n_bits: int, shift, sub_shift: b
     return gx, gs
 
 
+# QDrop forms (quantizers/_drop.py holds the definition): ``p`` the keep probability, ``state`` = (device int32[3] {seed_lo, seed_hi,
+# iteration}, Philox stream of the quantiser).  The kernels read seed and iteration on the device; no mask is stored.
+def _drop_state(state):
+    buf, stream = state
+    if not (buf.is_cuda and buf.dtype == torch.int32 and buf.is_contiguous() and buf.numel() >= 3):
+        raise _lib.AdalogHipError("drop state: a contiguous int32 tensor {seed_lo, seed_hi, iteration} on the HIP device")
+    return buf, stream
+
+
+def uniform_fake_quant_drop(x, scale, zero_point, n_bits: int, sym: bool, p: float, state):
+    """y = where(keep, fq(x), x) of the training form (keep: quantizers/_drop.py philox_keep_mask)."""
+    x, scale = _f32c(x, "x"), _f32c(scale, "scale")
+    zp = None if sym else _f32c(zero_point, "zero_point")
+    buf, stream = _drop_state(state)
+    n_ch, inner = broadcast_layout(x.shape, scale.shape)
+    y = torch.empty_like(x)
+    rc = _lib.load().adalog_uniform_fake_quant_drop_f32(x.data_ptr(), y.data_ptr(), x.numel(), scale.data_ptr(), _ptr(zp), n_ch, inner,
+                                                       int(n_bits), int(bool(sym)), float(p), buf.data_ptr(), int(stream), _stream())
+    _lib.check(rc, "adalog_uniform_fake_quant_drop_f32")
+    return y
+
+
+def uniform_fake_quant_backward_drop(gy, x, scale, zero_point, n_bits: int, sym: bool, want_gscale: bool, want_gzp: bool, p: float, state):
+    """-> (gx, gscale | None, gzp | None) of uniform_fake_quant_drop (the mask is regenerated from ``state``)."""
+    gy, x, scale = _f32c(gy, "gy"), _f32c(x, "x"), _f32c(scale, "scale")
+    zp = None if sym else _f32c(zero_point, "zero_point")
+    buf, stream = _drop_state(state)
+    n_ch, inner = broadcast_layout(x.shape, scale.shape)
+    lib = _lib.load()
+    gx = torch.empty_like(x)
+    gs = torch.empty_like(scale) if want_gscale else None
+    gz = torch.empty_like(zp) if (want_gzp and zp is not None) else None
+    ws = None
+    if gs is not None or gz is not None:
+        nb = lib.adalog_uniform_fq_backward_blocks(x.numel(), n_ch, inner)
+        ws = torch.empty(2 * (x.numel() // inner) * nb, dtype=torch.float32, device=x.device)
+    rc = lib.adalog_uniform_fq_backward_drop(gy.data_ptr(), x.data_ptr(), gx.data_ptr(), x.numel(), scale.data_ptr(), _ptr(zp), n_ch, inner,
+                                             int(n_bits), int(bool(sym)), _ptr(gs), _ptr(gz), _ptr(ws), float(p), buf.data_ptr(),
+                                             int(stream), _stream())
+    _lib.check(rc, "adalog_uniform_fq_backward_drop")
+    return gx, gs, gz
+
+
+def log_fake_quant_drop(x, scale, q, n_bits: int, shift, sub_shift: bool, pre_gelu: bool, p: float, state):
+    """y = where(keep, fq(x'), x') of AdaLog's training form, x' = GELU(x) when ``pre_gelu``."""
+    x, scale = _f32c(x, "x"), _f32c(scale, "scale")
+    buf, stream = _drop_state(state)
+    if scale.numel() != 1:
+        raise ValueError("AdaLog quantisers are per-tensor (scale must have one element)")
+    y = torch.empty_like(x)
+    rc = _lib.load().adalog_log_fake_quant_drop_f32(x.data_ptr(), y.data_ptr(), x.numel(), scale.data_ptr(), q.data_ptr(), int(n_bits),
+                                                   _ptr(None if shift is None else _f32c(shift, "shift")), int(bool(sub_shift)),
+                                                   int(bool(pre_gelu)), float(p), buf.data_ptr(), int(stream), _stream())
+    _lib.check(rc, "adalog_log_fake_quant_drop_f32")
+    return y
+
+
+def log_fake_quant_backward_drop(gy, x, scale, q, n_bits: int, shift, sub_shift: bool, pre_gelu: bool, p: float, state):
+    """-> (gx, gscale) of log_fake_quant_drop."""
+    gy, x, scale = _f32c(gy, "gy"), _f32c(x, "x"), _f32c(scale, "scale")
+    buf, stream = _drop_state(state)
+    gx = torch.empty_like(x)
+    gs = torch.empty_like(scale)
+    ws = torch.empty(1024, dtype=torch.float32, device=x.device)
+    rc = _lib.load().adalog_log_fq_backward_drop(gy.data_ptr(), x.data_ptr(), gx.data_ptr(), x.numel(), scale.data_ptr(), q.data_ptr(),
+                                                int(n_bits), _ptr(None if shift is None else _f32c(shift, "shift")),
+                                                int(bool(sub_shift)), gs.data_ptr(), ws.data_ptr(), int(bool(pre_gelu)), float(p),
+                                                buf.data_ptr(), int(stream), _stream())
+    _lib.check(rc, "adalog_log_fq_backward_drop")
+    return gx, gs
+
+
 def adaround(w2, alpha2, scale, zero_point, n_bits: int, soft: bool, gy=None):
     """Forward value (gy is None) or d/d alpha (gy given) of the AdaRound weight quantiser; w2/alpha2: [rows, inner]."""
     w2, alpha2 = _f32c(w2, "w"), _f32c(alpha2, "alpha")
@@ -1902,6 +1974,53 @@ def qkv_merge_quant_backward(gys, x: torch.Tensor, H: int, scales, zps, n_bits, 
     rc = lib.adalog_qkv_merge_quant_backward(_ptr(gs[0]), _ptr(gs[1]), _ptr(gs[2]), x.data_ptr(), _ptr(gx), B, N, int(H), int(D), psc, pzp,
                                              ph, nb, PA(*[t.data_ptr() for t in gsc]), ws.data_ptr(), _stream())
     _lib.check(rc, "adalog_qkv_merge_quant_backward")
+    return gx, [g_.view_as(s_) for g_, s_ in zip(gsc, scales)]
+
+
+def _qkv_drop(p, state):
+    import ctypes
+    buf, streams = _drop_state(state)
+    if len(p) != 3 or len(streams) != 3:
+        raise ValueError("qkv drop: three probabilities and three streams (q, k, v)")
+    return buf, (ctypes.c_float * 3)(*[float(v) for v in p]), (ctypes.c_int * 3)(*[int(v) for v in streams])
+
+
+def qkv_split_quant_drop(x: torch.Tensor, H: int, scales, zps, n_bits, p, state):
+    """qkv_split_quant with QDrop: ``p`` three keep probabilities, ``state`` = (device int32[3], three Philox streams); the element
+    index of a part is the index in its contiguous [B, H, N, D] output."""
+    x = _f32c(x, "x")
+    B, N, C = x.shape
+    D = C // (3 * H)
+    if C != 3 * H * D or D not in (32, 64):
+        raise _lib.AdalogHipError("qkv_split_quant_drop: head dimension 32 or 64")
+    buf, ps, streams = _qkv_drop(p, state)
+    ys = [torch.empty((B, H, N, D), dtype=torch.float32, device=x.device) for _ in range(3)]
+    sc, zp, psc, pzp, ph, nb = _qkv_params(scales, zps, n_bits, H)
+    rc = _lib.load().adalog_qkv_split_quant_drop(x.data_ptr(), ys[0].data_ptr(), ys[1].data_ptr(), ys[2].data_ptr(), B, N, int(H), int(D),
+                                                psc, pzp, ph, nb, ps, buf.data_ptr(), streams, _stream())
+    _lib.check(rc, "adalog_qkv_split_quant_drop")
+    return tuple(ys)
+
+
+def qkv_merge_quant_backward_drop(gys, x: torch.Tensor, H: int, scales, zps, n_bits, p, state, want_gx: bool = True):
+    """Gradients of qkv_split_quant_drop (as qkv_merge_quant_backward; the masks are regenerated from ``state``)."""
+    import ctypes
+    x = _f32c(x, "x")
+    B, N, C = x.shape
+    D = C // (3 * H)
+    gs = [None if g_ is None else _f32c(g_, "gy") for g_ in gys]
+    lib = _lib.load()
+    buf, ps, streams = _qkv_drop(p, state)
+    sc, zp, psc, pzp, ph, nb = _qkv_params(scales, zps, n_bits, H)
+    gx = torch.empty_like(x) if want_gx else None
+    gsc = [torch.empty_like(t) for t in sc]
+    nch = int(lib.adalog_qkv_quant_chunks(B, N, int(D)))
+    ws = torch.empty(3 * H * nch, dtype=torch.float32, device=x.device)
+    PA = ctypes.c_void_p * 3
+    rc = lib.adalog_qkv_merge_quant_backward_drop(_ptr(gs[0]), _ptr(gs[1]), _ptr(gs[2]), x.data_ptr(), _ptr(gx), B, N, int(H), int(D), psc,
+                                                  pzp, ph, nb, PA(*[t.data_ptr() for t in gsc]), ws.data_ptr(), ps, buf.data_ptr(),
+                                                  streams, _stream())
+    _lib.check(rc, "adalog_qkv_merge_quant_backward_drop")
     return gx, [g_.view_as(s_) for g_, s_ in zip(gsc, scales)]
 
 

@@ -11,6 +11,7 @@ import torch
 import torch.nn as nn
 
 from .. import backend
+from . import _drop
 
 
 class _AdaLogSTE(torch.autograd.Function):
@@ -47,7 +48,8 @@ class AdaLogQuantizer(nn.Module):
         self.n_bits = n_bits
         self.n_levels = 2 ** (self.n_bits - 1)
         self.inited = False
-        self.drop_prob = 1.0
+        self.drop_prob = 1.0                             # QDrop keep probability of the training form (_drop.py); 1.0: off
+        self.drop_state = None                           # (device int32 {seed_lo, seed_hi, iteration}, stream): the reconstructor's
         self.channel_wise = channel_wise
         self.training_mode = False
         self.r = 37.0
@@ -59,8 +61,12 @@ class AdaLogQuantizer(nn.Module):
     def init_training(self):
         self.training_mode = True
 
+    def attach_drop_state(self, buf, stream: int):
+        self.drop_state = (buf, int(stream))
+
     def end_training(self):
         self.training_mode = False
+        self.drop_state = None
 
     @staticmethod
     def make_tables(q: int, n_levels: int, r: float = 37.0):
@@ -89,6 +95,9 @@ class AdaLogQuantizer(nn.Module):
         if self.training_mode and torch.is_grad_enabled():
             if pre_gelu and not self.fused_gelu_ok(x):
                 x, pre_gelu = torch.nn.functional.gelu(x), False
+            if _drop.active(self):
+                return _drop.AdaLogDropSTE.apply(x, self.scale, self.q, self.n_bits, shift, sub, pre_gelu, float(self.drop_prob),
+                                                 *self.drop_state)
             return _AdaLogSTE.apply(x, self.scale, self.q, self.n_bits, shift, sub, pre_gelu)
         if pre_gelu:
             x = torch.nn.functional.gelu(x)

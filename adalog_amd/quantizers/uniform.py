@@ -8,6 +8,7 @@ import torch
 import torch.nn as nn
 
 from .. import backend
+from . import _drop
 from ._ste import round_ste
 
 
@@ -56,7 +57,8 @@ class UniformQuantizer(nn.Module):
         self.n_bits = n_bits
         self.n_levels = 2 ** (self.n_bits - 1)
         self.channel_wise = channel_wise
-        self.drop_prob = 1.0
+        self.drop_prob = 1.0                             # QDrop keep probability of the training form (_drop.py); 1.0: off
+        self.drop_state = None                           # (device int32 {seed_lo, seed_hi, iteration}, stream): the reconstructor's
         self.inited = False
         self.training_mode = False
         self.use_clip_forward = False
@@ -64,8 +66,12 @@ class UniformQuantizer(nn.Module):
     def init_training(self):
         self.training_mode = True
 
+    def attach_drop_state(self, buf, stream: int):
+        self.drop_state = (buf, int(stream))
+
     def end_training(self):
         self.training_mode = False
+        self.drop_state = None
         self.forget_codes_fit()
 
     def codes_fit(self, lo: int, hi: int) -> bool:
@@ -94,6 +100,9 @@ class UniformQuantizer(nn.Module):
         if self.n_bits == 32:
             return x
         assert self.inited
+        if _drop.active(self):
+            return _drop.UniformDropSTE.apply(x, self.scale, None if self.sym else self.zero_point, self.n_bits, self.sym,
+                                              float(self.drop_prob), *self.drop_state)
         if self.training_mode and torch.is_grad_enabled():
             return _UniformSTE.apply(x, self.scale, None if self.sym else self.zero_point, self.n_bits, self.sym)
         return backend.get().uniform_fake_quant(x, self.scale.data, None if self.sym else self.zero_point.data,

@@ -21,6 +21,7 @@ import torch
 import torch.nn.functional as F
 
 from . import backend
+from .quantizers import _drop
 
 ENABLED = os.environ.get("ADALOG_BRECQ_MM", "1") != "0"
 # pre-split w_sim planes (1) or the split in the GEMM's registers (0, default: measured 571 against 546 it/s on a deit_small block --
@@ -184,8 +185,10 @@ def quant_linear(x, a_quantizer, w_sim, bias, pre_gelu=False, addend=None):
     lead = x.shape[:-1]
     x2 = x.reshape(-1, x.shape[-1])
     aq = a_quantizer
+    # (QDrop: a dropped element is no integer multiple of the scale -- the integer operand cannot hold it; the quantiser's own drop
+    # kernels run and the general product takes their output)
     fused = (INT_ACT and type(aq) is UniformQuantizer and aq.training_mode and not aq.sym and aq.n_bits < 8
-             and aq.scale.numel() == 1 and torch.is_grad_enabled() and _usable(x2, w_sim, bias))
+             and aq.scale.numel() == 1 and torch.is_grad_enabled() and _usable(x2, w_sim, bias) and not _drop.active(aq))
     if not fused:
         return linear(aq(x), w_sim, bias, addend)
     out = _QuantLinearFn.apply(x2.contiguous(), aq.scale.view(1), aq.zero_point.view(1), w_sim.contiguous(), bias, aq.n_bits)
@@ -244,6 +247,27 @@ class _QkvQuantFn(torch.autograd.Function):
         return gx, (gs[0] if need[1] else None), None, (gs[1] if need[3] else None), None, (gs[2] if need[5] else None), None, None, None
 
 
+class _QkvQuantDropFn(torch.autograd.Function):
+    """_QkvQuantFn with QDrop: the three quantisers drop on their own Philox streams (adalog_qkv_split_quant_drop /
+    adalog_qkv_merge_quant_backward_drop); element index = the index in each contiguous [B, H, N, D] output."""
+
+    @staticmethod
+    def forward(ctx, x, s0, z0, s1, z1, s2, z2, H, bits, ps, buf, streams):
+        be = backend.get()
+        ctx.save_for_backward(x, s0, z0, s1, z1, s2, z2)
+        ctx.H, ctx.bits, ctx.ps, ctx.state = H, bits, ps, (buf, streams)
+        return be.qkv_split_quant_drop(x, H, [s0, s1, s2], [z0, z1, z2], bits, ps, ctx.state)
+
+    @staticmethod
+    def backward(ctx, g0, g1, g2):
+        x, s0, z0, s1, z1, s2, z2 = ctx.saved_tensors
+        gx, gs = backend.get().qkv_merge_quant_backward_drop([g0, g1, g2], x, ctx.H, [s0, s1, s2], [z0, z1, z2], ctx.bits, ctx.ps,
+                                                             ctx.state, want_gx=ctx.needs_input_grad[0])
+        need = ctx.needs_input_grad
+        return (gx, (gs[0] if need[1] else None), None, (gs[1] if need[3] else None), None, (gs[2] if need[5] else None), None, None, None,
+                None, None, None)
+
+
 def qkv_split_quant(x, H, mm1, mm2):
     """The fused route of an attention block inside a BRECQ iteration: q, k, v split from x [B, N, 3*H*D] AND passed through the
     input quantisers of the two attention products (mm1.A_quantizer for q, mm1.B_quantizer for k -- elementwise per head, so it
@@ -263,6 +287,15 @@ def qkv_split_quant(x, H, mm1, mm2):
         if not (type(q_) is UniformQuantizer and q_.training_mode and q_.inited and not q_.sym and q_.n_bits <= 8
                 and q_.scale.numel() in (1, H) and q_.zero_point.numel() == q_.scale.numel() and not q_.zero_point.requires_grad):
             return None
+    if any(_drop.active(q_) for q_ in qs):
+        # one launch for the three quantisers needs one state buffer; a quantiser that does not drop keeps everything (p = 1)
+        states = [q_.drop_state for q_ in qs if _drop.active(q_)]
+        if not hasattr(backend.get(), "qkv_split_quant_drop") or any(st[0] is not states[0][0] for st in states):
+            return None
+        ps = tuple(float(q_.drop_prob) if _drop.active(q_) else 1.0 for q_ in qs)
+        streams = tuple(q_.drop_state[1] if _drop.active(q_) else 0 for q_ in qs)
+        return _QkvQuantDropFn.apply(x.contiguous(), qs[0].scale, qs[0].zero_point, qs[1].scale, qs[1].zero_point, qs[2].scale,
+                                     qs[2].zero_point, H, tuple(q_.n_bits for q_ in qs), ps, states[0][0], streams)
     return _QkvQuantFn.apply(x.contiguous(), qs[0].scale, qs[0].zero_point, qs[1].scale, qs[1].zero_point, qs[2].scale,
                              qs[2].zero_point, H, tuple(q_.n_bits for q_ in qs))
 

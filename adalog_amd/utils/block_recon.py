@@ -22,11 +22,19 @@ from .. import backend, parallel, train_mm
 from ..quant_layers import MinMaxQuantConv2d, MinMaxQuantLinear, MinMaxQuantMatMul
 from ..quantizers.adaround import AdaRoundQuantizer
 from ..quantizers import adaround as adaround_mod
+from ..quantizers import _drop
 from .calibrator import QuantCalibrator
 from . import models as M
 
 # gather of the mini-batch (inputs, outputs) and the iteration's schedule row in ONE launch before a graph replay (adalog_brecq_prepare)
 PREPARE_FUSED = os.environ.get("ADALOG_BRECQ_PREPARE", "1") != "0"
+_DROP_IGNORED_LOGGED = False
+
+
+def drop_seed(block_index: int, rank: int = 0) -> int:
+    """The 64-bit Philox key of a block's QDrop masks: 1234 (+ the rank in batch-split data-parallel mode, as the mini-batch
+    generator's seed) mixed with the block's index.  Block-parallel BRECQ trains a block as one process would: rank 0 there."""
+    return ((1234 + int(rank)) ^ (((int(block_index) + 1) * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF)) & 0xFFFFFFFFFFFFFFFF
 
 
 class HipAdam(torch.optim.Optimizer):
@@ -81,6 +89,8 @@ class HipAdam(torch.optim.Optimizer):
 
 
 class BlockReconstructor(QuantCalibrator):
+    drop_prob = None                   # QDrop keep probability of a reconstruct_model() call that gives none (quant_qdrop.py sets it)
+
     def __init__(self, model, full_model, calib_loader):
         super().__init__(model, calib_loader)
         self.full_model = full_model
@@ -164,7 +174,10 @@ class BlockReconstructor(QuantCalibrator):
 
     def reconstruct_single_block(self, name, block, device, batch_size: int = 32, iters: int = 20000,
                                  weight: float = 0.01, b_range: tuple = (20, 2), warmup: float = 0.2, lr: float = 4e-5,
-                                 p: float = 2.0, quant_act=False):
+                                 p: float = 2.0, quant_act=False, drop_prob: float = 1.0):
+        """``drop_prob`` < 1 (QDrop, quantizers/_drop.py; with ``quant_act`` only): every activation quantiser of the block keeps a
+        fake-quantised element with that probability during the iterations.  Quantisers whose ``drop_prob`` the caller set below 1
+        drop as well.  1.0 (and no such quantiser): the code path of a call without the argument."""
         self.wrap_quantizers_in_net(block, name)
         self.set_block_mode(block, 'quant_forward')
         for _, module in block.named_modules():
@@ -184,6 +197,20 @@ class BlockReconstructor(QuantCalibrator):
                         a_params += [module.A_quantizer.scale, module.B_quantizer.scale]
                     else:
                         module.mode = 'raw'
+        drop_qs, drop_prev = [], []
+        if quant_act:
+            a_qs = _drop.activation_quantizers(block)
+            drop_prev = [(q_, q_.drop_prob) for q_ in a_qs]
+            if float(drop_prob) < 1.0:
+                for q_ in a_qs:
+                    q_.drop_prob = float(drop_prob)
+            if any(q_.drop_prob < 1.0 for q_ in a_qs):
+                drop_qs = a_qs                               # (the position in a_qs is the quantiser's Philox stream)
+        elif float(drop_prob) < 1.0 or any(q_.drop_prob < 1.0 for q_ in _drop.activation_quantizers(block)):
+            global _DROP_IGNORED_LOGGED
+            if not _DROP_IGNORED_LOGGED:
+                logging.info('drop_prob={} is ignored: activation quantisers are off (quant_act=False)'.format(drop_prob))
+                _DROP_IGNORED_LOGGED = True
         ws = parallel.world_size()
         local_bs = max(1, batch_size // ws)
         n_local = block.raw_input.size(0)
@@ -213,8 +240,24 @@ class BlockReconstructor(QuantCalibrator):
         # python floats by the reference's own objects (LinearTempDecay, torch's CosineAnnealingLR on a float learning rate).
         table_mode = full_graph and hip_adam
         sched_dev = torch.zeros(3, dtype=torch.float32, device=device) if table_mode else None
+        # QDrop: the masks' key and the iteration number live in an int32 device triple {seed_lo, seed_hi, iteration} the quantisers'
+        # kernels read.  In table mode the triple and the schedule share ONE buffer -- words {seed_lo, seed_hi, iteration, b, gate, lr}
+        # -- and the schedule row grows a leading column, the iteration number (its int32 bits in a float), that lands on word 2: the
+        # copy / adalog_brecq_prepare launch that refreshes the schedule before a replay advances the iteration too.
+        drop_state, so = None, 0
+        if drop_qs:
+            names = list(getattr(self, 'blocks', {}).keys())
+            blk_index = names.index(name) if name in names else 0
+            drop_state = _drop.make_state(drop_seed(blk_index, parallel.rank()), 0, device)
+            if table_mode:
+                words = torch.zeros(6, dtype=torch.int32, device=device)
+                words[:3] = drop_state
+                drop_state, sched_dev, so = words[0:3], words.view(torch.float32)[2:6], 1
+            for i, q_ in enumerate(drop_qs):
+                if q_.drop_prob < 1.0:
+                    q_.attach_drop_state(drop_state, i)
         if table_mode:
-            a_lr = sched_dev[2:3]
+            a_lr = sched_dev[2 + so:3 + so]
             a_lr.fill_(lr)
         if hip_adam:
             w_optimizer = HipAdam(w_params)
@@ -309,7 +352,10 @@ class BlockReconstructor(QuantCalibrator):
                     rows.append([float(loss_func.temp_decay(count)) if active else 0.0, 1.0 if active else 0.0,
                                  float(twin_opt.param_groups[0]['lr'])])
                     twin.step()                              # (block_recon.py:124-125: the scheduler steps after the optimiser)
-                host = torch.tensor(rows, dtype=torch.float32).pin_memory()
+                host = torch.tensor(rows, dtype=torch.float32)
+                if so:                                       # QDrop: the iteration number in front (bit pattern, see drop_state)
+                    host = torch.cat([torch.arange(it, it + cnt, dtype=torch.int32).view(torch.float32).unsqueeze(1), host], dim=1)
+                host = host.pin_memory()
                 sched_block, sched_base = host.to(device, non_blocking=True), it
             if copy:
                 sched_dev.copy_(sched_block[it - sched_base])
@@ -320,8 +366,15 @@ class BlockReconstructor(QuantCalibrator):
             iteration) on a FIXED set of its optimisation images -- what the iterations are meant to lower (block_recon.py:189-198)"""
             n_eval = min(n_local, 2 * local_bs)
             train_mm.reset_offers()
-            with torch.enable_grad():                        # the iteration's own forward path (contractions on csrc/brecq_gemm.hip)
-                pred = block(block.raw_input[:n_eval].to(device)).detach()
+            held = [(q_, q_.drop_state) for q_ in drop_qs]   # QDrop: the report quantises every element
+            for q_ in drop_qs:
+                q_.drop_state = None
+            try:
+                with torch.enable_grad():                    # the iteration's own forward path (contractions on csrc/brecq_gemm.hip)
+                    pred = block(block.raw_input[:n_eval].to(device)).detach()
+            finally:
+                for q_, st_ in held:
+                    q_.drop_state = st_
             with torch.no_grad():
                 return float(loss_func.rec_term(pred, block.raw_out[:n_eval].to(device)))
 
@@ -334,6 +387,8 @@ class BlockReconstructor(QuantCalibrator):
                 sched_row = None
                 if table_mode:
                     sched_row = next_schedule(it, copy=not replaying)
+                elif drop_state is not None:
+                    drop_state[2:3].fill_(it)                # (table mode: the schedule row carries it)
                 if not use_graph or it < 3:                  # eager (and the warm-up iterations before the capture)
                     eager_step(block.raw_input[idx].to(device), block.raw_out[idx].to(device))
                     if iter_hook is not None:
@@ -342,7 +397,7 @@ class BlockReconstructor(QuantCalibrator):
                 if graph is None:
                     static_inp, static_out = block.raw_input[idx].to(device).clone(), block.raw_out[idx].to(device).clone()
                     if table_mode:
-                        b_dev, rw_dev = sched_dev[0:1], sched_dev[1:2]
+                        b_dev, rw_dev = sched_dev[so:so + 1], sched_dev[so + 1:so + 2]
                     else:
                         b_dev = torch.zeros(1, dtype=torch.float32, device=device)
                         rw_dev = torch.zeros(1, dtype=torch.float32, device=device)
@@ -410,6 +465,10 @@ class BlockReconstructor(QuantCalibrator):
             torch.backends.cuda.matmul.allow_tf32 = prev_tf32
             for prm in frozen:
                 prm.requires_grad_(True)
+            for q_ in drop_qs:                               # the iterations are over: the report below quantises every element
+                q_.drop_state = None
+            for q_, prev in drop_prev:
+                q_.drop_prob = prev
         if report:
             rec_after = fixed_rec_loss()
             self.__dict__.setdefault('rec_report', {})[name] = (rec_before, rec_after)
@@ -438,7 +497,7 @@ class BlockReconstructor(QuantCalibrator):
                     out += [module.A_quantizer.scale, module.B_quantizer.scale]
         return out
 
-    def _reconstruct_blocks_parallel(self, device, quant_act, keep_gpu, iters):
+    def _reconstruct_blocks_parallel(self, device, quant_act, keep_gpu, iters, drop_prob=1.0):
         """Block-parallel BRECQ over the ranks.  A block's inputs AND targets come from the FP model (block_recon.py:62-82), so
         the blocks are independent: they are dealt to the ranks round-robin, every rank trains the blocks it owns exactly as a
         single process would (full mini-batch, full HIP-graph replay, no collective inside the 20 000 iterations), and the
@@ -490,7 +549,7 @@ class BlockReconstructor(QuantCalibrator):
                 block.raw_input, block.raw_out = gin, gout
                 del mine, gin, gout
                 with parallel.solo():
-                    self.reconstruct_single_block(name, block, device, quant_act=quant_act, iters=iters)
+                    self.reconstruct_single_block(name, block, device, quant_act=quant_act, iters=iters, drop_prob=drop_prob)
             # the ranks meet here once per round: a wait is at most one block's training (the process group's timeout -- 
             # ADALOG_DIST_TIMEOUT_MIN, default 120 -- is what bounds it, not the library's 10 minutes)
             parallel.barrier()
@@ -518,15 +577,26 @@ class BlockReconstructor(QuantCalibrator):
             weights = max(weights, block.weight.numel())
         return float(tokens) * float(max(1, weights))
 
-    def reconstruct_model(self, quant_act: bool = False, keep_gpu: bool = True, iters: int = 20000):
+    def reconstruct_model(self, quant_act: bool = False, keep_gpu: bool = True, iters: int = 20000, drop_prob: float = None):
+        """``drop_prob`` (QDrop, see reconstruct_single_block): a number is set on every activation quantiser of the model, 1.0
+        included (off, whatever they carried); None takes ``self.drop_prob``, and with that None as well the quantisers keep their
+        own -- 1.0 unless the config gave wrap_modules_in_net another."""
         device = next(self.model.parameters()).device
+        if drop_prob is None:
+            drop_prob = self.drop_prob
+        if drop_prob is not None:
+            if not 0.0 <= float(drop_prob) <= 1.0:
+                raise ValueError("drop_prob must lie in [0, 1]")
+            for q_ in _drop.activation_quantizers(self.model):
+                q_.drop_prob = float(drop_prob)
+        drop_prob = 1.0                                      # (the quantisers carry it from here on)
         for _, module in self.model.named_modules():
             if hasattr(module, 'mode'):
                 module.mode = 'raw'
         self.dp_mode = 'single'
         if parallel.world_size() > 1 and os.environ.get("ADALOG_BRECQ_DP", "block") != "batch":
             self.dp_mode = 'block'
-            self._reconstruct_blocks_parallel(device, quant_act, keep_gpu, iters)
+            self._reconstruct_blocks_parallel(device, quant_act, keep_gpu, iters, drop_prob)
         else:
             if parallel.world_size() > 1:
                 self.dp_mode = 'batch'
@@ -534,7 +604,7 @@ class BlockReconstructor(QuantCalibrator):
                 block, full_block = self.blocks[name], self.full_blocks[name]
                 logging.info('reconstructing {} ...'.format(name))
                 self.init_block_raw_data(block, full_block, name, device, keep_gpu=keep_gpu)
-                self.reconstruct_single_block(name, block, device, quant_act=quant_act, iters=iters)
+                self.reconstruct_single_block(name, block, device, quant_act=quant_act, iters=iters, drop_prob=drop_prob)
         for _, module in self.model.named_modules():
             if hasattr(module, 'mode'):
                 module.mode = 'quant_forward'

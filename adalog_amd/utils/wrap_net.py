@@ -12,6 +12,7 @@ from ..quant_layers.conv import AsymmetricallyBatchingQuantConv2d
 from ..quant_layers.linear import (AsymmetricallyBatchingQuantLinear, AsymmetricallyChannelWiseBatchingQuantLinear,
                                    PostGeluLogBasedBatchingQuantLinear)
 from ..quant_layers.matmul import AsymmetricallyBatchingQuantMatMul, PostSoftmaxAsymmetricallyBatchingQuantMatMul
+from ..quantizers import _drop
 from .models import MatMul
 
 
@@ -79,6 +80,14 @@ def wrap_modules_in_net(model, cfg, reparam=False):
             new_module.to(dev)
             setattr(father, leaf, new_module)
             module_dict[name] = new_module
+    # QDrop (quantizers/_drop.py): a config may carry the keep probability of the BRECQ iterations; the activation quantisers hold it
+    # until block reconstruction reads it.  configs/ carry none: 1.0, off.
+    drop_prob = float(getattr(cfg, "drop_prob", 1.0))
+    if not 0.0 <= drop_prob <= 1.0:
+        raise ValueError("config drop_prob must lie in [0, 1]")
+    if drop_prob < 1.0:
+        for q_ in _drop.activation_quantizers(model):
+            q_.drop_prob = drop_prob
     return model
 
 
@@ -100,6 +109,7 @@ def wrap_reparamed_modules_in_net(model):
         new_module.calibrated = True
         new_module.a_quantizer.inited = True
         new_module.w_quantizer.inited = True
+        new_module.a_quantizer.drop_prob = module.a_quantizer.drop_prob
         new_module.to(module.weight.device)
         setattr(father, leaf, new_module)
     return model

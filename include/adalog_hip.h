@@ -638,6 +638,34 @@ int adalog_uniform_fq_backward(const float* gy, const float* x, float* gx, int64
 int adalog_log_fq_backward(const float* gy, const float* x, const float* y, float* gx, int64_t n, const float* scale,
                            const int64_t* q, int n_bits, const float* shift, int sub_shift, float* gscale, float* workspace,
                            void* stream);
+/* QDrop (Wei et al., ICLR 2022) forms of the training-form quantisers above, for BRECQ iterations: element e (linear index in the
+ *   quantiser's output, storage order) keeps its fake-quantised value when u_e < p and takes the quantiser's input otherwise
+ *   (GELU(x) when pre; x itself for the shift variants); a dropped element passes its gradient through (times GELU'(x) when pre)
+ *   and adds nothing to the parameter gradients.  u_e = float(w >> 8) * 2^-24 with w = word e & 3 of Philox4x32-10 under key
+ *   (seed_lo, seed_hi) at counter (e >> 2 low, e >> 2 high, iteration, drop_stream); drop_state = device int32[3] {seed_lo, seed_hi,
+ *   iteration}, read by the kernels (a captured graph draws a new mask per replay; a backward call with the same arguments
+ *   regenerates its forward's mask).  No mask is stored.  Kept elements: exactly the operations of the calls above; p = 1 equals them.
+ *   The uniform forms take the [rows][inner] broadcast layout (inner == 1 with n_channels > 1 is rejected).  The q/k/v forms take
+ *   HOST arrays of three probabilities and three streams; e indexes each part's [B][H][N][D] output.  Workspaces as above. */
+int adalog_uniform_fake_quant_drop_f32(const float* x, float* y, int64_t n, const float* scale, const float* zero_point,
+                                       int64_t n_channels, int64_t inner, int n_bits, int symmetric, float p,
+                                       const int32_t* drop_state, int drop_stream, void* stream);
+int adalog_uniform_fq_backward_drop(const float* gy, const float* x, float* gx, int64_t n, const float* scale, const float* zero_point,
+                                    int64_t n_channels, int64_t inner, int n_bits, int symmetric, float* gscale, float* gzp,
+                                    float* workspace, float p, const int32_t* drop_state, int drop_stream, void* stream);
+int adalog_log_fake_quant_drop_f32(const float* x, float* y, int64_t n, const float* scale, const int64_t* q, int n_bits,
+                                   const float* shift, int sub_shift, int pre, float p, const int32_t* drop_state, int drop_stream,
+                                   void* stream);
+int adalog_log_fq_backward_drop(const float* gy, const float* x, float* gx, int64_t n, const float* scale, const int64_t* q, int n_bits,
+                                const float* shift, int sub_shift, float* gscale, float* workspace, int pre, float p,
+                                const int32_t* drop_state, int drop_stream, void* stream);
+int adalog_qkv_split_quant_drop(const float* src, float* y0, float* y1, float* y2, int64_t B, int64_t N, int H, int D,
+                                const float* const* scales, const float* const* zps, const int* per_head, const int* n_bits,
+                                const float* ps, const int32_t* drop_state, const int* drop_streams, void* stream);
+int adalog_qkv_merge_quant_backward_drop(const float* g0, const float* g1, const float* g2, const float* src, float* gx, int64_t B,
+                                         int64_t N, int H, int D, const float* const* scales, const float* const* zps,
+                                         const int* per_head, const int* n_bits, float* const* gscales, float* workspace,
+                                         const float* ps, const int32_t* drop_state, const int* drop_streams, void* stream);
 int adalog_adaround(const float* w, const float* alpha, const float* gy, float* out, int64_t rows, int64_t inner,
                     const float* scale, const float* zero_point, int n_bits, int soft, int backward, void* stream);
 /* adalog_adaround's forward writing both orientations: out [rows][inner] and out_t [inner][rows] (the K-major image of the
