@@ -13,15 +13,16 @@ LIB_PATH = os.environ.get("ADALOG_LIB") or os.path.join(_HERE, "csrc", "libadalo
 
 p, i32, i64, f32, f64 = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double
 
-# name -> (restype, argtypes); must list every function of include/adalog_hip.h (tests/test_abi.py checks that)
+# ADALOG_ABI_VERSION of include/adalog_hip.h: what SIGNATURES below was written against
+ABI_VERSION = 2
+
+# name -> (restype, argtypes); must match every prototype of include/adalog_hip.h, type for type (tests/test_abi.py checks that)
 SIGNATURES = {
     "adalog_abi_version": (i32, []),
     "adalog_last_error": (C.c_char_p, []),
     "adalog_last_kernel": (C.c_char_p, []),
     "adalog_uniform_fake_quant_f32": (i32, [p, p, p, i64, p, p, i64, i64, i32, i32, p]),
-    "adalog_log_fake_quant_f32": (i32, [p, p, p, i64, p, p, p, p, i32, p, i32, i32, p]),
     "adalog_pack_uniform": (i32, [p, i64, i64, i64, i64, i64, i64, p, p, i64, i64, i64, i64, i64, i32, i32, p, i64, p, i32, p]),
-    "adalog_pack_adalog_bf16": (i32, [p, i64, i64, i64, i64, i64, i64, p, p, i64, i64, i64, i64, i32, p, p, i32, p, i64, i32, p]),
     "adalog_pack_raw_f32": (i32, [p, i64, i64, i64, i64, i64, i64, p, i64, p]),
     "adalog_pack_split3_bf16": (i32, [p, i64, i64, i64, i64, i64, i64, p, i64, p]),
     "adalog_gemm_score": (i32, [i32, p, p, i64, i64, i64, i64, i32, i32, i64, i64, i32, i32, i32, p, i64, i64, i64, i32,
@@ -59,17 +60,16 @@ SIGNATURES = {
     "adalog_topk_next": (i32, [p, i32, i32, i32, p, p, p, i32, p, p, i32, f32, p, p, p, p, p]),
     "adalog_topk_next_tail": (i32, [p, i32, i32, p, p, p]),
     "adalog_finish_topk_next_tail": (i32, [p, p, i32, i32, i32, i32, i32, i32, i32, i32, i32, f64, p, i64, p, p]),
-    "adalog_gemm_out_gen_ex": (i32, [p, i64, i64, i32, p, p, i64, i32, p, i64, i32, i32, i64, i32, i32, p, i64, f32, p, i64, i64, p, i64, i64,
-                                     p, p, i64, i64, p]),
+    "adalog_gemm_out_gen": (i32, [p, i64, i64, i32, p, p, i64, i32, p, i64, i32, i32, i64, i32, i32, p, i64, f32, p, i64, i64, p, i64, i64,
+                                  p, p, i64, i64, p]),
     "adalog_gemm_out_ex": (i32, [i32, p, p, i64, i64, i32, i32, i64, i32, i32, p, i64, f32, p, i64, i64, p, i64, i64, p, p, i64, i64, i32,
                                  i64, p]),
-    "adalog_pack_adalog_bf16_pre": (i32, [p, i64, i64, i64, i64, i64, i64, p, p, i64, i64, i64, i64, i32, p, p, i32, p, i64, i32, i32, p]),
-    "adalog_log_fake_quant_f32_pre": (i32, [p, p, p, i64, p, p, p, p, i32, p, i32, i32, i32, p]),
-    "adalog_log_fq_backward_pre": (i32, [p, p, p, p, i64, p, p, i32, p, i32, p, p, i32, p]),
+    "adalog_pack_adalog_bf16": (i32, [p, i64, i64, i64, i64, i64, i64, p, p, i64, i64, i64, i64, i32, p, p, i32, p, i64, i32, i32, p]),
+    "adalog_log_fake_quant_f32": (i32, [p, p, p, i64, p, p, p, p, i32, p, i32, i32, i32, p]),
+    "adalog_log_fq_backward": (i32, [p, p, p, p, i64, p, p, i32, p, i32, p, p, i32, p]),
     "adalog_brecq_prepare": (i32, [p, p, p, p, p, i64, i64, i64, p, p, i32, p]),
     "adalog_softmax_adalog_pack_bf16": (i32, [p, i64, i32, f32, p, p, i32, p, p, i64, p]),
-    "adalog_attn_split_pack": (i32, [p, i32, i32, i32, p, p, i32, p, p, i32, p, p, i32, i32, p, p, p, i64, p]),
-    "adalog_attn_split_pack_ex": (i32, [p, i32, i32, i32, i32, f32, p, p, i32, p, p, i32, p, p, i32, i32, p, p, p, i64, p]),
+    "adalog_attn_split_pack": (i32, [p, i32, i32, i32, i32, f32, p, p, i32, p, p, i32, p, p, i32, i32, p, p, p, i64, p]),
     "adalog_softmax_bias_adalog_pack_bf16": (i32, [p, i64, i32, i32, p, p, p, i32, p, p, i32, p, p, i64, p]),
     "adalog_gemm_out_gen_rows": (i32, [p, i64, i32, p, p, i32, p, i32, i32, i64, p, f32, p, i64, p, i64, p, p, i64, p, p, i64, p]),
     "adalog_attn_core_supported": (i32, [i32, i32]),
@@ -77,8 +77,6 @@ SIGNATURES = {
     "adalog_softmax_adalog_pack_long_bf16": (i32, [p, i64, i32, f32, p, p, i32, p, p, i64, p]),
     "adalog_attn_core_long_supported": (i32, [i32, i32]),
     "adalog_attn_core_long": (i32, [p, p, p, i64, i32, i32, i32, i32, i64, p, p, p, i32, f32, p, p, i32, p, f32, p, p]),
-    "adalog_gemm_out_gen": (i32, [p, i64, i64, i32, p, p, i64, i32, p, i64, i32, i32, i64, i32, i32, p, i64, f32, p, i64, i64, p, i64, i64,
-                            p, i64, i64, p]),
     "adalog_sort_workspace_bytes": (i64, [i64, i64, i32]),
     "adalog_sort_f32": (i32, [p, i64, i64, p, p, p, i64, p]),
     "adalog_gram_amax": (i32, [p, i32, i32, p, p, p]),
@@ -113,7 +111,6 @@ SIGNATURES = {
     "adalog_scaled_softmax_backward": (i32, [p, p, p, i64, i32, f32, p]),
     "adalog_uniform_fq_backward_blocks": (i32, [i64, i64, i64]),
     "adalog_uniform_fq_backward": (i32, [p, p, p, i64, p, p, i64, i64, i32, i32, p, p, p, p]),
-    "adalog_log_fq_backward": (i32, [p, p, p, p, i64, p, p, i32, p, i32, p, p, p]),
     "adalog_uniform_fake_quant_drop_f32": (i32, [p, p, i64, p, p, i64, i64, i32, i32, f32, p, i32, p]),
     "adalog_uniform_fq_backward_drop": (i32, [p, p, p, i64, p, p, i64, i64, i32, i32, p, p, p, f32, p, i32, p]),
     "adalog_log_fake_quant_drop_f32": (i32, [p, p, i64, p, p, i32, p, i32, i32, f32, p, i32, p]),
@@ -172,6 +169,14 @@ class AdalogHipError(RuntimeError):
     pass
 
 
+def check_abi_version(lib):
+    """A library of another ABI version takes other argument lists under the same names: refuse it before any call."""
+    got = lib.adalog_abi_version()
+    if got != ABI_VERSION:
+        raise AdalogHipError(f"{LIB_PATH} reports ABI version {got}, this package binds version {ABI_VERSION}: rebuild the library "
+                             "(`make -C adalog_amd/csrc`) or point ADALOG_LIB at a build of this source tree")
+
+
 def load():
     """Load the shared library (once).  Raises if it has not been built -- there is no CPU fallback."""
     global _lib
@@ -181,6 +186,7 @@ def load():
                 f"{LIB_PATH} not found: build the HIP kernels first (python -c 'import __graft_entry__ as g; g.build()' "
                 "or `make -C adalog_amd/csrc`).  The AdaLog MI355X path has no CPU fallback.")
         lib = C.CDLL(LIB_PATH)
+        check_abi_version(lib)
         for name, (res, args) in SIGNATURES.items():
             fn = getattr(lib, name)
             fn.restype = res

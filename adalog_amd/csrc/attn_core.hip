@@ -1,6 +1,6 @@
 // quant_forward of the attention core in ONE launch (reference utils/wrap_net.py:23-30 / :41-51 with both products in quant_forward,
 // quant_layers/matmul.py:43-45): q . k^T on the int8 MFMA, scale (or relative-position bias + shift mask), softmax, the post-softmax
-// AdaLog quantiser and softmax . v on the bf16 MFMA, from the packed operands of adalog_attn_split_pack(_ex) to the heads-last
+// AdaLog quantiser and softmax . v on the bf16 MFMA, from the packed operands of adalog_attn_split_pack to the heads-last
 // output [B][N][H][D].  The scores and the quantised probabilities live in LDS only: what gemm_out(I8) -> softmax_(bias_)adalog_pack
 // -> gemm_out(BF16, heads_last) hand from launch to launch through HBM (deit_small, 32 images: 49 MB written and read per block).
 //

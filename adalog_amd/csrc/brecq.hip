@@ -1168,14 +1168,6 @@ extern "C" int adalog_uniform_fq_backward_drop(const float* gy, const float* x, 
 }
 
 // gscale: [1] optional; workspace: 1024 floats
-extern "C" int adalog_log_fq_backward_pre(const float* gy, const float* x, const float* y, float* gx, int64_t n,
-                                          const float* scale, const int64_t* q, int n_bits, const float* shift, int sub_shift,
-                                          float* gscale, float* workspace, int pre, void* stream);
-extern "C" int adalog_log_fq_backward(const float* gy, const float* x, const float* y, float* gx, int64_t n,
-                                      const float* scale, const int64_t* q, int n_bits, const float* shift, int sub_shift,
-                                      float* gscale, float* workspace, void* stream) {
-    return adalog_log_fq_backward_pre(gy, x, y, gx, n, scale, q, n_bits, shift, sub_shift, gscale, workspace, 0, stream);
-}
 static int log_fq_backward(const float* gy, const float* x, const float* y, float* gx, int64_t n, const float* scale, const int64_t* q,
                            int n_bits, const float* shift, int sub_shift, float* gscale, float* workspace, int pre,
                            const DropArgs* drop, void* stream) {
@@ -1195,10 +1187,10 @@ static int log_fq_backward(const float* gy, const float* x, const float* y, floa
     ADALOG_LAUNCH_CHECK("adalog_log_fq_backward");
     return 0;
 }
-// pre = 1: backward of adalog_log_fake_quant_f32_pre -- x is the GELU's INPUT; gx = dL/dx through the quantiser (STE) and the GELU
-extern "C" int adalog_log_fq_backward_pre(const float* gy, const float* x, const float* y, float* gx, int64_t n,
-                                          const float* scale, const int64_t* q, int n_bits, const float* shift, int sub_shift,
-                                          float* gscale, float* workspace, int pre, void* stream) {
+// pre = 1: backward of adalog_log_fake_quant_f32 with pre = 1 -- x is the GELU's INPUT; gx = dL/dx through the quantiser (STE) and the GELU
+extern "C" int adalog_log_fq_backward(const float* gy, const float* x, const float* y, float* gx, int64_t n,
+                                      const float* scale, const int64_t* q, int n_bits, const float* shift, int sub_shift,
+                                      float* gscale, float* workspace, int pre, void* stream) {
     return log_fq_backward(gy, x, y, gx, n, scale, q, n_bits, shift, sub_shift, gscale, workspace, pre, nullptr, stream);
 }
 // The gradients of adalog_log_fake_quant_drop_f32 (same p / drop_state / drop_stream): gx = gy (times GELU'(x) when pre) where

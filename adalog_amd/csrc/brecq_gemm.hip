@@ -805,10 +805,6 @@ static int bq_run(const float* A, int64_t lda, int transA, const void* B, int64_
 // Two-level groups (adalog_gemm_f32x3_g2): group g = go * Gi + gi sits at gi * s?g + go * s?o in each operand -- a [B][H] batch whose
 //   two strides do not collapse, e.g. the softmax.v product writing its [B][N][H][D] result in place (no transposed copy before
 //   the projection layer).  Gi <= 0 or Gi >= G: one level (the outer strides are ignored).
-extern "C" int adalog_gemm_f32x3_g2(const float* A, int64_t lda, int transA, const float* B, int64_t ldb, int transB, float* C,
-                                    int64_t ldc, int M, int N, int K, int G, int64_t sAg, int64_t sBg, int64_t sCg, int Gi,
-                                    int64_t sAo, int64_t sBo, int64_t sCo, const float* bias, float alpha, const float* alpha_dev,
-                                    int allow_split, int exactA, int exactB, float* workspace, void* stream);
 // ... + addend[g][m][n] (laid out like C; may be null): added in the split product's reduction pass (no extra launch) or, for a product
 // that is not split, by a pass of its own -- x + fc2(...) of a transformer block inside a BRECQ iteration.
 extern "C" int adalog_gemm_f32x3_add(const float* A, int64_t lda, int transA, const float* B, int64_t ldb, int transB, float* C,

@@ -15,8 +15,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 def build(verbose=False):
     src = os.path.join(HERE, "torch_ops.cpp")
     out = os.path.join(HERE, "libadalog_torch.so")
-    dep = os.path.join(HERE, "libadalog_hip.so")
-    if os.path.exists(out) and os.path.getmtime(out) >= max(os.path.getmtime(src), os.path.getmtime(dep)):
+    deps = [src, os.path.join(HERE, "libadalog_hip.so"), os.path.join(HERE, "..", "..", "include", "adalog_hip.h")]
+    if os.path.exists(out) and os.path.getmtime(out) >= max(os.path.getmtime(d) for d in deps):
         return out
     tlib = os.path.join(os.path.dirname(torch.__file__), "lib")
     cmd = ["hipcc", "-x", "c++", "-std=c++17", "-O2", "-fPIC", "-shared", "-D__HIP_PLATFORM_AMD__=1", "-DUSE_ROCM=1",

@@ -6,6 +6,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <type_traits>
+#include "../../include/adalog_hip.h"   // the public C ABI: every definition is compiled against its declaration
 
 #define ADALOG_R 37            // AdaLog fixed denominator r (reference quantizers/logarithm.py:71)
 

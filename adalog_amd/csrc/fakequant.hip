@@ -211,14 +211,6 @@ extern "C" int adalog_uniform_fake_quant_drop_f32(const float* x, float* y, int6
     return uniform_fake_quant(x, y, nullptr, n, scale, zero_point, n_channels, inner, n_bits, symmetric, &d, stream);
 }
 
-extern "C" int adalog_log_fake_quant_f32_pre(const float* x, float* y, uint8_t* bins, int64_t n, const float* scale,
-                                             const int64_t* q, const float* table1, const float* table2, int n_bits,
-                                             const float* shift, int sub_shift, int train_form, int pre, void* stream);
-extern "C" int adalog_log_fake_quant_f32(const float* x, float* y, uint8_t* bins, int64_t n, const float* scale,
-                                         const int64_t* q, const float* table1, const float* table2, int n_bits,
-                                         const float* shift, int sub_shift, int train_form, void* stream) {
-    return adalog_log_fake_quant_f32_pre(x, y, bins, n, scale, q, table1, table2, n_bits, shift, sub_shift, train_form, 0, stream);
-}
 // (drop != null: the QDrop form -- y required, no bins)
 static int log_fake_quant(const float* x, float* y, uint8_t* bins, int64_t n, const float* scale, const int64_t* q, const float* table1,
                           const float* table2, int n_bits, const float* shift, int sub_shift, int train_form, int pre,
@@ -248,14 +240,14 @@ static int log_fake_quant(const float* x, float* y, uint8_t* bins, int64_t n, co
 }
 
 // pre = 1: the quantiser's input is GELU(x) (erf form), applied on the fly: a BRECQ iteration's fc2 input quantiser reads fc1's output
-// (the GELU pass and its stored result disappear; adalog_log_fq_backward_pre is the matching backward)
-extern "C" int adalog_log_fake_quant_f32_pre(const float* x, float* y, uint8_t* bins, int64_t n, const float* scale,
-                                             const int64_t* q, const float* table1, const float* table2, int n_bits,
-                                             const float* shift, int sub_shift, int train_form, int pre, void* stream) {
+// (the GELU pass and its stored result disappear; adalog_log_fq_backward with pre = 1 is the matching backward)
+extern "C" int adalog_log_fake_quant_f32(const float* x, float* y, uint8_t* bins, int64_t n, const float* scale,
+                                         const int64_t* q, const float* table1, const float* table2, int n_bits,
+                                         const float* shift, int sub_shift, int train_form, int pre, void* stream) {
     return log_fake_quant(x, y, bins, n, scale, q, table1, table2, n_bits, shift, sub_shift, train_form, pre, nullptr, stream);
 }
 
-// QDrop form of the TRAINING form of adalog_log_fake_quant_f32_pre: y[e] = u_e < p ? fq(x[e]) : (pre ? GELU(x[e]) : x[e])
+// QDrop form of the TRAINING form of adalog_log_fake_quant_f32: y[e] = u_e < p ? fq(x[e]) : (pre ? GELU(x[e]) : x[e])
 // (drop_state / drop_stream as for adalog_uniform_fake_quant_drop_f32).
 extern "C" int adalog_log_fake_quant_drop_f32(const float* x, float* y, int64_t n, const float* scale, const int64_t* q, int n_bits,
                                               const float* shift, int sub_shift, int pre, float p, const int32_t* drop_state,

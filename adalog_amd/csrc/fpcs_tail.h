@@ -15,21 +15,9 @@
 #pragma once
 #include "common.h"
 
-// the C-ABI form of the arguments (include/adalog_hip.h declares the same struct)
-extern "C" {
-typedef struct adalog_fpcs_tail {
-    int32_t k, new_cnt, has_clamp;
-    float clamp_min;
-    const float* scale; const float* zp; const float* third;    // the grid that was scored: [P][cols] (zp / third may be null)
-    const float* lin;                                           // linspace(0, 1, new_cnt) (new_cnt > 0)
-    const float* delta_in; float* delta_out;                    // [cols]: spacing read / spacing / (new_cnt - 0.5) written; may alias
-    float* out_scale; float* out_zp; float* out_third;          // [k * new_cnt][cols], or the committed winner [cols] (new_cnt == 0)
-} adalog_fpcs_tail;
-}
-
 namespace fpcs {
 
-typedef adalog_fpcs_tail Tail;
+typedef adalog_fpcs_tail Tail;   // the C-ABI form of the arguments (include/adalog_hip.h, through common.h)
 
 // host-side check shared by the entry points that take a tail
 static inline const char* tail_problem(const Tail* t, int P) {

@@ -677,18 +677,8 @@ extern "C" int adalog_gemm_out_ex(int dtype, const void* A, const void* B, int64
 // x fp32 [G][M][ldx] (groups sxg apart, K valid, K % 16 == 0), (a_scale, a_zp)[gh * a_pg] its per-tensor (a_pg = 0) / per-head
 // quantiser (gh = g % gmod), B the packed int8 operand [G][N][Kp] (adalog_pack_uniform).  Same result, bit for bit, as
 // adalog_pack_uniform(x) + adalog_gemm_score(out): the activation is read once as fp32 instead of written and re-read as int8, and
-// one launch per layer disappears.
-extern "C" int adalog_gemm_out_gen_ex(const float* x, int64_t ldx, int64_t sxg, int K, const float* a_scale, const float* a_zp, int64_t a_pg,
-                                      int n_bits, const void* B, int64_t sBg, int M, int N, int64_t Kp, int G, int gmod, const float* sa,
-                                      int64_t sa_g, float sa_mul, const float* sb, int64_t sb_g, int64_t sb_n, const float* bias,
-                                      int64_t bi_g, int64_t bi_n, const float* addend, float* out, int64_t ldo, int64_t sOg, void* stream);
-extern "C" int adalog_gemm_out_gen(const float* x, int64_t ldx, int64_t sxg, int K, const float* a_scale, const float* a_zp, int64_t a_pg,
-                                   int n_bits, const void* B, int64_t sBg, int M, int N, int64_t Kp, int G, int gmod, const float* sa,
-                                   int64_t sa_g, float sa_mul, const float* sb, int64_t sb_g, int64_t sb_n, const float* bias,
-                                   int64_t bi_g, int64_t bi_n, float* out, int64_t ldo, int64_t sOg, void* stream) {
-    return adalog_gemm_out_gen_ex(x, ldx, sxg, K, a_scale, a_zp, a_pg, n_bits, B, sBg, M, N, Kp, G, gmod, sa, sa_g, sa_mul, sb, sb_g, sb_n,
-                                  bias, bi_g, bi_n, nullptr, out, ldo, sOg, stream);
-}
+// one launch per layer disappears.  adalog_gemm_out_gen below is the entry point; its relatives share gemm_out_gen_impl.
+
 // The A side of adalog_gemm_out_gen and its relatives: the fp32 activation and its quantiser, the row maps (null = identity)
 struct MmGenA { const float* x; int64_t ldx, sxg; int K; const float *a_scale, *a_zp; int64_t a_pg; int n_bits; const int *a_rows, *o_rows; int64_t period; };
 
@@ -731,11 +721,11 @@ static int gemm_out_gen_impl(const MmCall& c, const MmGenA& g) {
     return 0;
 }
 
-// ... + addend[g][m][n] (same strides as out): the residual stream added in the epilogue (x + proj(...) of a transformer block)
-extern "C" int adalog_gemm_out_gen_ex(const float* x, int64_t ldx, int64_t sxg, int K, const float* a_scale, const float* a_zp, int64_t a_pg,
-                                      int n_bits, const void* B, int64_t sBg, int M, int N, int64_t Kp, int G, int gmod, const float* sa,
-                                      int64_t sa_g, float sa_mul, const float* sb, int64_t sb_g, int64_t sb_n, const float* bias,
-                                      int64_t bi_g, int64_t bi_n, const float* addend, float* out, int64_t ldo, int64_t sOg, void* stream) {
+// addend[g][m][n] (same strides as out; may be null): the residual stream added in the epilogue (x + proj(...) of a transformer block)
+extern "C" int adalog_gemm_out_gen(const float* x, int64_t ldx, int64_t sxg, int K, const float* a_scale, const float* a_zp, int64_t a_pg,
+                                   int n_bits, const void* B, int64_t sBg, int M, int N, int64_t Kp, int G, int gmod, const float* sa,
+                                   int64_t sa_g, float sa_mul, const float* sb, int64_t sb_g, int64_t sb_n, const float* bias,
+                                   int64_t bi_g, int64_t bi_n, const float* addend, float* out, int64_t ldo, int64_t sOg, void* stream) {
     const MmOutEx ox{addend, 0, 0};
     const MmGenA g{x, ldx, sxg, K, a_scale, a_zp, a_pg, n_bits, nullptr, nullptr, 1};
     MmCall c{};
@@ -851,10 +841,6 @@ extern "C" int adalog_gemm_score_gen_ok(int dtype, int M, int N, int G, int gmod
 //   s_w[o] * s_p * sum_k Wq[o][k] * (clamp(rne(x[t][k] / s_p) + z_p, 0, 2^bits - 1) - z_p))^2
 // Wp: packed weight image (q_w - z_w) [M][Kp] int8 (dtype 0) or fp8 e4m3 (dtype 3); x: fp32 [T][ldx] (K valid); ref: raw_out
 // [T][M]; scale / zp: the P (64, 128 or 256) per-tensor candidates; row_scale [M] = s_w, row_bias [M] = bias (or null).
-extern "C" int adalog_finish_scores(const float* partial, float* scores, int MT, int N, int Npad, int C, int G, int gmod,
-                                    int keep_h, int keep_n, int cand_inner, double norm, void* workspace,
-                                    int64_t workspace_bytes, void* stream);
-
 static Layout gen_layout(int dtype, int M, int64_t T, int K, int64_t Kp, int P) {
     Layout L{};
     if (!(dtype == 0 || dtype == 3) || !(P == 64 || P == 128 || P == 256) || T < 1 || T * P >= ((int64_t)1 << 31) || K < 16 || K % 16 != 0 ||
@@ -1030,8 +1016,6 @@ extern "C" int adalog_finish_scores(const float* partial, float* scores, int MT,
 // finish + top-k + next grid in one launch where the layout allows it (see gemm_finish.inc); otherwise adalog_finish_scores
 // followed by adalog_topk_next.  Arguments: those of adalog_finish_scores, then those of adalog_topk_next (scores [C][cols],
 // cols = (keep_h ? gmod : 1) * (keep_n ? N : 1)).  Single-GPU only: with several ranks the scores are all-reduced between the two.
-extern "C" int adalog_topk_next_tail(const float* scores, int P, int cols, const adalog_fpcs_tail* tail, int* idx_out, void* stream);
-
 extern "C" int adalog_finish_topk_next_tail(const float* partial, float* scores, int MT, int N, int Npad, int C, int G, int gmod,
                                             int keep_h, int keep_n, int cand_inner, double norm, void* workspace, int64_t workspace_bytes,
                                             const adalog_fpcs_tail* tail, void* stream) {

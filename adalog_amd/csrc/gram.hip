@@ -852,8 +852,6 @@ extern "C" int adalog_gram_score_w(const float* W, int O, int K, int64_t ldw, co
     return 0;
 }
 
-extern "C" int adalog_topk_next_tail(const float* scores, int P, int cols, const adalog_fpcs_tail* tail, int* idx_out, void* stream);
-
 // adalog_gram_score_w followed by the FPCS step's tail (`tail` may be null).  The tail is a SECOND launch here (adalog_topk_next_tail):
 // run inside k_gram_score -- a ticket per output row, the wave / workgroup storing a row's last block ranks it -- it cost 25 us per
 // launch (agent-scope ticket round trips of ~2 us per pass, then ~2 rows of tails at the end of every workgroup) against the 11 us of

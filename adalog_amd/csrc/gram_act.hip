@@ -41,11 +41,6 @@
 #include <type_traits>
 #include <utility>
 
-extern "C" int64_t adalog_sort_workspace_bytes(int64_t S, int64_t n, int with_perm);
-extern "C" int adalog_sort_f32(const float* x, int64_t S, int64_t n, float* sorted, unsigned int* perm, void* workspace,
-                               int64_t workspace_bytes, void* stream);
-extern "C" int adalog_topk_next_tail(const float* scores, int P, int cols, const adalog_fpcs_tail* tail, int* idx_out, void* stream);
-
 namespace {
 
 typedef int v4i __attribute__((ext_vector_type(4)));

@@ -772,24 +772,13 @@ extern "C" int adalog_pack_uniform(const float* x, int64_t G, int64_t R, int64_t
     return 0;
 }
 
-extern "C" int adalog_pack_adalog_bf16_pre(const float* x, int64_t G, int64_t R, int64_t K, int64_t sxg, int64_t sxr,
-                                           int64_t sxk, const float* scale, const float* qv, int64_t C, int64_t pc,
-                                           int64_t gmod, int64_t pg, int n_bits, const float* mant37, const float* shift,
-                                           int clamp_u, void* out, int64_t Kp, int c_inner, int pre, void* stream);
-extern "C" int adalog_pack_adalog_bf16(const float* x, int64_t G, int64_t R, int64_t K, int64_t sxg, int64_t sxr,
-                                       int64_t sxk, const float* scale, const float* qv, int64_t C, int64_t pc,
-                                       int64_t gmod, int64_t pg, int n_bits, const float* mant37, const float* shift,
-                                       int clamp_u, void* out, int64_t Kp, int c_inner, void* stream) {
-    return adalog_pack_adalog_bf16_pre(x, G, R, K, sxg, sxr, sxk, scale, qv, C, pc, gmod, pg, n_bits, mant37, shift, clamp_u, out, Kp,
-                                       c_inner, 0, stream);
-}
 // pre = 1: the operand is GELU(x) -- the activation function between fc1 and fc2 (reference timm Mlp / quant_layers/linear.py:770-796
 // quant_forward) applied in the packer's loader, so that quant_forward of the MLP runs no separate GELU pass.  Per-tensor scale, unit
 // stride along K only (the fast kernel); anything else is refused.
-extern "C" int adalog_pack_adalog_bf16_pre(const float* x, int64_t G, int64_t R, int64_t K, int64_t sxg, int64_t sxr,
-                                           int64_t sxk, const float* scale, const float* qv, int64_t C, int64_t pc,
-                                           int64_t gmod, int64_t pg, int n_bits, const float* mant37, const float* shift,
-                                           int clamp_u, void* out, int64_t Kp, int c_inner, int pre, void* stream) {
+extern "C" int adalog_pack_adalog_bf16(const float* x, int64_t G, int64_t R, int64_t K, int64_t sxg, int64_t sxr,
+                                       int64_t sxk, const float* scale, const float* qv, int64_t C, int64_t pc,
+                                       int64_t gmod, int64_t pg, int n_bits, const float* mant37, const float* shift,
+                                       int clamp_u, void* out, int64_t Kp, int c_inner, int pre, void* stream) {
     ADALOG_ARG_CHECK(pre == 0 || (pre == 1 && pg == 0 && sxk == 1 && !getenv("ADALOG_PACK_GENERIC")), "pack_adalog: the GELU prologue needs a per-tensor scale and unit K stride");
     ADALOG_ARG_CHECK(x && scale && qv && mant37 && out, "pack_adalog: null pointer");
     ADALOG_ARG_CHECK(G >= 1 && R >= 1 && K >= 1 && C >= 1 && C <= 65535 && gmod >= 1, "pack_adalog: bad sizes");
@@ -951,9 +940,9 @@ extern "C" int adalog_softmax_bias_adalog_pack_bf16(const float* x, int64_t G, i
 // [B][N][3][H][D] (contiguous, 16-byte aligned), D in {16, 32, 48, 64}; (scale, zero point) of the three uniform quantisers per head
 // (pg = 1: [H]) or per tensor (pg = 0); qp, kp int8 [B*H][N][128]; vp bf16 [B*H][D][Np], Np a multiple of 64 covering N.  q_mul != 1:
 // q is multiplied by it (fp32) before its quantiser.  Images beyond grid z's 65535 go in further launches (Swin: B = windows).
-extern "C" int adalog_attn_split_pack_ex(const float* qkv, int B, int N, int H, int D, float q_mul, const float* q_scale, const float* q_zp,
-                                         int q_bits, const float* k_scale, const float* k_zp, int k_bits, const float* v_scale,
-                                         const float* v_zp, int v_bits, int pg, void* qp, void* kp, void* vp, int64_t Np, void* stream) {
+extern "C" int adalog_attn_split_pack(const float* qkv, int B, int N, int H, int D, float q_mul, const float* q_scale, const float* q_zp,
+                                      int q_bits, const float* k_scale, const float* k_zp, int k_bits, const float* v_scale,
+                                      const float* v_zp, int v_bits, int pg, void* qp, void* kp, void* vp, int64_t Np, void* stream) {
     if (B == 0 || N == 0) return 0;
     ADALOG_ARG_CHECK(qkv && q_scale && q_zp && k_scale && k_zp && v_scale && v_zp && qp && kp && vp, "attn_split_pack: null pointer");
     ADALOG_ARG_CHECK(B >= 1 && N >= 1 && H >= 1 && H <= 65535 && Np >= N && Np % 64 == 0, "attn_split_pack: bad sizes (Np: a multiple of 64 covering N)");
@@ -978,12 +967,4 @@ extern "C" int adalog_attn_split_pack_ex(const float* qkv, int B, int N, int H, 
         ADALOG_LAUNCH_CHECK("adalog_attn_split_pack");
     }
     return 0;
-}
-
-// Head dimension 64, no multiplier (the ViT / DeiT block).
-extern "C" int adalog_attn_split_pack(const float* qkv, int B, int N, int H, const float* q_scale, const float* q_zp, int q_bits,
-                                      const float* k_scale, const float* k_zp, int k_bits, const float* v_scale, const float* v_zp,
-                                      int v_bits, int pg, void* qp, void* kp, void* vp, int64_t Np, void* stream) {
-    return adalog_attn_split_pack_ex(qkv, B, N, H, 64, 1.0f, q_scale, q_zp, q_bits, k_scale, k_zp, k_bits, v_scale, v_zp, v_bits, pg, qp, kp,
-                                     vp, Np, stream);
 }

@@ -14,64 +14,7 @@
 #include <string>
 #include <tuple>
 
-extern "C" {
-const char* adalog_last_error(void);
-int adalog_uniform_fake_quant_f32(const float* x, float* y, uint8_t* bins, int64_t n, const float* scale, const float* zp,
-                                  int64_t n_ch, int64_t inner, int n_bits, int sym, void* stream);
-int adalog_log_fake_quant_f32(const float* x, float* y, uint8_t* bins, int64_t n, const float* scale, const int64_t* q,
-                              const float* table1, const float* table2, int n_bits, const float* shift, int sub_shift,
-                              int train_form, void* stream);
-int adalog_log2_shift(const float* x, float* out, int64_t n, float shift, void* stream);
-int adalog_score_act_fused_ok(int M, int64_t T, int K, int64_t Kp, int P, int n_bits);
-int64_t adalog_score_act_fused_workspace_bytes(int64_t T, int64_t Kp);
-int adalog_score_act_fused(const void* Wp, int M, int64_t Kp, const float* x, const float* Lx, int64_t T, int K,
-                           const float* ref, const float* row_scale, const float* row_bias, const float* scale,
-                           const float* qv, int P, int n_bits, const float* mant37, float shift, int clamp_u, float sa_mul,
-                           double norm, void* workspace, int64_t workspace_bytes, float* scores, void* stream);
-int adalog_topk(const float* scores, int P, int cols, int k, int32_t* idx, void* stream);
-int adalog_pack_uniform(const float* x, int64_t G, int64_t R, int64_t K, int64_t sxg, int64_t sxr, int64_t sxk,
-                        const float* scale, const float* zero_point, int64_t C, int64_t pc, int64_t gmod, int64_t pg,
-                        int64_t pr, int n_bits, int out_dtype, void* out, int64_t Kp, int32_t* rowsum, int c_inner,
-                        void* stream);
-int adalog_pack_adalog_bf16(const float* x, int64_t G, int64_t R, int64_t K, int64_t sxg, int64_t sxr, int64_t sxk,
-                            const float* scale, const float* qv, int64_t C, int64_t pc, int64_t gmod, int64_t pg,
-                            int n_bits, const float* mant37, const float* shift, int clamp_u, void* out, int64_t Kp,
-                            int c_inner, void* stream);
-int64_t adalog_gemm_score_layout(int M, int N, int C, int G, int gmod, int ref_div, int reduce_cols, int dtype, int64_t Kp,
-                                 int64_t k_valid, int ref_transposed, int* MT, int* Npad, int* mode);
-int adalog_gemm_score(int dtype, const void* A, const void* B, int64_t sAc, int64_t sAg, int64_t sBc, int64_t sBg, int M, int N,
-                      int64_t Kp, int64_t k_valid, int C, int G, int gmod, const float* ref, int64_t ldr, int64_t sRg,
-                      int64_t ref_cs, int ref_div, const float* sa, int64_t sa_c, int64_t sa_g, float sa_mul, const float* sb,
-                      int64_t sb_c, int64_t sb_g, int64_t sb_n, const float* bias, int64_t bi_c, int64_t bi_g, int64_t bi_n,
-                      const float* row_scale, const float* row_bias, float* partial, int64_t partial_elems, float* out,
-                      int64_t ldo, int64_t sOc, int64_t sOg, int order, int reduce_cols, void* stream);
-int adalog_finish_scores(const float* partial, float* scores, int MT, int N, int Npad, int C, int G, int gmod, int keep_h,
-                         int keep_n, int cand_inner, double norm, void* workspace, int64_t workspace_bytes, void* stream);
-int64_t adalog_finish_workspace_bytes(int MT, int N, int C, int G, int keep_n, int cand_inner);
-int adalog_finish_topk_next(const float* partial, float* scores, int MT, int N, int Npad, int C, int G, int gmod, int keep_h,
-                            int keep_n, int cand_inner, double norm, void* workspace, int64_t workspace_bytes, int k,
-                            const float* scale, const float* zp, const float* third, int new_cnt, const float* lin, float* delta,
-                            int has_clamp, float clamp_min, float* out_scale, float* out_zp, float* out_third, void* stream);
-int adalog_topk_next(const float* scores, int P, int cols, int k, const float* scale, const float* zp, const float* third,
-                     int new_cnt, const float* lin, float* delta, int has_clamp, float clamp_min, float* out_scale,
-                     float* out_zp, float* out_third, int* idx_out, void* stream);
-int adalog_score_w_self(const float* w, int rows, int I, const float* scale, const float* zp, int P, int n_bits,
-                        float* scores, void* stream);
-int adalog_score_a_self(const float* x, int64_t rows, int I, const float* scale, const float* zp, int P, int channel_wise,
-                        int n_bits, double norm, float* partial, int64_t partial_elems, float* scores, void* stream);
-int64_t adalog_score_a_self_partial_elems(int64_t rows, int I, int P);
-int adalog_score_act_gen_ok(int dtype, int M, int64_t T, int K, int64_t Kp, int P);
-int64_t adalog_score_act_gen_workspace_bytes(int dtype, int M, int64_t T, int K, int64_t Kp, int P);
-int adalog_score_act_gen(int dtype, const void* Wp, int M, int64_t Kp, const float* x, int64_t T, int K, int64_t ldx,
-                         const float* scale, const float* zp, int P, int n_bits, const float* ref, const float* row_scale,
-                         const float* row_bias, double norm, void* workspace, int64_t workspace_bytes, float* scores,
-                         void* stream);
-int64_t adalog_sorted_prefix_workspace_bytes(int64_t S, int64_t n);
-int adalog_sorted_prefix_build(const float* x, int64_t S, int64_t n, float* sorted, double* prefix, void* workspace,
-                               int64_t workspace_bytes, void* stream);
-int adalog_score_self_sorted(const float* sorted, const double* prefix, int64_t S, int64_t n, const float* scale,
-                             const float* zp, int P, int n_bits, double norm, float* scores, void* stream);
-}
+#include "../../include/adalog_hip.h"
 
 namespace {
 
@@ -104,7 +47,7 @@ at::Tensor log_fake_quant(const at::Tensor& x, const at::Tensor& scale, const at
     at::Tensor y = at::empty_like(x);
     check(adalog_log_fake_quant_f32(fptr(x, "x"), y.data_ptr<float>(), nullptr, x.numel(), fptr(scale, "scale"),
                                     q.data_ptr<int64_t>(), fptr(table1, "table1"), fptr(table2, "table2"), (int)n_bits,
-                                    shift.has_value() ? fptr(*shift, "shift") : nullptr, sub_shift ? 1 : 0, 0, cur_stream()),
+                                    shift.has_value() ? fptr(*shift, "shift") : nullptr, sub_shift ? 1 : 0, 0, 0, cur_stream()),
           "adalog::log_fake_quant");
     return y;
 }
@@ -178,7 +121,7 @@ at::Tensor pack_adalog(const at::Tensor& x3, const at::Tensor& scale, const at::
                                x3.options().dtype(at::kBFloat16));
     check(adalog_pack_adalog_bf16(x3.data_ptr<float>(), G, R, K, x3.stride(0), x3.stride(1), x3.stride(2), fptr(scale, "scale"),
                                   fptr(qv, "qv"), C, pc, gmod, pg, (int)n_bits, fptr(mant37, "mant37"), optf(shift, "shift"),
-                                  clamp_u ? 1 : 0, out.data_ptr(), Kp, c_inner ? 1 : 0, cur_stream()),
+                                  clamp_u ? 1 : 0, out.data_ptr(), Kp, c_inner ? 1 : 0, 0, cur_stream()),
           "adalog::pack_adalog");
     return out;
 }

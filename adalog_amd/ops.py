@@ -105,7 +105,7 @@ def uniform_fake_quant(x, scale, zero_point, n_bits: int, sym: bool = False, wan
 
 def log_fake_quant(x, scale, q, table1, table2, n_bits: int, shift=None, sub_shift: bool = False,
                    train_form: bool = False, want_bins: bool = False, want_y: bool = True, pre_gelu: bool = False):
-    """``pre_gelu``: the quantiser's input is GELU(x) (erf form), applied in the kernel (adalog_log_fake_quant_f32_pre)."""
+    """``pre_gelu``: the quantiser's input is GELU(x) (erf form), applied in the kernel (adalog_log_fake_quant_f32, pre = 1)."""
     x = _f32c(x, "x")
     scale = _f32c(scale, "scale")
     if scale.numel() != 1:
@@ -118,11 +118,11 @@ def log_fake_quant(x, scale, q, table1, table2, n_bits: int, shift=None, sub_shi
     y = torch.empty_like(x) if want_y else None
     bins = torch.empty(x.shape, dtype=torch.uint8, device=x.device) if want_bins else None
     lib = _lib.load()
-    rc = lib.adalog_log_fake_quant_f32_pre(_ptr(x), _ptr(y), _ptr(bins), x.numel(), _ptr(scale), _ptr(q),
-                                           _ptr(None if train_form else _f32c(table1, "table1")),
-                                           _ptr(None if train_form else _f32c(table2, "table2")), int(n_bits),
-                                           _ptr(None if shift is None else _f32c(shift, "shift")), int(bool(sub_shift)),
-                                           int(bool(train_form)), int(bool(pre_gelu)), _stream())
+    rc = lib.adalog_log_fake_quant_f32(_ptr(x), _ptr(y), _ptr(bins), x.numel(), _ptr(scale), _ptr(q),
+                                       _ptr(None if train_form else _f32c(table1, "table1")),
+                                       _ptr(None if train_form else _f32c(table2, "table2")), int(n_bits),
+                                       _ptr(None if shift is None else _f32c(shift, "shift")), int(bool(sub_shift)),
+                                       int(bool(train_form)), int(bool(pre_gelu)), _stream())
     _lib.check(rc, "adalog_log_fake_quant_f32")
     return (y, bins) if want_bins else y
 
@@ -232,7 +232,7 @@ def pack_uniform(x3, scale, zero_point, C: int, pc: int, gmod: int, pg: int, pr:
 
 def pack_adalog(x3, scale, qv, C: int, pc: int, gmod: int, pg: int, n_bits: int, mant37, shift=None,
                 clamp_u: bool = True, c_inner: bool = False, k_align: int = 128, pre_gelu: bool = False):
-    """``pre_gelu``: the operand is GELU(x3) (erf form) -- applied in the packer's loader (adalog_pack_adalog_bf16_pre)."""
+    """``pre_gelu``: the operand is GELU(x3) (erf form) -- applied in the packer's loader (adalog_pack_adalog_bf16, pre = 1)."""
     G, R, K, sg, sr, sk = _view3(x3)
     Kp = pad_k(K, BF16, k_align)
     scale, qv, mant37 = _f32c(scale, "scale"), _f32c(qv, "qv"), _f32c(mant37, "mant37")
@@ -242,10 +242,10 @@ def pack_adalog(x3, scale, qv, C: int, pc: int, gmod: int, pg: int, n_bits: int,
                    bool(c_inner))
     else:
         out = torch.empty((1, G, R * C, Kp) if c_inner else (C, G, R, Kp), dtype=torch.bfloat16, device=x3.device)
-        rc = _lib.load().adalog_pack_adalog_bf16_pre(x3.data_ptr(), G, R, K, sg, sr, sk, _ptr(scale), _ptr(qv), C, pc, gmod, pg, int(n_bits),
-                                                    _ptr(mant37), _ptr(shift), int(bool(clamp_u)), out.data_ptr(), Kp, int(bool(c_inner)),
-                                                    int(bool(pre_gelu)), _stream())
-        _lib.check(rc, "adalog_pack_adalog_bf16_pre")
+        rc = _lib.load().adalog_pack_adalog_bf16(x3.data_ptr(), G, R, K, sg, sr, sk, _ptr(scale), _ptr(qv), C, pc, gmod, pg, int(n_bits),
+                                                _ptr(mant37), _ptr(shift), int(bool(clamp_u)), out.data_ptr(), Kp, int(bool(c_inner)),
+                                                int(bool(pre_gelu)), _stream())
+        _lib.check(rc, "adalog_pack_adalog_bf16")
     out.k_valid = K
     return out
 
@@ -359,7 +359,7 @@ def _layout(M, n_cols, c_grid, G, gmod, ref_div, reduce_cols, dtype, Kp, k_valid
 
 class FpcsTail:
     """The tail of one FPCS step (reference linear.py:483-523: top-k of the scores, then the next 16 x 8 grid around the survivors or
-    the committed winner) as ARGUMENTS (adalog_fpcs_tail, csrc/fpcs_tail.h), so that a kernel producing final scores runs it in its own
+    the committed winner) as ARGUMENTS (adalog_fpcs_tail of include/adalog_hip.h; csrc/fpcs_tail.h holds the device code), so that a kernel producing final scores runs it in its own
     launch, or adalog_topk_next_tail / adalog_finish_topk_next_tail run it.  ``delta_in`` is read, ``delta_out`` written (they may be
     the same tensor): the memoised grid spacing is never modified.  ``out`` (commit step only): write the winner straight into these
     [cols] tensors -- the quantiser's own parameter storage -- instead of fresh ones."""
@@ -702,12 +702,12 @@ def gemm_out_gen(x3, a_scale, a_zp, n_bits: int, B, N: int, gmod: int, sa: Strid
     if addend is not None:                               # the residual stream, added in the epilogue
         addend = _f32c(addend, "addend")
         assert addend.numel() == G * M * N
-    rc = lib.adalog_gemm_out_gen_ex(x3.data_ptr(), x3.stride(1), x3.stride(0), K, a_scale.data_ptr(), a_zp.data_ptr(),
-                                    0 if a_scale.numel() == 1 else 1, int(n_bits), B.data_ptr(), sBg, M, N, Kp, G, gmod,
-                                    sa.t.data_ptr(), sa.g, float(sa_mul), sb.t.data_ptr(), sb.g, sb.n,
-                                    None if bias is None else bias.t.data_ptr(), 0 if bias is None else bias.g,
-                                    0 if bias is None else bias.n, _ptr(addend), out.data_ptr(), N, M * N, _stream())
-    _lib.check(rc, "adalog_gemm_out_gen_ex")
+    rc = lib.adalog_gemm_out_gen(x3.data_ptr(), x3.stride(1), x3.stride(0), K, a_scale.data_ptr(), a_zp.data_ptr(),
+                                 0 if a_scale.numel() == 1 else 1, int(n_bits), B.data_ptr(), sBg, M, N, Kp, G, gmod,
+                                 sa.t.data_ptr(), sa.g, float(sa_mul), sb.t.data_ptr(), sb.g, sb.n,
+                                 None if bias is None else bias.t.data_ptr(), 0 if bias is None else bias.g,
+                                 0 if bias is None else bias.n, _ptr(addend), out.data_ptr(), N, M * N, _stream())
+    _lib.check(rc, "adalog_gemm_out_gen")
     return out
 
 
@@ -740,9 +740,9 @@ def softmax_adalog_pack_ok(S: int) -> bool:
     return S <= 256 and pad_k(S, BF16) <= 256
 
 
-def _attn_split_pack(c_name: str, qkv, H: int, q_par, k_par, v_par, per_head: bool, D: int, ex_args=()):
-    """attn_split_pack / attn_split_pack_ex: the C entry point ``c_name`` (``ex_args``: what adalog_attn_split_pack_ex takes after H)
-    over qkv fp32 [B, N, 3*H*D] -> qp, kp int8 [1, B*H, N, 128], vp bf16 [1, B*H, D, Np]"""
+def _attn_split_pack(qkv, H: int, q_par, k_par, v_par, per_head: bool, D: int, q_mul: Optional[float]):
+    """attn_split_pack / attn_split_pack_ex: adalog_attn_split_pack over qkv fp32 [B, N, 3*H*D] -> qp, kp int8 [1, B*H, N, 128],
+    vp bf16 [1, B*H, D, Np]"""
     qkv = _f32c(qkv, "qkv")
     B, N, C3 = qkv.shape
     assert D in (16, 32, 48, 64) and C3 == 3 * H * D
@@ -756,9 +756,9 @@ def _attn_split_pack(c_name: str, qkv, H: int, q_par, k_par, v_par, per_head: bo
         assert s_.numel() == z_.numel() == (H if per_head else 1)
         par.append((s_, z_, int(b_)))
     quant_args = [v for s_, z_, b_ in par for v in (s_.data_ptr(), z_.data_ptr(), b_)]
-    rc = getattr(_lib.load(), c_name)(qkv.data_ptr(), B, N, H, *ex_args, *quant_args, 1 if per_head else 0, qp.data_ptr(), kp.data_ptr(),
-                                      vp.data_ptr(), Np, _stream())
-    _lib.check(rc, c_name)
+    rc = _lib.load().adalog_attn_split_pack(qkv.data_ptr(), B, N, H, int(D), 1.0 if q_mul is None else float(q_mul), *quant_args,
+                                            1 if per_head else 0, qp.data_ptr(), kp.data_ptr(), vp.data_ptr(), Np, _stream())
+    _lib.check(rc, "adalog_attn_split_pack")
     qp.k_valid = kp.k_valid = D
     vp.k_valid = N
     return qp, kp, vp
@@ -767,8 +767,8 @@ def _attn_split_pack(c_name: str, qkv, H: int, q_par, k_par, v_par, per_head: bo
 def attn_split_pack(qkv, H: int, q_par, k_par, v_par, per_head: bool):
     """qkv fp32 [B, N, 3*H*64] (the qkv projection's output) -> (qp, kp, vp): the packed operands of q . k^T (int8 [1, B*H, N, 128])
     and of softmax . v's second operand (bf16 [1, B*H, 64, Np], v transposed) through the three uniform input quantisers
-    ((scale, zero_point, n_bits) each; per head or per tensor) in one launch (adalog_attn_split_pack)."""
-    return _attn_split_pack("adalog_attn_split_pack", qkv, H, q_par, k_par, v_par, per_head, 64)
+    ((scale, zero_point, n_bits) each; per head or per tensor) in one launch: attn_split_pack_ex(..., D=64)."""
+    return _attn_split_pack(qkv, H, q_par, k_par, v_par, per_head, 64, None)
 
 
 # Capability flag of the Swin block's fused quant_forward (utils/models.py: SwinTransformerBlock), read like QF_EXTRAS: attn_split_pack_ex,
@@ -779,9 +779,8 @@ QF_SWIN = True
 def attn_split_pack_ex(qkv, H: int, q_par, k_par, v_par, per_head: bool, D: int = 64, q_mul: Optional[float] = None):
     """attn_split_pack for head dimension D in {16, 32, 48, 64} (qkv fp32 [B, N, 3*H*D]): qp, kp int8 [1, B*H, N, 128] (D codes, then
     zeros), vp bf16 [1, B*H, D, Np].  ``q_mul``: q is multiplied by float32(q_mul) before its quantiser -- Swin's q * scale, the product
-    ATen forms (adalog_attn_split_pack_ex).  Any number of images B."""
-    return _attn_split_pack("adalog_attn_split_pack_ex", qkv, H, q_par, k_par, v_par, per_head, D,
-                            (int(D), 1.0 if q_mul is None else float(q_mul)))
+    ATen forms.  Any number of images B."""
+    return _attn_split_pack(qkv, H, q_par, k_par, v_par, per_head, D, q_mul)
 
 
 def softmax_bias_adalog_pack(x3, H: int, table, index, mask, scale, qv, n_bits: int, mant37):
@@ -1602,10 +1601,10 @@ def log_fake_quant_backward(gy, x, y, scale, q, n_bits: int, shift, sub_shift: b
     gx = torch.empty_like(x)
     gs = torch.empty_like(scale)
     ws = torch.empty(1024, dtype=torch.float32, device=x.device)
-    rc = _lib.load().adalog_log_fq_backward_pre(gy.data_ptr(), x.data_ptr(), y.data_ptr(), gx.data_ptr(), x.numel(),
-                                               scale.data_ptr(), q.data_ptr(), int(n_bits),
-                                               _ptr(None if shift is None else _f32c(shift, "shift")), int(bool(sub_shift)),
-                                               gs.data_ptr(), ws.data_ptr(), int(bool(pre_gelu)), _stream())
+    rc = _lib.load().adalog_log_fq_backward(gy.data_ptr(), x.data_ptr(), y.data_ptr(), gx.data_ptr(), x.numel(),
+                                           scale.data_ptr(), q.data_ptr(), int(n_bits),
+                                           _ptr(None if shift is None else _f32c(shift, "shift")), int(bool(sub_shift)),
+                                           gs.data_ptr(), ws.data_ptr(), int(bool(pre_gelu)), _stream())
     _lib.check(rc, "adalog_log_fq_backward")
     return gx, gs
 

@@ -20,6 +20,9 @@
 extern "C" {
 #endif
 
+/* what adalog_abi_version() of a library built from this header returns.  Raise it whenever an existing name's argument list changes:
+ * a binding written against one number must refuse a library that reports another (adalog_amd/_lib.py does, before any call). */
+#define ADALOG_ABI_VERSION 2
 int adalog_abi_version(void);
 const char* adalog_last_error(void);
 /* measurement aid: name of the scoring kernel the last adalog_gemm_score / adalog_score_act_fused call of this thread launched */
@@ -41,10 +44,12 @@ int adalog_uniform_fake_quant_f32(const float* x, float* y, uint8_t* bins, int64
  * k = rne(-log2(clamp((x+shift)/s, 1e-15, 1)) * 37 / q);  y = 2^-table1[k] * table2[k] * s * [k < 2L]  [- shift]
  * scale: [1]; q: int64 [1] (the quantiser's buffer); table1/table2: fp32 [2L] (update_table, logarithm.py:77-81);
  * shift: [1] or NULL; sub_shift: subtract the shift again (bias not yet re-parameterised);
- * train_form: y = 2^(-k*q/37) * s (logarithm.py:88-92, no LUT).  bins: k, or 255 where masked. */
+ * train_form: y = 2^(-k*q/37) * s (logarithm.py:88-92, no LUT).  bins: k, or 255 where masked.
+ * pre = 1: the quantiser reads GELU(x) (x * 0.5 * (1 + erf(x / sqrt 2)), ATen's fp32 expression) in place of x -- fc2's input
+ *   quantiser inside a BRECQ iteration (block_recon.py:116-121) reading fc1's output, with no GELU pass of its own; pre = 0: x. */
 int adalog_log_fake_quant_f32(const float* x, float* y, uint8_t* bins, int64_t n, const float* scale, const int64_t* q,
                               const float* table1, const float* table2, int n_bits, const float* shift, int sub_shift,
-                              int train_form, void* stream);
+                              int train_form, int pre, void* stream);
 
 /* ---- operand packing for the scoring GEMMs (prologue of K7/K8/K11-K15)
  * Input: fp32 view x[g][r][k] with element strides (sxg, sxr, sxk), g < G, r < R, k < K.
@@ -59,7 +64,9 @@ int adalog_log_fake_quant_f32(const float* x, float* y, uint8_t* bins, int64_t n
  * adalog_pack_adalog_bf16: value = m * 2^-t with k = rne(-log2(u)*37/q_c), t = floor(k*q_c/37), m = mant37[(k*q_c) % 37],
  *   u = (x + shift)/s_c [clamped to [1e-15,1] when clamp_u];  masked bins (k >= 2L) -> 0
  *   replaces linear.py:830-836,872-878,913-919 and matmul.py:337-342.  mant37: fp32 [37] integer numerators
- *   round(2^(-j/37) * (4L-2))  (linear.py:750-752).
+ *   round(2^(-j/37) * (4L-2))  (linear.py:750-752).  pre = 1: the operand is GELU(x) (ATen's fp32 erf expression) -- the activation
+ *   between fc1 and fc2 (timm Mlp; reference linear.py:770-796 reads GELU's output) applied in the packer's loader; needs a
+ *   per-tensor scale (pg = 0) and sxk = 1.  pre = 0: x itself.
  * adalog_pack_raw_f32: zero-padded fp32 copy (conv input with qconv_a_bit = 8, conv.py:55-58).
  * adalog_pack_split3_bf16: the same unquantised operand as three bf16 terms, out[row] = [hi(Kt) | mid(Kt) | lo(Kt)] with
  *   hi + mid + lo == x exactly (8 + 8 + 8 mantissa bits; zero past K).  Scored against an exact-integer bf16 candidate operand
@@ -71,7 +78,7 @@ int adalog_pack_uniform(const float* x, int64_t G, int64_t R, int64_t K, int64_t
 int adalog_pack_adalog_bf16(const float* x, int64_t G, int64_t R, int64_t K, int64_t sxg, int64_t sxr, int64_t sxk,
                             const float* scale, const float* qv, int64_t C, int64_t pc, int64_t gmod, int64_t pg,
                             int n_bits, const float* mant37, const float* shift, int clamp_u, void* out, int64_t Kp,
-                            int c_inner, void* stream);
+                            int c_inner, int pre, void* stream);
 int adalog_pack_raw_f32(const float* x, int64_t G, int64_t R, int64_t K, int64_t sxg, int64_t sxr, int64_t sxk, void* out,
                         int64_t Kp, void* stream);
 int adalog_pack_split3_bf16(const float* x, int64_t G, int64_t R, int64_t K, int64_t sxg, int64_t sxr, int64_t sxk, void* out,
@@ -384,20 +391,16 @@ int adalog_score_self_sorted_tail(const float* sorted, const double* prefix, int
 
 /* ---- K15 with the A-side fake quantisation in the GEMM's loader (round 6)      reference linear.py:46-51, matmul.py:43-45
  *   out[g][m][n] = sa[gh * sa_g] * sa_mul * sb[gh * sb_g + n * sb_n] * sum_k (q_a(x[g][m][k]) - z_a) * B[g][n][k] + bias[gh * bi_g + n * bi_n]
+ *                  + addend[g][m][n]
  * x: fp32 [G][M][ldx] (groups sxg elements apart; K valid, K % 16 == 0); (a_scale, a_zp)[gh * a_pg]: its uniform quantiser, per tensor
  * (a_pg = 0) or per head (gh = g % gmod); B: packed int8 [G][N][Kp] (adalog_pack_uniform; sBg bytes between groups, 0 = shared);
- * out fp32 [G][M][ldo] (groups sOg apart).  Bit for bit adalog_pack_uniform(x) + adalog_gemm_score(out = ...), in one launch and
- * without the int8 image of the activation. */
+ * out fp32 [G][M][ldo] (groups sOg apart); addend (may be null; indexed like out): the residual stream of a transformer block added
+ * in the epilogue.  Bit for bit adalog_pack_uniform(x) + adalog_gemm_score(out = ...) (+ a separate add), in one launch and without
+ * the int8 image of the activation. */
 int adalog_gemm_out_gen(const float* x, int64_t ldx, int64_t sxg, int K, const float* a_scale, const float* a_zp, int64_t a_pg, int n_bits,
                         const void* B, int64_t sBg, int M, int N, int64_t Kp, int G, int gmod, const float* sa, int64_t sa_g,
                         float sa_mul, const float* sb, int64_t sb_g, int64_t sb_n, const float* bias, int64_t bi_g, int64_t bi_n,
-                        float* out, int64_t ldo, int64_t sOg, void* stream);
-
-/* ... + addend[g][m][n] (may be null; indexed like out): the residual stream of a transformer block added in the epilogue */
-int adalog_gemm_out_gen_ex(const float* x, int64_t ldx, int64_t sxg, int K, const float* a_scale, const float* a_zp, int64_t a_pg, int n_bits,
-                           const void* B, int64_t sBg, int M, int N, int64_t Kp, int G, int gmod, const float* sa, int64_t sa_g,
-                           float sa_mul, const float* sb, int64_t sb_g, int64_t sb_n, const float* bias, int64_t bi_g, int64_t bi_n,
-                           const float* addend, float* out, int64_t ldo, int64_t sOg, void* stream);
+                        const float* addend, float* out, int64_t ldo, int64_t sOg, void* stream);
 /* K15 from packed operands (dtype 0 = int8, 1 = bf16; A [G][M][Kp], B [G][N][Kp], group strides in elements, 0 = shared) with the
  * same epilogue extras:  out = sa * sa_mul * sb[n] * (A . B^T) + bias[n] + addend.  out_gi > 0: two-level output groups, group g
  * written at (g % out_gi) * sOg + (g / out_gi) * sOo -- softmax . v with out_gi = H, sOg = D, sOo = N * H * D, ldo = H * D writes
@@ -408,49 +411,33 @@ int adalog_gemm_out_ex(int dtype, const void* A, const void* B, int64_t sAg, int
                        void* stream);
 
 /* ---- quant_forward prologues of a transformer block (round 6): the passes between two products folded into the packers
- * adalog_pack_adalog_bf16_pre: adalog_pack_adalog_bf16 of GELU(x) (pre = 1: x * 0.5 * (1 + erf(x / sqrt 2)), ATen's fp32 expression) --
- *   the activation between fc1 and fc2 (timm Mlp; reference linear.py:770-796 reads GELU's output).  Per-tensor scale, sxk = 1.
+ * (the GELU between fc1 and fc2: adalog_pack_adalog_bf16 with pre = 1, above)
  * adalog_softmax_adalog_pack_bf16: (x * mul).softmax(-1) (reference utils/wrap_net.py:26-27), quantised by the post-softmax AdaLog
  *   quantiser (matmul.py:337-343: per-tensor scale, log base 2^(-q/37), u clamped to [1e-15, 1]) into the bf16 operand [rows][Kp]
  *   of softmax . v; the probabilities are never stored.  x fp32 [rows][S] contiguous, S <= Kp <= 256.  ATen's softmax arithmetic,
  *   operation for operation.
- * adalog_attn_split_pack: qkv fp32 [B][N][3][H][64] -> the packed operands of both attention products through their three per-head
- *   (pg = 1) or per-tensor (pg = 0) uniform quantisers: qp, kp int8 [B*H][N][128]; vp bf16 [B*H][64][Np] (v transposed, zero beyond
- *   N; Np a multiple of 64).  Replaces the split / permute copies of wrap_net.py:20-22 and three adalog_pack_uniform launches. */
-int adalog_pack_adalog_bf16_pre(const float* x, int64_t G, int64_t R, int64_t K, int64_t sxg, int64_t sxr, int64_t sxk,
-                                const float* scale, const float* qv, int64_t C, int64_t pc, int64_t gmod, int64_t pg,
-                                int n_bits, const float* mant37, const float* shift, int clamp_u, void* out, int64_t Kp,
-                                int c_inner, int pre, void* stream);
-/* the same prologue in the training-form quantiser of a BRECQ iteration (block_recon.py:116-121 through fc2's input quantiser,
- * logarithm.py:88-92): y = q(GELU(x)) and its backward (x = the GELU's input; gx through the STE and the GELU's derivative) */
-int adalog_log_fake_quant_f32_pre(const float* x, float* y, uint8_t* bins, int64_t n, const float* scale, const int64_t* q,
-                                  const float* table1, const float* table2, int n_bits, const float* shift, int sub_shift,
-                                  int train_form, int pre, void* stream);
-int adalog_log_fq_backward_pre(const float* gy, const float* x, const float* y, float* gx, int64_t n, const float* scale,
-                               const int64_t* q, int n_bits, const float* shift, int sub_shift, float* gscale, float* workspace,
-                               int pre, void* stream);
+ * adalog_attn_split_pack: qkv fp32 [B][N][3][H][D] -> the packed operands of both attention products through their three per-head
+ *   (pg = 1) or per-tensor (pg = 0) uniform quantisers: qp, kp int8 [B*H][N][128] with D codes then zeros; vp bf16 [B*H][D][Np] (v
+ *   transposed, zero beyond N; Np a multiple of 64).  Replaces the split / permute copies of wrap_net.py:20-22 and three
+ *   adalog_pack_uniform launches.  D: the head dimension, 16, 32, 48 or 64 (ViT / DeiT: 64).  q_mul: q is multiplied by it (fp32)
+ *   before its quantiser when q_mul != 1 -- Swin's q * scale (wrap_net.py:41); 1.0f: q as it is.  Any B: images beyond 65535 go in
+ *   further launches. */
 /* what precedes a captured BRECQ iteration's replay (block_recon.py:114-117) in one launch: dst_in[b] = src_in[idx[b]],
  * dst_out[b] = src_out[idx[b]] (rows of row_in / row_out floats, multiples of 4), sched_dev[0..n_sched) = sched_row[0..n_sched) */
 int adalog_brecq_prepare(const float* src_in, const float* src_out, const int64_t* idx, float* dst_in, float* dst_out, int64_t bs,
                          int64_t row_in, int64_t row_out, const float* sched_row, float* sched_dev, int n_sched, void* stream);
 int adalog_softmax_adalog_pack_bf16(const float* x, int64_t rows, int S, float mul, const float* scale, const float* qv, int n_bits,
                                     const float* mant37, void* out, int64_t Kp, void* stream);
-int adalog_attn_split_pack(const float* qkv, int B, int N, int H, const float* q_scale, const float* q_zp, int q_bits,
+int adalog_attn_split_pack(const float* qkv, int B, int N, int H, int D, float q_mul, const float* q_scale, const float* q_zp, int q_bits,
                            const float* k_scale, const float* k_zp, int k_bits, const float* v_scale, const float* v_zp, int v_bits,
                            int pg, void* qp, void* kp, void* vp, int64_t Np, void* stream);
-/* ---- quant_forward of a Swin block (round 7): the window-attention counterparts of the three above
- * adalog_attn_split_pack_ex: adalog_attn_split_pack for head dimension D in {16, 32, 48, 64} (qkv fp32 [B][N][3][H][D]; qp, kp int8
- *   [B*H][N][128] with D codes then zeros; vp bf16 [B*H][D][Np]), q multiplied by q_mul (fp32) first when q_mul != 1 -- Swin's
- *   q * scale (reference utils/wrap_net.py:41).  Any B: images beyond 65535 go in further launches.
+/* ---- quant_forward of a Swin block (round 7): the window-attention counterparts of the softmax packer and adalog_gemm_out_gen
  * adalog_softmax_bias_adalog_pack_bf16: adalog_softmax_adalog_pack_bf16 of (x + bias) + mask instead of x * mul (wrap_net.py:43-49):
  *   x fp32 [G][S][S] (G = windows * H), bias[g][r][c] = table[index[r * S + c] * H + g % H] (relative_position_bias_table fp32, read on
  *   every call; relative_position_index int64 [S][S]), mask fp32 [nW][S][S] of window (g / H) % nW, or null.
- * adalog_gemm_out_gen_rows: adalog_gemm_out_gen_ex (G = 1, per-tensor quantiser) with a row gather of the activation and a row scatter
+ * adalog_gemm_out_gen_rows: adalog_gemm_out_gen (G = 1, per-tensor quantiser) with a row gather of the activation and a row scatter
  *   of out and addend, in periods of L rows: A row r reads x row a_rows[r % L] + (r / L) L, out / addend row o_rows[r % L] + (r / L) L
  *   takes GEMM row r (int32 maps of L entries in [0, L), null = identity; o_rows a permutation).  M a multiple of L. */
-int adalog_attn_split_pack_ex(const float* qkv, int B, int N, int H, int D, float q_mul, const float* q_scale, const float* q_zp, int q_bits,
-                              const float* k_scale, const float* k_zp, int k_bits, const float* v_scale, const float* v_zp, int v_bits,
-                              int pg, void* qp, void* kp, void* vp, int64_t Np, void* stream);
 int adalog_softmax_bias_adalog_pack_bf16(const float* x, int64_t G, int S, int H, const float* table, const int64_t* index,
                                          const float* mask, int nW, const float* scale, const float* qv, int n_bits,
                                          const float* mant37, void* out, int64_t Kp, void* stream);
@@ -461,7 +448,7 @@ int adalog_gemm_out_gen_rows(const float* x, int64_t ldx, int K, const float* a_
 
 /* ---- quant_forward's attention core in one launch (csrc/attn_core.hip): q . k^T (int8 MFMA), scale or relative-position bias +
  * shift mask, softmax, the post-softmax AdaLog quantiser and softmax . v (bf16 MFMA) from the packed operands of
- * adalog_attn_split_pack(_ex); the scores and the quantised probabilities never reach memory.  Bit-identical to
+ * adalog_attn_split_pack; the scores and the quantised probabilities never reach memory.  Bit-identical to
  *   adalog_gemm_score(int8, qp, kp -> out) ; adalog_softmax_(bias_)adalog_pack_bf16 ; adalog_gemm_out_ex(bf16, ., vp, out_gi = H)
  * (reference utils/wrap_net.py:23-30 and :41-51 with both products in quant_forward, quant_layers/matmul.py:43-45).
  * adalog_attn_core: qp, kp int8 [G][N][128] (D codes q - rne(z), then zeros); vp bf16 [G][D][Np] (v transposed, zero beyond N;
@@ -573,7 +560,7 @@ int adalog_unpack_codes(const uint32_t* in, int64_t R, int64_t K, const float* s
  *   channel, or several with inner >= 64 (per-row weights, per-head [N,H,S,C]); several channels with inner < 64 return -1.
  * log_code_hist: out[2^b + 1] (int64) = the count of every bin of K2 (AdaLog / ShiftAdaLog, per-tensor scale[1], q[1] on the device,
  *   shift[1] or NULL), the last entry the masked code (K2's 255).  The bin comes from the device function K2 takes its ``bins``
- *   output from.  pre: the input is GELU(x), as in adalog_log_fake_quant_f32_pre.
+ *   output from.  pre: the input is GELU(x), as in adalog_log_fake_quant_f32.
  * All validate their arguments before touching the device; out is zeroed by the call. */
 int64_t adalog_err_stats_workspace_bytes(int64_t n, int64_t n_channels, int64_t inner);
 int adalog_err_stats_f32(const float* a, const float* b, int64_t n, int64_t n_channels, int64_t inner, double* out,
@@ -591,7 +578,8 @@ int adalog_log_code_hist_f32(const float* x, int64_t n, const float* scale, cons
  *   blocks = adalog_uniform_fq_backward_blocks(n, n_channels, inner).
  * adalog_log_fq_backward: gradients of AdaLog's training form (reference quantizers/logarithm.py:88-92,133-135):
  *   gx = gy * y'/(u*s) inside both clamps, gscale = sum gy*(y'/s - dy/dx * (x+shift)/s), y' = y before the shift
- *   subtraction.  workspace: 1024 floats.
+ *   subtraction.  workspace: 1024 floats.  pre = 1: the backward of adalog_log_fake_quant_f32 with pre = 1 -- x is the GELU's
+ *   input, and gx also goes through the GELU's derivative; pre = 0: the quantiser alone.
  * adalog_adaround: forward (backward = 0): out = (clamp(floor(w/s) + h + zp, 0, 2L-1) - zp) * s with
  *   h = clamp(sigmoid(alpha)*1.2 - 0.1, 0, 1) (soft) or [alpha >= 0] (hard)   (reference quantizers/adaround.py:43-60);
  *   backward = 1: out = d loss / d alpha = gy * s * h'(alpha) * [inside clamp].  w/alpha: [rows][inner], scale/zp: [rows].
@@ -637,7 +625,7 @@ int adalog_uniform_fq_backward(const float* gy, const float* x, float* gx, int64
                                float* gscale, float* gzp, float* workspace, void* stream);
 int adalog_log_fq_backward(const float* gy, const float* x, const float* y, float* gx, int64_t n, const float* scale,
                            const int64_t* q, int n_bits, const float* shift, int sub_shift, float* gscale, float* workspace,
-                           void* stream);
+                           int pre, void* stream);
 /* QDrop (Wei et al., ICLR 2022) forms of the training-form quantisers above, for BRECQ iterations: element e (linear index in the
  *   quantiser's output, storage order) keeps its fake-quantised value when u_e < p and takes the quantiser's input otherwise
  *   (GELU(x) when pre; x itself for the shift variants); a dropped element passes its gradient through (times GELU'(x) when pre)

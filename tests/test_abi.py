@@ -8,10 +8,14 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def header_functions():
+def header_source():
+    """include/adalog_hip.h without its comments"""
     src = open(os.path.join(ROOT, "include", "adalog_hip.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(adalog_[a-z0-9_]+)\s*\(", src)))
+    return re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+
+
+def header_functions():
+    return sorted(set(re.findall(r"\b(adalog_[a-z0-9_]+)\s*\(", header_source())))
 
 
 def test_header_lists_functions():
@@ -29,7 +33,84 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, name), f"{name} declared in include/adalog_hip.h but not exported"
         assert name in _lib.SIGNATURES, f"{name} has no ctypes signature"
     assert set(_lib.SIGNATURES) == set(header_functions())
-    assert lib.adalog_abi_version() == 1
+    assert lib.adalog_abi_version() == 2
+
+
+def header_prototypes():
+    """name -> (ctypes restype, [ctypes argtypes]) of every prototype in the header; a type the map does not know raises"""
+    import ctypes as C
+    scalar = {"int": C.c_int, "int32_t": C.c_int, "int64_t": C.c_int64, "float": C.c_float, "double": C.c_double}
+
+    def ctype(decl, ret=False):
+        if "*" in decl:
+            return C.c_char_p if ret and decl.replace(" ", "") == "constchar*" else C.c_void_p
+        assert decl in scalar, f"type {decl!r} of the header has no ctypes counterpart in this test"
+        return scalar[decl]
+
+    src = re.sub(r"typedef struct \w+ \{.*?\} \w+;", "", header_source(), flags=re.S)
+    src = re.sub(r'^\s*(#.*|extern "C" \{|\})\s*$', "", src, flags=re.M)
+    protos = {}
+    for stmt in filter(None, (s.strip() for s in src.split(";"))):
+        m = re.fullmatch(r"(.*?)\b(adalog_\w+)\s*\((.*)\)", stmt, flags=re.S)
+        assert m, f"not a prototype: {stmt!r}"
+        params = [" ".join(a.split()) for a in m.group(3).split(",")]
+        # a parameter is "<type> <name>", its type everything in front of the name; "void" alone: no parameters
+        args = [] if params == ["void"] else [ctype(re.fullmatch(r"(.*?)\s*\w+", a).group(1)) for a in params]
+        protos[m.group(2)] = (ctype(m.group(1).strip(), ret=True), args)
+    return protos
+
+
+def test_signatures_match_the_header_type_for_type():
+    from adalog_amd import _lib
+    protos = header_prototypes()
+    assert set(protos) == set(header_functions())
+    for name, proto in protos.items():
+        res, args = _lib.SIGNATURES[name]
+        assert (res, list(args)) == proto, f"{name}: _lib.SIGNATURES disagrees with include/adalog_hip.h"
+    m = re.search(r"#define ADALOG_ABI_VERSION (\d+)", header_source())
+    assert m and int(m.group(1)) == _lib.ABI_VERSION
+
+
+def test_header_is_valid_c(tmp_path):
+    import shutil
+    cc = next((c for c in ("cc", "gcc", "clang") if shutil.which(c)), None)
+    if cc is None:
+        pytest.skip("no C compiler found")
+    src = tmp_path / "abi.c"
+    src.write_text('#include "adalog_hip.h"\nint adalog_abi_version(void) { return ADALOG_ABI_VERSION; }\n')
+    subprocess.run([cc, "-std=c99", "-fsyntax-only", "-I", os.path.join(ROOT, "include"), str(src)], check=True)
+
+
+def test_folded_entry_points_take_the_longer_argument_lists():
+    """The five names that absorbed their _pre / _ex twins reject bad arguments THROUGH the new argument lists (host-side checks, no
+    launch): arity and order are what ops.py passes.  d: a non-null pointer that is never dereferenced."""
+    from adalog_amd import _lib
+    lib = _lib.load()
+    d = 64
+
+    def rejected(rc, phrase):
+        assert rc == -1 and phrase in lib.adalog_last_error().decode(), lib.adalog_last_error()
+
+    rejected(lib.adalog_attn_split_pack(d, 1, 1, 1, 24, 1.0, d, d, 4, d, d, 4, d, d, 4, 1, d, d, d, 64, None), "head dimension")
+    rejected(lib.adalog_pack_adalog_bf16(d, 1, 1, 16, 16, 16, 1, d, d, 1, 0, 1, 1, 4, d, None, 1, d, 16, 0, 1, None), "GELU prologue")
+    rejected(lib.adalog_log_fake_quant_f32(d, d, None, 4, d, d, None, None, 4, None, 0, 0, 0, None), "needs table1/table2")
+    # K = 24 is no multiple of 16; everything in front of that check (pointers, M, N, G, gmod) is in order
+    rejected(lib.adalog_gemm_out_gen(d, 32, 0, 24, d, d, 0, 4, d, 0, 1, 1, 128, 1, 1, d, 0, 1.0, d, 0, 0, None, 0, 0, None, d, 1, 1, None),
+             "K must be a multiple of 16")
+    rejected(lib.adalog_log_fq_backward(d, d, d, d, 4, d, d, 4, None, 0, d, None, 0, None), "needs a workspace")
+    for kept, suffix in (("adalog_log_fake_quant_f32", "_pre"), ("adalog_pack_adalog_bf16", "_pre"), ("adalog_log_fq_backward", "_pre"),
+                         ("adalog_gemm_out_gen", "_ex"), ("adalog_attn_split_pack", "_ex")):
+        assert hasattr(lib, kept) and not hasattr(lib, kept + suffix), f"{kept + suffix} is still exported"
+
+
+def test_library_of_another_abi_version_is_refused(monkeypatch):
+    from adalog_amd import _lib
+    lib = _lib.load()
+    _lib.check_abi_version(lib)
+    monkeypatch.setattr(lib, "adalog_abi_version", lambda: 1)
+    with pytest.raises(_lib.AdalogHipError) as err:
+        _lib.check_abi_version(lib)
+    assert "version 1" in str(err.value) and "version 2" in str(err.value) and _lib.LIB_PATH in str(err.value)
 
 
 def test_argument_rejection_without_gpu():

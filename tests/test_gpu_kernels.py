@@ -1889,7 +1889,7 @@ def test_gemm_out_gen_equals_pack_then_gemm(ops, bits, M, N, K):
     view = wide[:, 0].unsqueeze(0)
     assert not view.is_contiguous() and ops.gemm_out_gen_ok(view, Kp, bits)
     assert torch.equal(ops.gemm_out_gen(view, scale.to(DEV), zp.to(DEV), bits, wd, N, 1, sa_, sb_, bi_), want)
-    # the residual stream added in the epilogue (adalog_gemm_out_gen_ex): bit for bit the separate add
+    # the residual stream added in the epilogue (adalog_gemm_out_gen with an addend): bit for bit the separate add
     add = torch.randn(1, M, N, generator=gen).to(DEV)
     assert torch.equal(ops.gemm_out_gen(xd, scale.to(DEV), zp.to(DEV), bits, wd, N, 1, sa_, sb_, bi_, addend=add), want + add)
     assert _last_kernel() == "k_gemm_cand_gen_ex"

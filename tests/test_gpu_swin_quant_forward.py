@@ -34,7 +34,7 @@ def _report(rec):
 @pytest.mark.parametrize("q_mul", [None, "scale"])
 def test_attn_split_pack_ex_equals_the_module_route_packs(ops, D, N, per_head, q_mul):
     """q / k / v of a window attention split, q multiplied by the head scale, quantised and packed in one launch
-    (adalog_attn_split_pack_ex) against what the module route packs: pack_uniform of (q * scale) (ATen's fp32 product), of k and of
+    (adalog_attn_split_pack) against what the module route packs: pack_uniform of (q * scale) (ATen's fp32 product), of k and of
     v^T -- identical bytes, padding included; values on rounding ties of k and v by construction."""
     H, B = 3, 5
     gen = g(11000 + D * 7 + N + (1 if per_head else 0) + (2 if q_mul else 0))
