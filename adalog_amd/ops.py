@@ -333,6 +333,86 @@ def unpack_codes(packed, K: int, scale, zero_point, n_bits: int, dtype: int = F3
     return out
 
 
+# ------------------------------------------------------------------------------------------------ GPTQ (csrc/gptq.hip)
+def gptq_sweep_ok(R: int, K: int) -> bool:
+    """Whether gptq_sweep takes a weight of R rows and K columns: K a multiple of 32 in [32, 4096], R >= 1."""
+    return bool(_lib.load().adalog_gptq_sweep_ok(int(R), int(K)))
+
+
+def gptq_sweep(w2, scale, zero_point, n_bits: int, U, want_codes: bool = False, want_objective: bool = False):
+    """The GPTQ column sweep of fp32 w2 [R, K] in one launch: column j of every row is quantised with the row's asymmetric uniform
+    quantiser (scale / zero_point: one element, or one per row), and its rounding error is pushed onto the columns behind it through
+    row j of ``U``, the fp64 upper-triangular [K, K] factor of the inverse Hessian (H^-1 = U^T U).  The recurrence is specified in
+    include/adalog_hip.h and has one result in IEEE arithmetic; two calls return the same bits.
+    -> What fp32 [R, K] [, codes uint8 [R, K]] [, objective fp64 [R]: sum_j e_j^2 = (w - What)^T H (w - What)]."""
+    if w2.dim() != 2:
+        raise ValueError("gptq_sweep: the weight must be viewed as [rows, cols]")
+    w2 = _f32c(w2, "w2")
+    R, K = w2.shape
+    if not gptq_sweep_ok(R, K):
+        raise _lib.AdalogHipError(f"gptq_sweep: unsupported shape [{R}, {K}] (K must be a multiple of 32 in [32, 4096])")
+    if not U.is_cuda or U.dtype != torch.float64 or tuple(U.shape) != (K, K):
+        raise ValueError(f"gptq_sweep: U must be a float64 [{K}, {K}] tensor on the HIP device")
+    U = U if U.is_contiguous() else U.contiguous()
+    if not 2 <= int(n_bits) <= 8:
+        raise ValueError(f"gptq_sweep: n_bits = {n_bits} outside [2, 8]")
+    scale, zero_point, per_row = _codes_params(scale, zero_point, R)
+    what = torch.empty_like(w2)
+    codes = torch.empty((R, K), dtype=torch.uint8, device=w2.device) if want_codes else None
+    obj = torch.empty((R,), dtype=torch.float64, device=w2.device) if want_objective else None
+    rc = _lib.load().adalog_gptq_sweep_f32(w2.data_ptr(), R, K, K, _ptr(scale), _ptr(zero_point), per_row, int(n_bits), U.data_ptr(), K,
+                                          what.data_ptr(), _ptr(codes), _ptr(obj), _stream())
+    _lib.check(rc, "adalog_gptq_sweep_f32")
+    out = (what,) + ((codes,) if want_codes else ()) + ((obj,) if want_objective else ())
+    return out if len(out) > 1 else what
+
+
+_GPTQ_SLICES = 4                       # 7 + 8 + 8 + 8 = 31 bits below the chunk's power-of-two bound
+_GPTQ_MAX_CHUNK = 512                  # tokens per product: 512 * 128 * 128 = 2^23, every partial sum an exact fp32 integer
+
+
+def gptq_hessian_add(H, xq, chunk: int = _GPTQ_MAX_CHUNK):
+    """H += xq^T . xq for fp32 xq [T, K] into the fp64 [K, K] accumulator H (in place; returns H), exact to 2^-31 of the chunk's
+    largest |xq| per element -- far below fp32's own rounding of every element that matters.
+
+    GPTQ's objective lives in the low-curvature directions of H, which amplify an error of H: a plain fp32-accumulating product per
+    chunk (3.5e-7 of the largest entry over 197 tokens, 6e-8 over 32) left the objective of a layer 1e-6 .. 5e-6 off its fp64 value.
+    So a chunk (``chunk`` <= 512 tokens) is cut into four fixed-point slices under a common power of two g >= max |xq|:
+        xq = g (a0 2^-7 + a1 2^-15 + a2 2^-23 + a3 2^-31) + r,   a_k integers, |a_k| <= 128,   |r| <= g 2^-32
+    (each cut an exact fp32 subtraction).  A slice is exact in bf16, a product of two slices is an integer below 2^14 and a sum over 512
+    tokens one below 2^23: gemm_f32x3 (bf16 matrix cores, fp32 accumulation; the split of such a value is (x, 0, 0)) returns
+    a_k^T a_l EXACTLY, in any summation order.  The eight pairs with k <= l, k + l <= 4 are weighted and added in fp64 (the pairs left
+    out are below 2^-40 g^2 per token).  No host synchronisation: g stays on the device."""
+    if xq.dim() != 2:
+        raise ValueError("gptq_hessian_add: xq must be viewed as [tokens, K]")
+    xq = _f32c(xq, "xq")
+    T, K = xq.shape
+    if not H.is_cuda or H.dtype != torch.float64 or tuple(H.shape) != (K, K) or not H.is_contiguous():
+        raise ValueError(f"gptq_hessian_add: H must be a contiguous float64 [{K}, {K}] tensor on the HIP device")
+    chunk = int(chunk)
+    if not 1 <= chunk <= _GPTQ_MAX_CHUNK:
+        raise ValueError(f"gptq_hessian_add: chunk = {chunk} outside [1, {_GPTQ_MAX_CHUNK}] (the slice products must stay exact in fp32)")
+    for t0 in range(0, T, chunk):
+        x = xq[t0:t0 + chunk]
+        g = torch.ldexp(torch.ones((), dtype=torch.float32, device=x.device), torch.frexp(x.abs().amax())[1])   # 2^e > max |x|
+        r = (x / g) * 128.0
+        slices = []
+        for k in range(_GPTQ_SLICES):
+            a = torch.round(r)                           # (ties to even; |a| <= 128)
+            slices.append(a)
+            if k + 1 < _GPTQ_SLICES:
+                r = (r - a) * 256.0                      # exact: |r - a| <= 1/2 keeps no bit above r's last
+        g2 = g.double() * g.double()
+        for k in range(_GPTQ_SLICES):
+            for l in range(k, min(_GPTQ_SLICES, 5 - k)):             # k <= l, k + l <= 4
+                at, bt = slices[k].t(), slices[l].t()    # [K, tokens], K-major: read in place
+                p = gemm_f32x3(at, bt).double() * (g2 * 2.0 ** -(14 + 8 * (k + l)))
+                H.add_(p)
+                if l != k:
+                    H.add_(p.t())
+    return H
+
+
 # ------------------------------------------------------------------------------------------------ scoring GEMM
 class Strided:
     """A device fp32 parameter with (candidate, head, column) element strides for the GEMM epilogue."""

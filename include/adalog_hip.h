@@ -570,6 +570,21 @@ int adalog_uniform_code_hist_f32(const float* x, int64_t n, const float* scale, 
 int adalog_log_code_hist_f32(const float* x, int64_t n, const float* scale, const int64_t* q, int n_bits, const float* shift,
                              int pre, int64_t* out, void* stream);
 
+/* ---- GPTQ column sweep of a layer's weight (utils/gptq.py; Frantar et al., ICLR 2023; no counterpart in the reference)
+ * Per row r of w[R][K] (rows start ldw elements apart), with the row's asymmetric uniform quantiser s, z (scale / zero_point: [1]
+ * when per_row = 0, [R] when 1; 2 <= n_bits <= 8) and U fp64 [K][K] upper triangular (rows ldu apart), H^-1 = U^T U:
+ *   run = double(w[r]);  for j = 0 .. K-1:  c = clamp(rne(float(run[j]) / s) + rne(z), 0, 2^n_bits - 1);  q = (c - rne(z)) * s (fp32);
+ *   e = (run[j] - double(q)) / U[j][j];  run[k] = run[k] - e * U[j][k] for k > j (fp64, one multiply and one subtract, j ascending).
+ * what[R][K] = q (fp32, contiguous); codes[R][K] = c (uint8, optional); objective[R] = sum_j e^2 in ascending j (fp64, optional).
+ * The result is the one the recurrence has in IEEE arithmetic: two calls, and the numpy restatement of tests/gptq_reference.py,
+ * give the same bits.  One launch, no workspace.
+ * adalog_gptq_sweep_ok: 1 when the kernel takes the shape -- R >= 1, K a multiple of 32 with 32 <= K <= 4096 -- else 0 (host only);
+ * adalog_gptq_sweep_f32 returns -1 for any other shape.  Both validate their arguments before touching the device. */
+int adalog_gptq_sweep_ok(int64_t R, int64_t K);
+int adalog_gptq_sweep_f32(const float* w, int64_t R, int64_t K, int64_t ldw, const float* scale, const float* zero_point,
+                          int per_row, int n_bits, const double* U, int64_t ldu, float* what, uint8_t* codes, double* objective,
+                          void* stream);
+
 /* ---- K17  BRECQ / AdaRound block reconstruction: fused straight-through backward passes and AdaRound kernels
  * adalog_uniform_fq_backward: gradients of the training form y = (clamp(round_ste(x/s) + round_ste(zp), 0, 2L-1) - round_ste(zp)) * s
  *   (reference quantizers/uniform.py:29-35 + _ste.py:5-6):  gx = gy*[inside];  gscale[ch] = sum gy*((q - z) - [inside]*x/s);
