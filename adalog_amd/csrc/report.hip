@@ -1,12 +1,13 @@
 // Measurement passes of the per-layer quantisation report (utils/report.py): HBM-bound streaming kernels, one pass over each input,
 // nothing of the input's size written.
-//   adalog_err_stats_f32         per channel: sum (a-b)^2, sum a^2, sum b^2, max |a-b| in fp64                      (k_err_stats)
+//   adalog_err_stats_f32         per channel: sum (a-b)^2, sum a^2, sum b^2, max |a-b| in fp64                      (k_stats<Acc>)
+//   adalog_mean_err_f32          per channel: sum (a-b), sum (a-b)^2, max |a| in fp64 (utils/bias_correct.py)       (k_stats<MeanAcc>)
 //   adalog_uniform_code_hist_f32 per channel: counts of the codes rne(x/s) + rne(z) and of the two clip sides       (k_code_hist_uniform)
 //   adalog_log_code_hist_f32     counts of the AdaLog / ShiftAdaLog bins and of the masked code                      (k_code_hist_log)
 // Channel convention of the uniform quantiser (fakequant.hip): channel(i) = (i / inner) % n_channels, i.e. the tensor is
 // [rpc][n_channels][inner] and channel c owns rpc rows of inner contiguous elements.
 //
-// Reproducibility: no floating-point atomics.  err_stats writes one fp64 partial per (channel, block) to the caller's workspace and a
+// Reproducibility: no floating-point atomics.  err_stats and mean_err write one fp64 partial per (channel, block) to the caller's workspace and a
 // second small launch adds them in a fixed order (block partials: lanes, then waves, in a fixed tree), so two runs give the same bits.
 // The histograms count in 32-bit LDS counters private to a wave (several copies per wave for narrow codes: 64 lanes on 16 counters
 // would serialise on the same address) and flush with 64-bit integer atomics: integer sums do not depend on the order.
@@ -72,27 +73,48 @@ __device__ __forceinline__ void stream_channel(const float* __restrict__ a, cons
 }
 
 // ------------------------------------------------------------------------------------------------ error statistics
-struct Acc {
-    double d2, a2, b2, mx;
+// An accumulator is N fp64 values v[] with add(x, y) for one element pair and merge(o) for another accumulator: the kernels below
+// (stream or cols pass, block tree, finish) are written once over it.
+struct Acc {                                           // err_stats: sum (a-b)^2, sum a^2, sum b^2, max |a-b|
+    static constexpr int N = 4;
+    double v[N];
     __device__ __forceinline__ void add(float x, float y) {
         const double dx = (double)x, dy = (double)y, d = dx - dy;     // fp64 from the fp32 inputs: no fp32 rounding, no fp32 overflow
-        d2 += d * d;
-        a2 += dx * dx;
-        b2 += dy * dy;
-        mx = fmax(mx, fabs(d));
+        v[0] += d * d;
+        v[1] += dx * dx;
+        v[2] += dy * dy;
+        v[3] = fmax(v[3], fabs(d));
     }
-    __device__ __forceinline__ void merge(const Acc& o) { d2 += o.d2; a2 += o.a2; b2 += o.b2; mx = fmax(mx, o.mx); }
+    __device__ __forceinline__ void merge(const Acc& o) { v[0] += o.v[0]; v[1] += o.v[1]; v[2] += o.v[2]; v[3] = fmax(v[3], o.v[3]); }
 };
 
-// the block's Acc in thread 0: lanes by shuffles (a fixed tree), then the waves in order
-__device__ __forceinline__ Acc block_reduce(Acc v, Acc* red /* [WAVES] in LDS */) {
+struct MeanAcc {                                       // mean_err: sum (a-b), sum (a-b)^2, max |a|
+    static constexpr int N = 3;
+    double v[N];
+    __device__ __forceinline__ void add(float x, float y) {
+        const double dx = (double)x, d = dx - (double)y;              // exact: the difference of two fp32 values fits fp64's exponent range
+        v[0] += d;
+        v[1] += d * d;
+        v[2] = fmax(v[2], fabs(dx));
+    }
+    __device__ __forceinline__ void merge(const MeanAcc& o) { v[0] += o.v[0]; v[1] += o.v[1]; v[2] = fmax(v[2], o.v[2]); }
+};
+
+template <class A> __device__ __forceinline__ A zero_acc() {
+    A a;
+#pragma unroll
+    for (int k = 0; k < A::N; ++k) a.v[k] = 0.0;
+    return a;
+}
+
+// the block's accumulator in thread 0: lanes by shuffles (a fixed tree), then the waves in order
+template <class A>
+__device__ __forceinline__ A block_reduce(A v, A* red /* [WAVES] in LDS */) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
-        Acc o;
-        o.d2 = __shfl_down(v.d2, off);
-        o.a2 = __shfl_down(v.a2, off);
-        o.b2 = __shfl_down(v.b2, off);
-        o.mx = __shfl_down(v.mx, off);
+        A o;
+#pragma unroll
+        for (int k = 0; k < A::N; ++k) o.v[k] = __shfl_down(v.v[k], off);
         v.merge(o);
     }
     const int wave = threadIdx.x >> 6;
@@ -104,43 +126,49 @@ __device__ __forceinline__ Acc block_reduce(Acc v, Acc* red /* [WAVES] in LDS */
     return v;
 }
 
-__device__ __forceinline__ void store_acc(double* p, const Acc& v) { p[0] = v.d2; p[1] = v.a2; p[2] = v.b2; p[3] = v.mx; }
+template <class A> __device__ __forceinline__ void store_acc(double* p, const A& a) {
+#pragma unroll
+    for (int k = 0; k < A::N; ++k) p[k] = a.v[k];
+}
 
-// part[c][blockIdx.x][4]: the share of block blockIdx.x (of gridDim.x = parts) in channel c
-__global__ __launch_bounds__(TPB) void k_err_stats(const float* __restrict__ a, const float* __restrict__ b, Geo g,
-                                                   double* __restrict__ part) {
-    __shared__ Acc red[WAVES];
+// part[c][blockIdx.x][N]: the share of block blockIdx.x (of gridDim.x = parts) in channel c
+template <class A>
+__global__ __launch_bounds__(TPB) void k_stats(const float* __restrict__ a, const float* __restrict__ b, Geo g, double* __restrict__ part) {
+    __shared__ A red[WAVES];
     for (int64_t c = blockIdx.y; c < g.n_ch; c += gridDim.y) {
-        Acc v = {0.0, 0.0, 0.0, 0.0};
+        A v = zero_acc<A>();
         stream_channel<true>(a, b, g, c, [&](float x, float y) { v.add(x, y); });
         v = block_reduce(v, red);
-        if (threadIdx.x == 0) store_acc(part + (c * gridDim.x + blockIdx.x) * 4, v);
+        if (threadIdx.x == 0) store_acc(part + (c * gridDim.x + blockIdx.x) * A::N, v);
     }
 }
 
 // inner = 1: x is [rows][n_ch], a thread owns a channel (coalesced along the channels) and every parts-th row of it
-__global__ __launch_bounds__(TPB) void k_err_stats_cols(const float* __restrict__ a, const float* __restrict__ b, int64_t rows,
-                                                        int64_t n_ch, double* __restrict__ part) {
+template <class A>
+__global__ __launch_bounds__(TPB) void k_stats_cols(const float* __restrict__ a, const float* __restrict__ b, int64_t rows, int64_t n_ch,
+                                                    double* __restrict__ part) {
     const int64_t ch = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (ch >= n_ch) return;
-    Acc v = {0.0, 0.0, 0.0, 0.0};
+    A v = zero_acc<A>();
     for (int64_t r = blockIdx.y; r < rows; r += gridDim.y) v.add(a[r * n_ch + ch], b[r * n_ch + ch]);
-    store_acc(part + (ch * gridDim.y + blockIdx.y) * 4, v);
+    store_acc(part + (ch * gridDim.y + blockIdx.y) * A::N, v);
 }
 
-// out[c][4] = the parts of channel c added in a fixed order: thread t takes parts t, t + 256, ... in order, then the block's tree
-__global__ __launch_bounds__(TPB) void k_err_stats_finish(const double* __restrict__ part, int64_t n_ch, int parts,
-                                                          double* __restrict__ out) {
-    __shared__ Acc red[WAVES];
+// out[c][N] = the parts of channel c added in a fixed order: thread t takes parts t, t + 256, ... in order, then the block's tree
+template <class A>
+__global__ __launch_bounds__(TPB) void k_stats_finish(const double* __restrict__ part, int64_t n_ch, int parts, double* __restrict__ out) {
+    __shared__ A red[WAVES];
     for (int64_t c = blockIdx.x; c < n_ch; c += gridDim.x) {
-        Acc v = {0.0, 0.0, 0.0, 0.0};
+        A v = zero_acc<A>();
         for (int p = threadIdx.x; p < parts; p += TPB) {
-            const double* q = part + (c * parts + p) * 4;
-            Acc o = {q[0], q[1], q[2], q[3]};
+            const double* q = part + (c * parts + p) * A::N;
+            A o;
+#pragma unroll
+            for (int k = 0; k < A::N; ++k) o.v[k] = q[k];
             v.merge(o);
         }
         v = block_reduce(v, red);
-        if (threadIdx.x == 0) store_acc(out + c * 4, v);
+        if (threadIdx.x == 0) store_acc(out + c * A::N, v);
     }
 }
 
@@ -259,12 +287,37 @@ inline Geo geo_for(int64_t n, int64_t n_ch, int64_t inner, const void* a, const 
 
 inline dim3 channel_grid(int parts, int64_t n_ch) { return dim3((unsigned)parts, (unsigned)(n_ch < 65535 ? n_ch : 65535)); }
 
+// the two launches of err_stats / mean_err over accumulator A; ``what`` names the entry point in messages, ``label`` its kernels
+template <class A>
+int run_stats(const char* what, const char* label, const float* a, const float* b, int64_t n, int64_t n_channels, int64_t inner,
+              double* out, void* workspace, int64_t workspace_bytes, hipStream_t st) {
+    const int parts = err_parts(n, n_channels, inner);
+    ADALOG_ARG_CHECK(workspace && ((uintptr_t)workspace & 7) == 0 &&
+                         workspace_bytes >= n_channels * (int64_t)parts * A::N * (int64_t)sizeof(double),
+                     "err_stats / mean_err: workspace missing, misaligned or smaller than the workspace query's answer");
+    double* part = (double*)workspace;
+    int rc;
+    if (cols_form(n_channels, inner)) {
+        const dim3 grid((unsigned)((n_channels + TPB - 1) / TPB), (unsigned)parts);
+        rc = adalog_launch<k_stats_cols<A>>(label, 0, grid, TPB, 0, st, a, b, n / n_channels, n_channels, part);
+    } else {
+        rc = adalog_launch<k_stats<A>>(label, 0, channel_grid(parts, n_channels), TPB, 0, st, a, b, geo_for(n, n_channels, inner, a, b), part);
+    }
+    if (rc) return rc;
+    ADALOG_LAUNCH_CHECK(what);
+    const dim3 fgrid((unsigned)(n_channels < 4096 ? n_channels : 4096));
+    rc = adalog_launch<k_stats_finish<A>>(label, 0, fgrid, TPB, 0, st, (const double*)part, n_channels, parts, out);
+    if (rc) return rc;
+    ADALOG_LAUNCH_CHECK(what);
+    return 0;
+}
+
 }  // namespace
 
 extern "C" int64_t adalog_err_stats_workspace_bytes(int64_t n, int64_t n_channels, int64_t inner) {
     if (!layout_ok(n, n_channels, inner)) return -1;
     if (n == 0) return 0;
-    return n_channels * (int64_t)err_parts(n, n_channels, inner) * 4 * (int64_t)sizeof(double);
+    return n_channels * (int64_t)err_parts(n, n_channels, inner) * Acc::N * (int64_t)sizeof(double);
 }
 
 extern "C" int adalog_err_stats_f32(const float* a, const float* b, int64_t n, int64_t n_channels, int64_t inner, double* out,
@@ -273,30 +326,35 @@ extern "C" int adalog_err_stats_f32(const float* a, const float* b, int64_t n, i
     ADALOG_ARG_CHECK(out && ((uintptr_t)out & 7) == 0, "err_stats: out must be an 8-byte aligned device pointer");
     hipStream_t st = (hipStream_t)stream;
     if (n == 0) {
-        const hipError_t e = hipMemsetAsync(out, 0, (size_t)n_channels * 4 * sizeof(double), st);
+        const hipError_t e = hipMemsetAsync(out, 0, (size_t)n_channels * Acc::N * sizeof(double), st);
         if (e != hipSuccess) { adalog_set_error("err_stats: hipMemsetAsync", e); return (int)e; }
         return 0;
     }
     ADALOG_ARG_CHECK(a && b && aligned4(a) && aligned4(b), "err_stats: a and b must be 4-byte aligned device pointers");
-    const int parts = err_parts(n, n_channels, inner);
-    ADALOG_ARG_CHECK(workspace && ((uintptr_t)workspace & 7) == 0 && workspace_bytes >= n_channels * (int64_t)parts * 4 * (int64_t)sizeof(double),
-                     "err_stats: workspace missing, misaligned or smaller than adalog_err_stats_workspace_bytes");
-    double* part = (double*)workspace;
-    int rc;
-    if (cols_form(n_channels, inner)) {
-        const dim3 grid((unsigned)((n_channels + TPB - 1) / TPB), (unsigned)parts);
-        rc = adalog_launch<k_err_stats_cols>("k_err_stats", 0, grid, TPB, 0, st, a, b, n / n_channels, n_channels, part);
-    } else {
-        rc = adalog_launch<k_err_stats>("k_err_stats", 0, channel_grid(parts, n_channels), TPB, 0, st, a, b,
-                                        geo_for(n, n_channels, inner, a, b), part);
+    return run_stats<Acc>("adalog_err_stats_f32", "k_err_stats", a, b, n, n_channels, inner, out, workspace, workspace_bytes, st);
+}
+
+// (one channel: the tensor is one contiguous run whatever ``inner`` says -- the form with the 16-byte loads)
+extern "C" int64_t adalog_mean_err_workspace_bytes(int64_t n, int64_t n_channels, int64_t inner) {
+    if (!layout_ok(n, n_channels, inner)) return -1;
+    if (n == 0) return 0;
+    if (n_channels == 1) inner = n;
+    return n_channels * (int64_t)err_parts(n, n_channels, inner) * MeanAcc::N * (int64_t)sizeof(double);
+}
+
+extern "C" int adalog_mean_err_f32(const float* a, const float* b, int64_t n, int64_t n_channels, int64_t inner, double* out,
+                                   void* workspace, int64_t workspace_bytes, void* stream) {
+    ADALOG_ARG_CHECK(layout_ok(n, n_channels, inner), "mean_err: bad sizes (0 <= n <= 2^40, n a multiple of n_channels * inner)");
+    ADALOG_ARG_CHECK(out && ((uintptr_t)out & 7) == 0, "mean_err: out must be an 8-byte aligned device pointer");
+    hipStream_t st = (hipStream_t)stream;
+    if (n == 0) {
+        const hipError_t e = hipMemsetAsync(out, 0, (size_t)n_channels * MeanAcc::N * sizeof(double), st);
+        if (e != hipSuccess) { adalog_set_error("mean_err: hipMemsetAsync", e); return (int)e; }
+        return 0;
     }
-    if (rc) return rc;
-    ADALOG_LAUNCH_CHECK("adalog_err_stats_f32");
-    const dim3 fgrid((unsigned)(n_channels < 4096 ? n_channels : 4096));
-    rc = adalog_launch<k_err_stats_finish>("k_err_stats", 0, fgrid, TPB, 0, st, (const double*)part, n_channels, parts, out);
-    if (rc) return rc;
-    ADALOG_LAUNCH_CHECK("adalog_err_stats_f32");
-    return 0;
+    ADALOG_ARG_CHECK(a && b && aligned4(a) && aligned4(b), "mean_err: a and b must be 4-byte aligned device pointers");
+    if (n_channels == 1) inner = n;
+    return run_stats<MeanAcc>("adalog_mean_err_f32", "k_mean_err", a, b, n, n_channels, inner, out, workspace, workspace_bytes, st);
 }
 
 extern "C" int adalog_uniform_code_hist_f32(const float* x, int64_t n, const float* scale, const float* zero_point, int64_t n_channels,

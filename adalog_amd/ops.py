@@ -162,6 +162,26 @@ def err_stats(a, b, n_channels: int = 1, inner: Optional[int] = None):
     return out
 
 
+def mean_err(a, b, n_channels: int = 1, inner: Optional[int] = None):
+    """-> fp64 [n_channels, 3] on the device: sum d, sum d^2, max |a| per channel with d = double(a) - double(b) (exact), ``a`` the
+    reference and the channel layout of err_stats.  Sums in fp64 in a fixed order, no floating-point atomics: two calls on the same
+    input return the same bits."""
+    a, b = _f32c(a, "a"), _f32c(b, "b")
+    if a.numel() != b.numel():
+        raise ValueError(f"mean_err: a has {a.numel()} elements, b {b.numel()}")
+    n = a.numel()
+    n_channels, inner = _channel_layout(n, n_channels, inner, "mean_err")
+    lib = _lib.load()
+    out = torch.empty((n_channels, 3), dtype=torch.float64, device=a.device)
+    nbytes = lib.adalog_mean_err_workspace_bytes(n, n_channels, inner)
+    if nbytes < 0:
+        raise ValueError(f"mean_err: unsupported sizes n = {n}, n_channels = {n_channels}, inner = {inner}")
+    ws = torch.empty(max(1, nbytes // 8), dtype=torch.float64, device=a.device)
+    rc = lib.adalog_mean_err_f32(_ptr(a), _ptr(b), n, n_channels, inner, out.data_ptr(), ws.data_ptr(), ws.numel() * 8, _stream())
+    _lib.check(rc, "adalog_mean_err_f32")
+    return out
+
+
 def uniform_code_hist(x, scale, zp, n_bits: int, n_channels: int = 1, inner: Optional[int] = None):
     """-> int64 [n_channels, 2^n_bits + 2] on the device: per channel the count of every code rne(x / s) + rne(z) in [0, 2^n_bits - 1],
     then ``below`` and ``above`` (elements either clamp of the asymmetric uniform quantiser moves: counted there only).  No code tensor

@@ -19,7 +19,7 @@ Eligible: quantised Linear layers whose weight utils.packed would store as codes
 scale or one per row) and whose shape ops.gptq_sweep_ok takes.  Everything else keeps its weight and is listed with the reason; the
 patch-embedding convolution is out of scope here.
 
-    python -m adalog_amd.utils.gptq --model deit_small --config configs/4bit.py --checkpoint plain.pth --out gptq.pth [--packed]
+    python -m adalog_amd.utils.gptq --model deit_small --config configs/4bit.py --checkpoint plain.pth --out gptq.pth [--packed] [--bias-correct]
 """
 import argparse
 import logging
@@ -71,9 +71,11 @@ def _quadratic(D, Hd):
     return float(((D @ Hd) * D).sum())
 
 
-def gptq_model(model, images, damp=0.01, batch_size=32):
+def gptq_model(model, images, damp=0.01, batch_size=32, bias_correct=False):
     """GPTQ rounding of every eligible layer of a wrapped, calibrated ``model`` from ``images`` (on the model's device); see the module
-    text.  Every module's ``mode`` is restored afterwards (quant_forward for a calibrated model).
+    text.  Every module's ``mode`` is restored afterwards (quant_forward for a calibrated model).  ``bias_correct``: afterwards, the
+    empirical bias correction of utils/bias_correct.py on the same images (its result under "bias_correct"), against FP biases fixed
+    before the sweep -- which also takes out of fc2's bias the shift fold the sweep made stale.
     -> {"images", "damp", "layers": {name: {"R", "K", "n_bits", "objective_before" (round-to-nearest under the same damped H),
     "objective_after", "seconds" (factor + sweep)}}, "skipped": {name: reason}, "seconds": {"capture", "factor", "sweep"}}."""
     from . import models
@@ -85,6 +87,9 @@ def gptq_model(model, images, damp=0.01, batch_size=32):
             todo.append((name, m))
         else:
             skipped[name] = why
+    if bias_correct:
+        from .bias_correct import bias_correct_model, remember_fp_biases
+        remember_fp_biases(model)                          # the fold in fc2's bias is that of q(W) as it is now
     moded = [m for m in model.modules() if hasattr(m, "mode")]
     saved_modes = [(m, m.mode) for m in moded]
     saved_switches = (models.QF_FUSED, models.QF_ATTN_CORE, models.QF_LONG)
@@ -148,7 +153,10 @@ def gptq_model(model, images, damp=0.01, batch_size=32):
                      f"factor (host) {t2 - t1:.3f} s, sweep {t3 - t2:.4f} s")
     logging.info(f"gptq: {len(layers)} layers swept, {len(skipped)} left; capture {seconds['capture']:.2f} s, factor (host) "
                  f"{seconds['factor']:.2f} s, sweep {seconds['sweep']:.3f} s")
-    return {"images": B, "damp": float(damp), "layers": layers, "skipped": skipped, "seconds": seconds}
+    res = {"images": B, "damp": float(damp), "layers": layers, "skipped": skipped, "seconds": seconds}
+    if bias_correct:
+        res["bias_correct"] = bias_correct_model(model, images, batch_size=batch_size)
+    return res
 
 
 def main(argv=None):
@@ -167,6 +175,7 @@ def main(argv=None):
     ap.add_argument("--damp", type=float, default=0.01)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--dataset", default=None, help="ImageNet root: the first --images validation images instead of a seeded randn batch")
+    ap.add_argument("--bias-correct", action="store_true", help="after the sweep, correct the biases on the same images (utils/bias_correct.py)")
     ap.add_argument("--device", default="cuda")
     args = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="%(message)s")
@@ -178,7 +187,7 @@ def main(argv=None):
     else:
         size = args.img_size or getattr(getattr(model, "patch_embed", None), "img_size", (224, 224))[0]
         images = torch.randn(args.images, 3, size, size, generator=torch.Generator().manual_seed(args.seed)).to(device)
-    res = gptq_model(model, images, damp=args.damp, batch_size=args.batch_size)
+    res = gptq_model(model, images, damp=args.damp, batch_size=args.batch_size, bias_correct=args.bias_correct)
     if args.packed:
         save_packed(model, args.out)
     else:
@@ -186,8 +195,9 @@ def main(argv=None):
     before = sum(e["objective_before"] for e in res["layers"].values())
     after = sum(e["objective_after"] for e in res["layers"].values())
     s = res["seconds"]
+    bc = f"; {len(res['bias_correct']['layers'])} biases corrected" if args.bias_correct else ""
     print(f"{args.out}: {len(res['layers'])} layers swept, {len(res['skipped'])} left as they were; objective {before:.6g} -> {after:.6g}; "
-          f"capture {s['capture']:.2f} s, factor (host) {s['factor']:.2f} s, sweep {s['sweep']:.3f} s")
+          f"capture {s['capture']:.2f} s, factor (host) {s['factor']:.2f} s, sweep {s['sweep']:.3f} s{bc}")
     return 0
 
 

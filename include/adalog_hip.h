@@ -561,10 +561,16 @@ int adalog_unpack_codes(const uint32_t* in, int64_t R, int64_t K, const float* s
  * log_code_hist: out[2^b + 1] (int64) = the count of every bin of K2 (AdaLog / ShiftAdaLog, per-tensor scale[1], q[1] on the device,
  *   shift[1] or NULL), the last entry the masked code (K2's 255).  The bin comes from the device function K2 takes its ``bins``
  *   output from.  pre: the input is GELU(x), as in adalog_log_fake_quant_f32.
+ * mean_err: out[n_channels][3] (fp64) = sum d, sum d^2, max |a| per channel with d = double(a[i]) - double(b[i]) (exact in fp64: no
+ *   fp32 subtraction), a the reference (utils/bias_correct.py: the per-channel mean error of a layer's output).  Layouts, workspace
+ *   (its own query), fixed summation order and n = 0 as err_stats; one channel is read as one contiguous run whatever inner says.
  * All validate their arguments before touching the device; out is zeroed by the call. */
 int64_t adalog_err_stats_workspace_bytes(int64_t n, int64_t n_channels, int64_t inner);
 int adalog_err_stats_f32(const float* a, const float* b, int64_t n, int64_t n_channels, int64_t inner, double* out,
                          void* workspace, int64_t workspace_bytes, void* stream);
+int64_t adalog_mean_err_workspace_bytes(int64_t n, int64_t n_channels, int64_t inner);
+int adalog_mean_err_f32(const float* a, const float* b, int64_t n, int64_t n_channels, int64_t inner, double* out,
+                        void* workspace, int64_t workspace_bytes, void* stream);
 int adalog_uniform_code_hist_f32(const float* x, int64_t n, const float* scale, const float* zero_point, int64_t n_channels,
                                  int64_t inner, int n_bits, int64_t* out, void* stream);
 int adalog_log_code_hist_f32(const float* x, int64_t n, const float* scale, const int64_t* q, int n_bits, const float* shift,
