@@ -5,6 +5,7 @@ stream.  No function here computes anything with torch ops, and none synchronise
 """
 from __future__ import annotations
 
+import ctypes
 import math
 import os
 from typing import Optional, Tuple
@@ -385,6 +386,48 @@ def gptq_sweep(w2, scale, zero_point, n_bits: int, U, want_codes: bool = False, 
     _lib.check(rc, "adalog_gptq_sweep_f32")
     out = (what,) + ((codes,) if want_codes else ()) + ((obj,) if want_objective else ())
     return out if len(out) > 1 else what
+
+
+# ------------------------------------------------------------------------------------------------ bit cost (csrc/bitcost.hip)
+def bit_cost_ok(R: int, K: int, n_widths: int) -> bool:
+    """Whether bit_cost takes a weight of R rows and K columns at n_widths widths: K a multiple of 32 in [32, 4096] (the GPTQ sweep's
+    domain), R >= 1, 1 <= n_widths <= 8."""
+    return bool(_lib.load().adalog_bit_cost_ok(int(R), int(K), int(n_widths)))
+
+
+def bit_cost(w2, scales, zero_points, bits, H):
+    """cost[i][r] = d H d^T of row r of fp32 w2 [R, K] at width bits[i], in one launch on the fp64 matrix cores: d = w - q_b(w) with the
+    asymmetric uniform quantiser of width bits[i] (``scales`` / ``zero_points``: [n_widths, 1] for one quantiser per width, or
+    [n_widths, R] for one per row), and d = w itself where bits[i] == 0 (the signal row, w H w^T).  ``H``: symmetric float64 [K, K].
+    The arithmetic is specified in include/adalog_hip.h; two calls return the same bits.  -> float64 [n_widths, R] on the device."""
+    if w2.dim() != 2:
+        raise ValueError("bit_cost: the weight must be viewed as [rows, cols]")
+    w2 = _f32c(w2, "w2")
+    R, K = w2.shape
+    bits = [int(b) for b in bits]
+    nw = len(bits)
+    if not bit_cost_ok(R, K, nw):
+        raise _lib.AdalogHipError(f"bit_cost: unsupported shape [{R}, {K}] at {nw} widths (K must be a multiple of 32 in [32, 4096], "
+                                  "1 <= n_widths <= 8)")
+    if any(b != 0 and not 2 <= b <= 8 for b in bits):
+        raise ValueError(f"bit_cost: bits = {bits}: every width must be 0 (the signal row) or in [2, 8]")
+    if not H.is_cuda or H.dtype != torch.float64 or tuple(H.shape) != (K, K):
+        raise ValueError(f"bit_cost: H must be a float64 [{K}, {K}] tensor on the HIP device")
+    H = H if H.is_contiguous() else H.contiguous()
+    scales, zero_points = _f32c(scales, "scales"), _f32c(zero_points, "zero_points")
+    if scales.dim() != 2 or scales.shape != zero_points.shape or scales.shape[0] != nw or scales.shape[1] not in (1, R):
+        raise ValueError(f"bit_cost: scales / zero_points must both be [{nw}, 1] or [{nw}, {R}] (one per row), got "
+                         f"{tuple(scales.shape)} / {tuple(zero_points.shape)}")
+    per_row = int(scales.shape[1] == R and R > 1)
+    lib = _lib.load()
+    nbytes = int(lib.adalog_bit_cost_workspace_bytes(R, K, nw))
+    ws = torch.empty((max(nbytes, 8) // 8,), dtype=torch.float64, device=w2.device)
+    cost = torch.empty((nw, R), dtype=torch.float64, device=w2.device)
+    bits_c = (ctypes.c_int * nw)(*bits)                  # host array: read before the call returns
+    rc = lib.adalog_bit_cost_f32(w2.data_ptr(), R, K, K, scales.data_ptr(), zero_points.data_ptr(), per_row,
+                                 ctypes.cast(bits_c, ctypes.c_void_p), nw, H.data_ptr(), K, cost.data_ptr(), ws.data_ptr(), nbytes, _stream())
+    _lib.check(rc, "adalog_bit_cost_f32")
+    return cost
 
 
 _GPTQ_SLICES = 4                       # 7 + 8 + 8 + 8 = 31 bits below the chunk's power-of-two bound

@@ -266,7 +266,7 @@ def bias_correct_model(model, images, batch_size=32):
 
 
 def main(argv=None):
-    from .packed import build_wrapped, load_plain, save_packed
+    from .packed import BIT_PLAN_HELP, build_wrapped, load_plain, plan_kwargs, save_packed
     from .report import _dataset_images
     ap = argparse.ArgumentParser(description="Empirical bias correction of a plain calibrated checkpoint")
     ap.add_argument("--model", required=True)
@@ -281,10 +281,11 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--dataset", default=None, help="ImageNet root: the first --images validation images instead of a seeded randn batch")
     ap.add_argument("--device", default="cuda")
+    ap.add_argument("--bit-plan", default=None, help=BIT_PLAN_HELP)
     args = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="%(message)s")
     device = torch.device(args.device)
-    model = build_wrapped(args.model, args.config, device, img_size=args.img_size, depth=args.depth)
+    model = build_wrapped(args.model, args.config, device, img_size=args.img_size, depth=args.depth, **plan_kwargs(args.bit_plan))
     model = load_plain(model, args.checkpoint, device)
     if args.dataset:
         images = _dataset_images(args.dataset, args.model, args.images, device)

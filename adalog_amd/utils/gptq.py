@@ -71,25 +71,12 @@ def _quadratic(D, Hd):
     return float(((D @ Hd) * D).sum())
 
 
-def gptq_model(model, images, damp=0.01, batch_size=32, bias_correct=False):
-    """GPTQ rounding of every eligible layer of a wrapped, calibrated ``model`` from ``images`` (on the model's device); see the module
-    text.  Every module's ``mode`` is restored afterwards (quant_forward for a calibrated model).  ``bias_correct``: afterwards, the
-    empirical bias correction of utils/bias_correct.py on the same images (its result under "bias_correct"), against FP biases fixed
-    before the sweep -- which also takes out of fc2's bias the shift fold the sweep made stale.
-    -> {"images", "damp", "layers": {name: {"R", "K", "n_bits", "objective_before" (round-to-nearest under the same damped H),
-    "objective_after", "seconds" (factor + sweep)}}, "skipped": {name: reason}, "seconds": {"capture", "factor", "sweep"}}."""
+def capture_hessians(model, modules, images, batch_size, rows_of):
+    """One pass of ``images`` through ``model`` in ``raw`` mode (the FP model, fused switches off): a forward hook on every module of
+    ``modules`` adds X^T X of X = rows_of(module, args) -- fp32 [tokens, in_features] -- into an fp64 accumulator
+    (ops.gptq_hessian_add).  Hooks, modes and switches are restored.  -> {id(module): H fp64 [K, K] on the module's device}."""
     from . import models
     be = backend.get()
-    skipped, todo = OrderedDict(), []
-    for name, m in _quantised_layers(model):
-        why = _why_not(be, m)
-        if why is None:
-            todo.append((name, m))
-        else:
-            skipped[name] = why
-    if bias_correct:
-        from .bias_correct import bias_correct_model, remember_fp_biases
-        remember_fp_biases(model)                          # the fold in fc2's bias is that of q(W) as it is now
     moded = [m for m in model.modules() if hasattr(m, "mode")]
     saved_modes = [(m, m.mode) for m in moded]
     saved_switches = (models.QF_FUSED, models.QF_ATTN_CORE, models.QF_LONG)
@@ -97,16 +84,14 @@ def gptq_model(model, images, damp=0.01, batch_size=32, bias_correct=False):
     handles = []
 
     def capture(m, args, out):
-        xq = m.quant_input(args[0]).reshape(-1, m.in_features)
-        be.gptq_hessian_add(hess[id(m)], xq)
+        be.gptq_hessian_add(hess[id(m)], rows_of(m, args))
 
     B = int(images.shape[0])
-    t0 = time.perf_counter()
     try:
         models.QF_FUSED = models.QF_ATTN_CORE = models.QF_LONG = False
         for m in moded:
             m.mode = "raw"
-        for _, m in todo:
+        for m in modules:
             hess[id(m)] = torch.zeros((m.in_features, m.in_features), dtype=torch.float64, device=m.weight.device)
             handles.append(m.register_forward_hook(capture))
         with torch.no_grad():
@@ -118,6 +103,31 @@ def gptq_model(model, images, damp=0.01, batch_size=32, bias_correct=False):
         for m, mode in saved_modes:
             m.mode = mode
         models.QF_FUSED, models.QF_ATTN_CORE, models.QF_LONG = saved_switches
+    return hess
+
+
+def gptq_model(model, images, damp=0.01, batch_size=32, bias_correct=False):
+    """GPTQ rounding of every eligible layer of a wrapped, calibrated ``model`` from ``images`` (on the model's device); see the module
+    text.  Every module's ``mode`` is restored afterwards (quant_forward for a calibrated model).  ``bias_correct``: afterwards, the
+    empirical bias correction of utils/bias_correct.py on the same images (its result under "bias_correct"), against FP biases fixed
+    before the sweep -- which also takes out of fc2's bias the shift fold the sweep made stale.
+    -> {"images", "damp", "layers": {name: {"R", "K", "n_bits", "objective_before" (round-to-nearest under the same damped H),
+    "objective_after", "seconds" (factor + sweep)}}, "skipped": {name: reason}, "seconds": {"capture", "factor", "sweep"}}."""
+    be = backend.get()
+    skipped, todo = OrderedDict(), []
+    for name, m in _quantised_layers(model):
+        why = _why_not(be, m)
+        if why is None:
+            todo.append((name, m))
+        else:
+            skipped[name] = why
+    if bias_correct:
+        from .bias_correct import bias_correct_model, remember_fp_biases
+        remember_fp_biases(model)                          # the fold in fc2's bias is that of q(W) as it is now
+    B = int(images.shape[0])
+    t0 = time.perf_counter()
+    hess = capture_hessians(model, [m for _, m in todo], images, batch_size,
+                            lambda m, args: m.quant_input(args[0]).reshape(-1, m.in_features))
     _sync(images)
     seconds = {"capture": time.perf_counter() - t0, "factor": 0.0, "sweep": 0.0}
 
@@ -160,7 +170,7 @@ def gptq_model(model, images, damp=0.01, batch_size=32, bias_correct=False):
 
 
 def main(argv=None):
-    from .packed import build_wrapped, load_plain, save_packed
+    from .packed import BIT_PLAN_HELP, build_wrapped, load_plain, plan_kwargs, save_packed
     from .report import _dataset_images
     ap = argparse.ArgumentParser(description="GPTQ weight rounding of a plain calibrated checkpoint")
     ap.add_argument("--model", required=True)
@@ -177,10 +187,11 @@ def main(argv=None):
     ap.add_argument("--dataset", default=None, help="ImageNet root: the first --images validation images instead of a seeded randn batch")
     ap.add_argument("--bias-correct", action="store_true", help="after the sweep, correct the biases on the same images (utils/bias_correct.py)")
     ap.add_argument("--device", default="cuda")
+    ap.add_argument("--bit-plan", default=None, help=BIT_PLAN_HELP)
     args = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="%(message)s")
     device = torch.device(args.device)
-    model = build_wrapped(args.model, args.config, device, img_size=args.img_size, depth=args.depth)
+    model = build_wrapped(args.model, args.config, device, img_size=args.img_size, depth=args.depth, **plan_kwargs(args.bit_plan))
     model = load_plain(model, args.checkpoint, device)
     if args.dataset:
         images = _dataset_images(args.dataset, args.model, args.images, device)

@@ -197,14 +197,39 @@ def load_plain(model, path, device):
     return model
 
 
-def build_wrapped(model_name, config_path, device, img_size=None, depth=None):
-    """The model of the zoo wrapped for loading a calibrated checkpoint (test_quant.py with --load-calibrate-checkpoint)."""
+BIT_PLAN_HELP = "adalog-bitplan-v1 file of utils/bitplan.py: the per-layer weight widths the checkpoint was calibrated with"
+
+
+def load_bit_plan(path):
+    """{module name: bits} of an adalog-bitplan-v1 file (utils/bitplan.py), or of a bare JSON object of names and widths"""
+    import json
+    with open(path) as f:
+        obj = json.load(f)
+    if isinstance(obj, dict) and "format" in obj:
+        if obj["format"] != "adalog-bitplan-v1" or not isinstance(obj.get("plan"), dict):
+            raise ValueError(f"{path}: not an adalog-bitplan-v1 file")
+        obj = obj["plan"]
+    if not isinstance(obj, dict):
+        raise ValueError(f"{path}: a bit plan is a JSON object of module names and widths")
+    return {str(k): int(v) for k, v in obj.items()}
+
+
+def plan_kwargs(path):
+    """build_wrapped's keyword for a --bit-plan flag: none when the flag was not given"""
+    return {"bit_plan": load_bit_plan(path)} if path else {}
+
+
+def build_wrapped(model_name, config_path, device, img_size=None, depth=None, bit_plan=None):
+    """The model of the zoo wrapped for loading a calibrated checkpoint (test_quant.py with --load-calibrate-checkpoint).
+    ``bit_plan``: {module name: bits}, the cfg.w_bit_plan of a mixed-width checkpoint (wrap_modules_in_net)."""
     from .models import create_model
     from .wrap_net import wrap_modules_in_net
     spec = importlib.util.spec_from_file_location("adalog_packed_cfg", config_path)
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
     cfg = mod.Config()
+    if bit_plan is not None:
+        cfg.w_bit_plan = dict(bit_plan)
     model = create_model(model_name, depth=depth, img_size=img_size)
     model = wrap_modules_in_net(model.to(device).eval(), cfg, reparam=False)
     return model.to(device).eval()
@@ -219,9 +244,10 @@ def main(argv=None):
     ap.add_argument("--img-size", type=int, default=None)
     ap.add_argument("--depth", type=int, default=None, help="truncate the block count (as the checkpoint's model was)")
     ap.add_argument("--device", default="cuda")
+    ap.add_argument("--bit-plan", default=None, help=BIT_PLAN_HELP)
     args = ap.parse_args(argv)
     device = torch.device(args.device)
-    model = build_wrapped(args.model, args.config, device, img_size=args.img_size, depth=args.depth)
+    model = build_wrapped(args.model, args.config, device, img_size=args.img_size, depth=args.depth, **plan_kwargs(args.bit_plan))
     model = load_plain(model, args.checkpoint, device)
     obj = save_packed(model, args.out)
     wb = obj["meta"]["weight_bytes"]

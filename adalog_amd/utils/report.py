@@ -334,7 +334,7 @@ def _dataset_images(root, model_name, n, device):
 
 
 def main(argv=None):
-    from .packed import build_wrapped, load_packed, load_plain
+    from .packed import BIT_PLAN_HELP, build_wrapped, load_packed, load_plain, plan_kwargs
     ap = argparse.ArgumentParser(description="Per-layer quantisation report of a calibrated checkpoint")
     ap.add_argument("--model", required=True)
     ap.add_argument("--config", required=True, help="the config file the checkpoint was calibrated with")
@@ -348,9 +348,10 @@ def main(argv=None):
     ap.add_argument("--dataset", default=None, help="ImageNet root: the first --images validation images instead of a seeded randn batch")
     ap.add_argument("--out", default=None, help="write the full report as JSON")
     ap.add_argument("--device", default="cuda")
+    ap.add_argument("--bit-plan", default=None, help=BIT_PLAN_HELP)
     args = ap.parse_args(argv)
     device = torch.device(args.device)
-    model = build_wrapped(args.model, args.config, device, img_size=args.img_size, depth=args.depth)
+    model = build_wrapped(args.model, args.config, device, img_size=args.img_size, depth=args.depth, **plan_kwargs(args.bit_plan))
     model = (load_packed if args.packed else load_plain)(model, args.checkpoint, device)
     if args.dataset:
         images = _dataset_images(args.dataset, args.model, args.images, device)

@@ -4,6 +4,8 @@
 Rules: 'qkv' -> n_V = 3; 'qkv' / 'fc1' / 'reduction' -> channel-wise search + LayerNorm fold when the
 activation bit-width equals the weight bit-width and ``reparam`` is set, with prev_layer = norm1 / norm2 / the merging
 block's norm; 'fc2' -> post-GELU AdaLog; 'head' -> cfg.qhead_a_bit; 'matmul2' -> post-softmax AdaLog.
+A config may carry ``w_bit_plan`` ({Linear name: weight bits}, utils/bitplan.py): a named layer's weight quantiser takes that width,
+the class choice above still compares the activation width with cfg.w_bit.
 The attention modules of adalog_amd.utils.models already expose matmul1/matmul2, so no forward patching is needed.
 """
 from torch import nn
@@ -24,7 +26,23 @@ def _parent_and_leaf(module_dict, name):
     return father_name, module_dict[father_name], name[idx + 1:]
 
 
+def _checked_plan(model, cfg):
+    """cfg.w_bit_plan -- {name of an nn.Linear: weight bits}, as utils/bitplan.py writes it -- or {} when the config carries none.
+    7 bits is the bound the int8 operand routes of quant_layers/linear.py state."""
+    plan = getattr(cfg, "w_bit_plan", None)
+    if not plan:
+        return {}
+    linears = {name for name, m in model.named_modules() if isinstance(m, nn.Linear)}
+    for name, bits in plan.items():
+        if name not in linears:
+            raise ValueError(f"config w_bit_plan names '{name}', which is no nn.Linear of the model")
+        if isinstance(bits, bool) or int(bits) != bits or not 2 <= int(bits) <= 7:
+            raise ValueError(f"config w_bit_plan gives '{name}' {bits!r} bits: a width must be an integer in [2, 7]")
+    return {name: int(bits) for name, bits in plan.items()}
+
+
 def wrap_modules_in_net(model, cfg, reparam=False):
+    plan = _checked_plan(model, cfg)
     module_dict = {}
     for name, module in list(model.named_modules()):
         module_dict[name] = module
@@ -56,7 +74,7 @@ def wrap_modules_in_net(model, cfg, reparam=False):
         elif isinstance(module, nn.Linear):
             cur_a_bit = cfg.qhead_a_bit if 'head' in name else cfg.a_bit
             kw = dict(in_features=module.in_features, out_features=module.out_features, bias=module.bias is not None,
-                      mode='raw', w_bit=cfg.w_bit, a_bit=cur_a_bit, calib_batch_size=cfg.calib_batch_size,
+                      mode='raw', w_bit=plan.get(name, cfg.w_bit), a_bit=cur_a_bit, calib_batch_size=cfg.calib_batch_size,
                       search_round=cfg.search_round, eq_n=cfg.eq_n, n_V=3 if 'qkv' in name else 1, fpcs=cfg.fpcs,
                       steps=cfg.steps)
             if cur_a_bit == cfg.w_bit and reparam and ('qkv' in name or 'reduction' in name or 'fc1' in name):

@@ -591,6 +591,27 @@ int adalog_gptq_sweep_f32(const float* w, int64_t R, int64_t K, int64_t ldw, con
                           int per_row, int n_bits, const double* U, int64_t ldu, float* what, uint8_t* codes, double* objective,
                           void* stream);
 
+/* ---- Hessian bit cost of a layer's weight at several widths in one launch (utils/bitplan.py; no counterpart in the reference)
+ * For width i (bits[i], a HOST array of n_widths entries) and row r of w[R][K] (rows ldw elements apart), with H fp64 [K][K]
+ * (rows ldh apart) SYMMETRIC -- the kernel reads whole rows of H and may be changed to read either triangle:
+ *   bits[i] == 0:       d_j = double(w[r][j])                     (the signal row: cost = w H w^T, the layer's output energy)
+ *   2 <= bits[i] <= 8:  c_j = clamp(rne(w[r][j] / s) + rne(z), 0, 2^bits[i] - 1);  q_j = (c_j - rne(z)) * s   (fp32: the rounding rule
+ *                       of adalog_gptq_sweep_f32 and adalog_pack_codes_f32);  d_j = double(w[r][j]) - double(q_j)
+ *   cost[i][r] = sum_j sum_k d_j * H[j][k] * d_k                  (products and sums in fp64)
+ * with s, z the quantiser of width i: scale / zero_point are [n_widths][1] when per_row = 0 and [n_widths][R] when 1 (the entries
+ * of a signal row are not used).  cost is fp64 [n_widths][R].  The summation order is the kernel's own and fixed: no floating-point
+ * atomics, two calls return the same bits; against an exact evaluation the error is at most (2K + 8) 2^-53 sum_jk |d_j| |H_jk| |d_k|.
+ * w 4-byte, cost 8-byte, H 16-byte aligned, ldh even.  workspace: adalog_bit_cost_workspace_bytes(R, K, n_widths) bytes, 8-byte aligned
+ * (0: none needed; -1: shape not taken); its contents need not survive the call.
+ * adalog_bit_cost_ok: 1 when the kernel takes the shape -- 1 <= R <= 2^31, K a multiple of 32 with 32 <= K <= 4096 (the GPTQ sweep's
+ * domain), 1 <= n_widths <= 8 -- else 0 (host only); adalog_bit_cost_f32 returns -1 for any other shape or width, before the
+ * device is touched. */
+int adalog_bit_cost_ok(int64_t R, int64_t K, int n_widths);
+int64_t adalog_bit_cost_workspace_bytes(int64_t R, int64_t K, int n_widths);
+int adalog_bit_cost_f32(const float* w, int64_t R, int64_t K, int64_t ldw, const float* scale, const float* zero_point, int per_row,
+                        const int* bits, int n_widths, const double* H, int64_t ldh, double* cost, void* workspace,
+                        int64_t workspace_bytes, void* stream);
+
 /* ---- K17  BRECQ / AdaRound block reconstruction: fused straight-through backward passes and AdaRound kernels
  * adalog_uniform_fq_backward: gradients of the training form y = (clamp(round_ste(x/s) + round_ste(zp), 0, 2L-1) - round_ste(zp)) * s
  *   (reference quantizers/uniform.py:29-35 + _ste.py:5-6):  gx = gy*[inside];  gscale[ch] = sum gy*((q - z) - [inside]*x/s);
