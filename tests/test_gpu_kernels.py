@@ -774,6 +774,7 @@ def test_gemm_score_candidates_in_columns(ops, dtype):
 
 
 # ------------------------------------------------------------------------------------------------ K17 (BRECQ)
+# (these kernels against fp64 at their edges -- bit widths, tails, clamp edges, ties: tests/test_gpu_brecq_kernels.py)
 @pytest.mark.parametrize("layout", ["tensor", "heads", "rows"])
 def test_uniform_backward(ops, layout):
     gen = g(41)
