@@ -41,6 +41,7 @@ namespace {
 #include "gemm_k_stream.inc"
 #include "gemm_k_slab.inc"
 #include "gemm_k_grp.inc"
+#include "gemm_k_avw.inc"
 #include "gemm_finish.inc"
 
 }  // namespace
@@ -825,6 +826,57 @@ extern "C" int adalog_gemm_score_avq(const void* A, int64_t sAg, int M, int N, i
                                       : adalog_launch<k_gemm_avq<4, 4, 1>>("k_gemm_avq<4,bf16>", 80 * 1024, wgs, 256, shm, st, p));
     if (e) return e;
     ADALOG_LAUNCH_CHECK("adalog_gemm_score_avq");
+    return 0;
+}
+
+// softmax.v, search over the uniform quantiser of v (reference quant_layers/matmul.py:173-201): the launch of adalog_gemm_score with
+// dtype 4 (bf16 rows x fp8 candidate columns, trimmed K: k_gemm_grpk8t) without its packed candidate operand -- the P quantisations
+// of v^T x [G][N][K] (fp32, rows ldx, groups sg apart) are generated inside the kernel (k_gemm_avw_gen) from the candidates' scales
+// (sb, the epilogue's column factors) and zero points (zp, same indexing).  Same items on the same grid, same MFMA and reduction
+// order: the partials equal those of the packed launch bit for bit wherever that launch exists.
+//   A: the fixed operand, packed bf16 [G][M <= 224][Kp] (zero past K; Kp a multiple of 8); K <= 200 (13 MFMAs); N a multiple of 32;
+//   P = 64, 128 or 256 candidates of <= 4 bits; partial: per-workgroup fp64 accumulators [workgroups][gmod][256].
+// adalog_gemm_score_avw_ok: 0 when the shape is not taken, otherwise the number of workgroups (the partial buffer's leading extent).
+// The kernel is built for k_gemm_grpk8t's family (193 .. 200 keys, 129 .. 224 rows): a block always costs 13 MFMAs and an item the
+// load of the whole LDS image (M <= 224: at most 90 064 bytes), so shorter K or fewer rows are computed correctly but wastefully.  The
+// predicate takes them (the tests run them); the search asks for this form only above 64 keys, where it ran k_gemm_grpk8t --
+// windows (K <= 64) stay on k_gemm_winb.
+static int avw_wgs(int M, int N, int G, int gmod, int P, int64_t k_valid, int64_t Kp, int n_bits) {
+    if (!(P == 64 || P == 128 || P == 256) || M < 1 || M > 224 || N < 32 || N % 32 || k_valid < 1 || k_valid > 200 || Kp < k_valid || Kp % 8 ||
+        n_bits < 1 || n_bits > 4 || gmod < 1 || G < 1 || G % gmod || (int64_t)N * P >= ((int64_t)1 << 30))
+        return 0;
+    const Layout L = layout_of(M, N * P, 1, G, gmod, P, 1, true, k_valid * 2, Kp * 2, true, 1);
+    return (L.stream && L.acc && !L.slab && L.wgs >= 1) ? L.wgs : 0;
+}
+extern "C" int adalog_gemm_score_avw_ok(int M, int N, int G, int gmod, int P, int64_t k_valid, int64_t Kp, int n_bits) {
+    return avw_wgs(M, N, G, gmod, P, k_valid, Kp, n_bits);
+}
+extern "C" int adalog_gemm_score_avw(const void* A, int64_t sAg, int M, int N, int64_t Kp, int64_t k_valid, int G, int gmod,
+                                     const float* x, int64_t ldx, int64_t sg, const float* zp, int n_bits, const float* ref, int64_t sRg,
+                                     int P, const float* sa, int64_t sa_c, int64_t sa_g, float sa_mul, const float* sb, int64_t sb_c,
+                                     int64_t sb_g, float* partial, int64_t partial_elems, void* stream) {
+    ADALOG_ARG_CHECK(A && x && zp && ref && sa && sb && partial, "gemm_score_avw: null pointer");
+    const int wgs = avw_wgs(M, N, G, gmod, P, k_valid, Kp, n_bits);
+    ADALOG_ARG_CHECK(wgs > 0, "gemm_score_avw: shape not taken (adalog_gemm_score_avw_ok)");
+    ADALOG_ARG_CHECK((((uintptr_t)A) & 15) == 0 && (sAg * 2) % 16 == 0 && (((uintptr_t)partial) & 7) == 0 && (((uintptr_t)x) & 3) == 0,
+                     "gemm_score_avw: operand / accumulator alignment");
+    ADALOG_ARG_CHECK(ldx >= k_valid && (int64_t)N * ldx * 4 < ((int64_t)1 << 31), "gemm_score_avw: rows of x shorter than K, or a group of x beyond 32-bit addressing");
+    ADALOG_ARG_CHECK(partial_elems >= (int64_t)2 * wgs * gmod * BN2, "gemm_score_avw: partial buffer too small");
+    GemmArgs p{};
+    p.A = (const uint8_t*)A; p.sAg = sAg * 2; p.M = M; p.N = N * P; p.Kb = Kp; p.KbA = Kp * 2; p.Kvb = k_valid; p.C = 1; p.G = G; p.gmod = gmod;
+    p.ref = ref; p.ldr = 1; p.sRg = sRg; p.ref_cs = M; p.ref_div = P;
+    p.sa = sa; p.sa_c = sa_c; p.sa_g = sa_g; p.sa_mul = sa_mul; p.sb = sb; p.sb_c = sb_c; p.sb_g = sb_g;
+    p.wg_acc = (double*)partial; p.partial = partial;
+    p.gen_x = x; p.gen_ldx = ldx; p.gen_sg = sg; p.gen_K = (int)k_valid; p.gen_zp = zp; p.gen_qmax = (float)((1 << n_bits) - 1);
+    grp_chunks(p, N * P, wgs, G);                                  // k_gemm_grpk8t's items
+    const size_t shm = (size_t)(M + 1) * 400 + 64;            // [M + 1 rows][25 slots] and a zero tail
+    hipStream_t st = (hipStream_t)stream;
+    if (const int e = with_nj(P, [&](auto nj) {
+            constexpr int NJ = decltype(nj)::value;
+            return M > 192 ? adalog_launch<k_gemm_avw_gen<NJ, true>>("k_gemm_avw_gen<13,bf16>", 160 * 1024, (unsigned)wgs, NJ * 64, shm, st, p)
+                           : adalog_launch<k_gemm_avw_gen<NJ, false>>("k_gemm_avw_gen<13,bf16>", 160 * 1024, (unsigned)wgs, NJ * 64, shm, st, p);
+        })) return e;
+    ADALOG_LAUNCH_CHECK("adalog_gemm_score_avw");
     return 0;
 }
 

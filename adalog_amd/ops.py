@@ -776,6 +776,46 @@ def gemm_score_avq(A, src3, q_all, lut, n_bits: int, M: int, N: int, P: int, G: 
     return PendingScores(partial, MT, Npad if mode != 1 else N, Npad, P, G, gmod, False, False, mode, norm, N).finish()
 
 
+def gemm_score_avw_ok(M: int, N: int, G: int, gmod: int, P: int, k_valid: int, Kp: int, n_bits: int) -> int:
+    """Workgroups of the gemm_score_avw launch of this shape (M attention rows, N head-dim columns of v, P candidates, rows of the
+    fixed operand Kp elements long), 0 when the kernel does not take it: <= 4-bit candidates, P = 64, 128 or 256, N a multiple of
+    32, M <= 224, K <= 200, Kp a multiple of 8."""
+    return int(_lib.load().adalog_gemm_score_avw_ok(int(M), int(N), int(G), int(gmod), int(P), int(k_valid), int(Kp), int(n_bits)))
+
+
+def gemm_score_avw(A, src3, zp, n_bits: int, M: int, N: int, P: int, G: int, gmod: int, ref, sa: Strided, sb: Strided, keep_h: bool,
+                   norm: float, sa_mul: float = 1.0):
+    """gemm_score(BF16_FP8, A, pack_uniform(src3, sb.t, zp, ..., FP8, c_inner=True), M, N, P, ..., ref_div=P, ref_transposed=True,
+    defer=True) of the softmax.v weight search without the packed candidate operand: src3 [G, N, K] fp32 (v^T, K-contiguous) is
+    quantised inside the kernel (adalog_gemm_score_avw), the same scores bit for bit.  sb: the candidates' scales as the epilogue's
+    column factors (Strided(scale [P, H], c=H, g=0|1)); zp: their zero points, same layout.  -> PendingScores."""
+    lib = _lib.load()
+    sa, sb = sa.checked(), sb.checked()
+    src3, zp, ref = _f32c(src3, "src"), _f32c(zp, "zero_point"), _f32c(ref, "ref")
+    Gs, Ns, K = src3.shape
+    Kp = A.shape[-1]
+    assert (Gs, Ns) == (G, N) and A.shape[-2] == M and A.is_contiguous() and A.dtype == torch.bfloat16 and zp.shape == sb.t.shape
+    assert ref.shape[-1] == M and ref.shape[-2] == N
+    wgs = gemm_score_avw_ok(M, N, G, gmod, P, K, Kp, n_bits)
+    if not wgs:
+        raise ValueError("gemm_score_avw: shape not taken (gemm_score_avw_ok)")
+    sAg = 0 if A.shape[1] == 1 and G > 1 else A.stride(1)
+    sRg = 0 if G == 1 else M * N
+    n_part = 2 * wgs * gmod * 256
+    partial = torch.empty(n_part // 2, dtype=torch.float64, device=A.device).view(torch.float32)
+    if GEMM_EVENTS is not None:
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ev0.record()
+    rc = lib.adalog_gemm_score_avw(A.data_ptr(), sAg, M, N, Kp, K, G, gmod, src3.data_ptr(), K, N * K, zp.data_ptr(), int(n_bits),
+                                   ref.data_ptr(), sRg, P, sa.t.data_ptr(), sa.c, sa.g, float(sa_mul), sb.t.data_ptr(), sb.c, sb.g,
+                                   partial.data_ptr(), n_part, _stream())
+    if GEMM_EVENTS is not None:
+        ev1.record()
+        GEMM_EVENTS.append((BF16_FP8, M, N, K, P, G, ev0, ev1, lib.adalog_last_kernel().decode()))
+    _lib.check(rc, "adalog_gemm_score_avw")
+    return PendingScores(partial, wgs, 256, 256, P, G, gmod, keep_h, False, 2, norm, N)
+
+
 def gemm_out(dtype: int, A, B, M: int, N: int, G: int, gmod: int, sa: Strided, sb: Strided, bias: Optional[Strided],
              sa_mul: float = 1.0, addend=None, heads_last: int = 0):
     """Quantised forward: out[g] = (A[g] . B[g]^T) * sa * sb[n] + bias[n] (+ addend[g])   -> fp32 [G, M, N].

@@ -28,6 +28,8 @@ GEN_MM = os.environ.get('ADALOG_GEN_MM', 'all')
 GEN_AVQ = os.environ.get('ADALOG_GEN_AVQ', '1') != '0'
 MIXED_B_SEARCH = os.environ.get('ADALOG_MIXED_B', '1') != '0'     # softmax.v weight search: fp8 candidates against the bf16 probabilities
 AV_KTRIM = os.environ.get('ADALOG_AV_KTRIM', '1') != '0'         # ... with rows of 208 instead of 256 elements where the kernel takes them (ops.gemm_mixed_ktrim)
+# ... and with the candidates generated inside the scoring kernel instead of packed as fp8 (ops.gemm_score_avw; same scores); 0 = packed
+AV_GEN = os.environ.get('ADALOG_AV_GEN', '1') != '0'
 
 
 class MinMaxQuantMatMul(nn.Module):
@@ -204,12 +206,13 @@ class AsymmetricallyBatchingQuantMatMul(PTQSLBatchingQuantMatMul):
         return be.pack_uniform(self._bt3_packable(B), s, z, 1, 0, H, 1 if H > 1 else 0, 0, self.B_quantizer.n_bits, dt,
                                k_align=al)
 
-    def _score(self, which, fixed, scale, zp, dt=I8, fixed_sa=None, sa_mul=1.0, defer=False):
+    def _score(self, which, fixed, scale, zp, dt=I8, fixed_sa=None, sa_mul=1.0, defer=False, gen=False):
         """matmul.py:135-163 (which='A') / :173-201 (which='B') -> scores [P, H].
 
         The candidates go into the GEMM's COLUMN axis (packed candidates-innermost): the 128 candidates of one output
         row/column share one reference element per accumulator row, and tiles are full along that axis.  For the
         A-operand search the product is evaluated transposed (D^T = B . A_p^T), reading raw_out transposed in place.
+        ``gen`` (mixed B search): the search asks for the candidates to be generated inside the kernel where it takes the shape.
         """
         be = backend.get()
         H = self._heads()
@@ -244,6 +247,14 @@ class AsymmetricallyBatchingQuantMatMul(PTQSLBatchingQuantMatMul):
             pend = be.gemm_score_gen(dt, fixed, src, zc, bits, mrows, ncols, P, G, H, ref, sa, sb, self.head_channel_wise,
                                      self._norm(A, S, Sp), sa_mul=sa_mul)
             return pend if defer else pend.finish()
+        if (gen and mixed and which == "B" and hasattr(be, "gemm_score_avw") and src.dtype == torch.float32 and src.is_contiguous()
+                and be.gemm_score_avw_ok(S, Sp, G, H, P, K, fixed.shape[-1], bits)):
+            # the P quantisations of v are generated inside the kernel (adalog_gemm_score_avw): nothing is packed
+            sc, zc = scale.contiguous(), zp.contiguous()
+            sa = fixed_sa if fixed_sa is not None else Strided(self.A_quantizer.scale.data.view(-1), g=pg)
+            pend = be.gemm_score_avw(fixed, src, zc, bits, S, Sp, P, G, H, self._ref3_t(), sa, Strided(sc, c=H, g=pg),
+                                     self.head_channel_wise, self._norm(A, S, Sp), sa_mul=sa_mul)
+            return pend if defer else pend.finish()
         out = []
         for s0 in range(0, P, chunk):
             e = min(P, s0 + chunk)
@@ -274,7 +285,7 @@ class AsymmetricallyBatchingQuantMatMul(PTQSLBatchingQuantMatMul):
             else self.B_quantizer.codes_fit(-128, 127)
         return b_ok and (isinstance(self, PostSoftmaxAsymmetricallyBatchingQuantMatMul) or self.A_quantizer.codes_fit(-128, 127))
 
-    def _fpcs(self, which, fpcs_width=16, steps=6, fixed=None, dt=I8, fixed_sa=None, sa_mul=1.0, checked=False):
+    def _fpcs(self, which, fpcs_width=16, steps=6, fixed=None, dt=I8, fixed_sa=None, sa_mul=1.0, checked=False, gen=False):
         """matmul.py:243-262."""
         if not checked and search.round_is_redundant(self, which, self.B_quantizer if which == "A" else self.A_quantizer):
             return                                 # the other operand's quantiser is what this search saw last round
@@ -282,7 +293,7 @@ class AsymmetricallyBatchingQuantMatMul(PTQSLBatchingQuantMatMul):
         scale, zp, delta = search.matmul_grid(x, self.B_quantizer.n_bits, self.eq_n, self.head_channel_wise)
         if fixed is None:
             fixed = self._pack_fixed("B" if which == "A" else "A", dt)
-        fn = lambda s, z, t: self._score(which, fixed, s, z, dt, fixed_sa, sa_mul, defer=True)
+        fn = lambda s, z, t: self._score(which, fixed, s, z, dt, fixed_sa, sa_mul, defer=True, gen=gen)
         q = self.A_quantizer if which == "A" else self.B_quantizer
         res = search.fpcs(scale, zp, None, delta, fn, steps, fpcs_width, self.eq_n, None,
                           commit_to=search.commit_targets(q.scale, q.zero_point, None))
@@ -456,7 +467,8 @@ class PostSoftmaxAsymmetricallyBatchingQuantMatMul(AsymmetricallyBatchingQuantMa
             ap = self._pack_A_adalog(self._a3(A), qv, self.A_quantizer.scale.data.view(-1), 1, True,
                                      k_align=self._mixed_kalign()[1] if mixed else self._kalign())
             self._fpcs("B", steps=self.steps, fixed=ap, dt=BF16_FP8 if mixed else BF16,
-                       fixed_sa=Strided(self.A_quantizer.scale.data.view(-1)), sa_mul=self._ts32(), checked=True)
+                       fixed_sa=Strided(self.A_quantizer.scale.data.view(-1)), sa_mul=self._ts32(), checked=True,
+                       gen=mixed and AV_GEN and K > 64)    # (K <= 64: windows, the mixed launch there is k_gemm_winb and stays)
         self.calibrated = True
         search.begin_rounds(self)
         search.forget_grids()

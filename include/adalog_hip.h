@@ -179,6 +179,17 @@ int adalog_gemm_score_avq(const void* A, int64_t sAg, int M, int N, int64_t Kp, 
                           int P, const float* sa, int64_t sa_c, int64_t sa_g, float sa_mul, const float* sb, int64_t sb_c,
                           int64_t sb_g, float* partial, int64_t partial_elems, void* stream);
 int adalog_gemm_score_avq_ok(int M, int N, int G, int gmod, int P, int64_t k_valid, int64_t Kp, int n_bits);
+/* softmax.v, search over the uniform quantiser of v (reference quant_layers/matmul.py:173-201): adalog_gemm_score with dtype 4
+ *   (trimmed K) without its packed candidate operand -- the P (64, 128 or 256) quantisations of v^T x [G][N][K] (fp32, rows ldx, groups
+ *   sg apart; N a multiple of 32, K <= 200) are generated inside the kernel from the candidates' scales sb (the column factors) and
+ *   zero points zp (same indexing), <= 4 bits.  A: the fixed operand as packed bf16 [G][M <= 224][Kp] (zero past K, Kp a multiple of
+ *   8, groups sAg elements apart); ref [G][N][M]; partial: fp64 accumulators [workgroups][gmod][256] (finish mode 2).  The partials
+ *   equal those of the packed launch bit for bit.  adalog_gemm_score_avw_ok: 0 = shape not taken, else the number of workgroups. */
+int adalog_gemm_score_avw(const void* A, int64_t sAg, int M, int N, int64_t Kp, int64_t k_valid, int G, int gmod, const float* x,
+                          int64_t ldx, int64_t sg, const float* zp, int n_bits, const float* ref, int64_t sRg, int P, const float* sa,
+                          int64_t sa_c, int64_t sa_g, float sa_mul, const float* sb, int64_t sb_c, int64_t sb_g, float* partial,
+                          int64_t partial_elems, void* stream);
+int adalog_gemm_score_avw_ok(int M, int N, int G, int gmod, int P, int64_t k_valid, int64_t Kp, int n_bits);
 int adalog_finish_scores(const float* partial, float* scores, int MT, int N, int Npad, int C, int G, int gmod, int keep_h,
                          int keep_n, int cand_inner, double norm, void* workspace, int64_t workspace_bytes, void* stream);
 /* Scratch for the two-stage form used when cand_inner = 1 and keep_n = 0 (sums of 10^4..10^5 terms per candidate): bytes
