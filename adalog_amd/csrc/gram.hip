@@ -684,7 +684,11 @@ static bool nj_supported(int nj) { return nj == 1 || nj == 2 || nj == 3 || nj ==
 extern "C" int adalog_gram_supported(int T, int O, int K, int a_bits, int w_bits, int P) {
     const GramPlan g = gram_plan(T, O, K, a_bits);
     if (!g.ok || !nj_supported(g.NJ) || w_bits < 2 || w_bits > 7 || P < 32 || P % 32 != 0) return 0;
-    if ((int64_t)128 * ((1 << w_bits) - 1) * K >= (1 << 23)) return 0;           // accumulators must fit 24 bits (v_mul_i32_i24)
+    const int64_t wq = (1 << w_bits) - 1;
+    if ((int64_t)128 * wq * K >= (1 << 23)) return 0;                            // accumulators must fit 24 bits (v_mul_i32_i24)
+    // ... and the row dot adds GRP products acc * w in an int before it goes to fp64 (gram_pass: GRP = 4 for w_bits > 4, else 16):
+    // 7-bit weights past K = 256 could wrap it (every lowest limb of G at -128 against a row of +-127)
+    if ((w_bits > 4 ? 4 : 16) * 128 * wq * wq * K >= ((int64_t)1 << 31)) return 0;
     if ((int64_t)O * P / 32 >= ((int64_t)1 << 30)) return 0;
     return 1;
 }

@@ -1795,6 +1795,13 @@ def test_gram_form_rejects_what_it_cannot_score(ops):
     assert lib.adalog_gram_supported(197, 1152, 384, 4, 4, 128) and not lib.adalog_gram_ok(197, 1152, 384, 4, 4, 128)   # one image: does not pay
     assert lib.adalog_gram_ok(6304, 1152, 384, 4, 4, 128) and lib.adalog_gram_limbs(6304, 4) == 3 and lib.adalog_gram_limbs(6304, 6) == 4
     assert lib.adalog_gram_build(None, 6304, 384, 384, None, None, 4, None, 1152, None, None, 0, None) == -1
+    # 7-bit weights: the row dot adds four products acc * w in an int, 4 * 128 * 127^2 * K < 2^31 only up to K = 256
+    assert lib.adalog_gram_supported(6304, 1152, 256, 4, 7, 128) and lib.adalog_gram_ok(25088, 768, 256, 7, 7, 128)
+    for K in (384, 512):
+        assert not lib.adalog_gram_supported(6304, 1152, K, 4, 7, 128) and not lib.adalog_gram_ok(25088, 1152, K, 4, 7, 128)
+    assert not lib.adalog_gram_supported(6304, 1152, 768, 4, 7, 128)   # (as before: the 24-bit accumulator bound)
+    for w in (2, 3, 4, 5, 6):                                           # every narrower width keeps every instantiated K
+        assert all(lib.adalog_gram_supported(6304, 1152, 32 * nj, 4, w, 128) for nj in (1, 2, 3, 4, 6, 8, 12, 16, 24))
 
 
 # ------------------------------------------------------------------------------------------------ Gram-form activation search (round 5)
