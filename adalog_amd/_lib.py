@@ -160,6 +160,8 @@ SIGNATURES = {
     "adalog_log_code_hist_f32": (i32, [p, i64, p, p, i32, p, i32, p, p]),
     "adalog_gptq_sweep_ok": (i32, [i64, i64]),
     "adalog_gptq_sweep_f32": (i32, [p, i64, i64, i64, p, p, i32, i32, p, i64, p, p, p, p]),
+    "adalog_gptq_sweep_perm_f32": (i32, [p, i64, i64, i64, p, p, i32, i32, p, i64, p, p, p, p, p]),
+    "adalog_permute_sym_f64": (i32, [p, i64, i64, p, p, i64, p]),
     "adalog_bit_cost_ok": (i32, [i64, i64, i32]),
     "adalog_bit_cost_workspace_bytes": (i64, [i64, i64, i32]),
     "adalog_bit_cost_f32": (i32, [p, i64, i64, i64, p, p, i32, p, i32, p, i64, p, p, i64, p]),

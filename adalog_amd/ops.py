@@ -355,16 +355,25 @@ def unpack_codes(packed, K: int, scale, zero_point, n_bits: int, dtype: int = F3
 
 
 # ------------------------------------------------------------------------------------------------ GPTQ (csrc/gptq.hip)
+def _perm_i32(perm, K, device, who):
+    if not isinstance(perm, torch.Tensor) or perm.dtype != torch.int32 or tuple(perm.shape) != (K,) or perm.device != device:
+        raise ValueError(f"{who}: perm must be an int32 [{K}] tensor on the HIP device of the other operands")
+    return perm if perm.is_contiguous() else perm.contiguous()
+
+
 def gptq_sweep_ok(R: int, K: int) -> bool:
     """Whether gptq_sweep takes a weight of R rows and K columns: K a multiple of 32 in [32, 4096], R >= 1."""
     return bool(_lib.load().adalog_gptq_sweep_ok(int(R), int(K)))
 
 
-def gptq_sweep(w2, scale, zero_point, n_bits: int, U, want_codes: bool = False, want_objective: bool = False):
+def gptq_sweep(w2, scale, zero_point, n_bits: int, U, want_codes: bool = False, want_objective: bool = False, perm=None):
     """The GPTQ column sweep of fp32 w2 [R, K] in one launch: column j of every row is quantised with the row's asymmetric uniform
     quantiser (scale / zero_point: one element, or one per row), and its rounding error is pushed onto the columns behind it through
     row j of ``U``, the fp64 upper-triangular [K, K] factor of the inverse Hessian (H^-1 = U^T U).  The recurrence is specified in
     include/adalog_hip.h and has one result in IEEE arithmetic; two calls return the same bits.
+    ``perm`` (act-order; an int32 [K] device tensor, a permutation of 0 .. K-1): step j works on column perm[j], ``U`` factors the
+    permuted Hessian H[perm][:, perm], and the outputs come back in natural column order -- the gather and the scatter happen inside
+    the kernel.  The call checks ``perm`` on the device first and waits for the verdict; None takes the natural-order entry point.
     -> What fp32 [R, K] [, codes uint8 [R, K]] [, objective fp64 [R]: sum_j e_j^2 = (w - What)^T H (w - What)]."""
     if w2.dim() != 2:
         raise ValueError("gptq_sweep: the weight must be viewed as [rows, cols]")
@@ -381,11 +390,32 @@ def gptq_sweep(w2, scale, zero_point, n_bits: int, U, want_codes: bool = False, 
     what = torch.empty_like(w2)
     codes = torch.empty((R, K), dtype=torch.uint8, device=w2.device) if want_codes else None
     obj = torch.empty((R,), dtype=torch.float64, device=w2.device) if want_objective else None
-    rc = _lib.load().adalog_gptq_sweep_f32(w2.data_ptr(), R, K, K, _ptr(scale), _ptr(zero_point), per_row, int(n_bits), U.data_ptr(), K,
-                                          what.data_ptr(), _ptr(codes), _ptr(obj), _stream())
-    _lib.check(rc, "adalog_gptq_sweep_f32")
+    if perm is None:
+        rc = _lib.load().adalog_gptq_sweep_f32(w2.data_ptr(), R, K, K, _ptr(scale), _ptr(zero_point), per_row, int(n_bits), U.data_ptr(), K,
+                                              what.data_ptr(), _ptr(codes), _ptr(obj), _stream())
+        _lib.check(rc, "adalog_gptq_sweep_f32")
+    else:
+        perm = _perm_i32(perm, K, w2.device, "gptq_sweep")
+        rc = _lib.load().adalog_gptq_sweep_perm_f32(w2.data_ptr(), R, K, K, _ptr(scale), _ptr(zero_point), per_row, int(n_bits),
+                                                   U.data_ptr(), K, perm.data_ptr(), what.data_ptr(), _ptr(codes), _ptr(obj), _stream())
+        _lib.check(rc, "adalog_gptq_sweep_perm_f32")
     out = (what,) + ((codes,) if want_codes else ()) + ((obj,) if want_objective else ())
     return out if len(out) > 1 else what
+
+
+def permute_sym(H, perm):
+    """H[perm][:, perm] of a float64 [K, K] device tensor (K <= 4096) as a new contiguous tensor, gathered by one kernel: the Hessian in
+    the column order of an act-order sweep.  ``perm``: int32 [K] on the same device, a permutation of 0 .. K-1 (checked on the device
+    before H is indexed with it)."""
+    if not H.is_cuda or H.dtype != torch.float64 or H.dim() != 2 or H.shape[0] != H.shape[1]:
+        raise ValueError("permute_sym: H must be a square float64 tensor on the HIP device")
+    K = int(H.shape[0])
+    perm = _perm_i32(perm, K, H.device, "permute_sym")
+    H = H if H.is_contiguous() else H.contiguous()
+    out = torch.empty_like(H)
+    rc = _lib.load().adalog_permute_sym_f64(H.data_ptr(), K, K, perm.data_ptr(), out.data_ptr(), K, _stream())
+    _lib.check(rc, "adalog_permute_sym_f64")
+    return out
 
 
 # ------------------------------------------------------------------------------------------------ bit cost (csrc/bitcost.hip)

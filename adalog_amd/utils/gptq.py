@@ -16,10 +16,17 @@ The scale and zero point do not change and the new weight lies on the quantiser'
 so the result is an ordinary calibrated model: quant_forward, the report, validation and the packed export work on it unchanged.
 
 Eligible: quantised Linear layers whose weight utils.packed would store as codes (committed asymmetric uniform quantiser, 2..8 bits, one
-scale or one per row) and whose shape ops.gptq_sweep_ok takes.  Everything else keeps its weight and is listed with the reason; the
-patch-embedding convolution is out of scope here.
+scale or one per row) and whose shape ops.gptq_sweep_ok takes.  Everything else keeps its weight and is listed with the reason.
+
+``sweep_conv=True`` adds the patch-embedding convolution (kernel == stride, no padding: a GEMM over flattened patches,
+quant_layers/conv.py) under the same conditions, K = C * kh * kw; the rows of its Hessian are the patches, flattened in the weight's
+(c, kh, kw) order.  ``act_order=True`` visits the columns in the order of decreasing diag H (stable: ties to the lower index; a dead
+column counts with the diagonal 1 that damped_factor gives it): the Hessian is permuted on the device (ops.permute_sym), factored
+as before, and ops.gptq_sweep(perm=...) gathers and scatters inside the kernel, so the committed weight is in natural column order
+and the permutation is not kept.  Both are off by default: the default call commits what it always did.
 
     python -m adalog_amd.utils.gptq --model deit_small --config configs/4bit.py --checkpoint plain.pth --out gptq.pth [--packed] [--bias-correct]
+                                    [--act-order] [--sweep-conv]
 """
 import argparse
 import logging
@@ -40,10 +47,23 @@ def _sync(t):
         torch.cuda.synchronize(t.device)
 
 
-def _why_not(be, module):
+def _patch_conv_why_not(module):
+    """None for a non-overlapping patch convolution (kernel == stride, no padding: a GEMM over flattened patches), else the reason"""
+    pad = module.padding if isinstance(module.padding, tuple) else (module.padding, module.padding)
+    if not hasattr(module, "_patches") or tuple(module.kernel_size) != tuple(module.stride) or tuple(pad) != (0, 0) \
+            or tuple(module.dilation) != (1, 1) or module.groups != 1:
+        return "convolution: not a non-overlapping patch convolution (kernel == stride, no padding, groups = 1)"
+    return None
+
+
+def _why_not(be, module, sweep_conv=False):
     """None when the layer is swept, else the reason it is left as it is."""
-    if not isinstance(module, nn.Linear):
-        return CONV_REASON if isinstance(module, nn.Conv2d) else f"{type(module).__name__} is not a Linear layer"
+    if isinstance(module, nn.Conv2d):
+        why = _patch_conv_why_not(module) if sweep_conv else CONV_REASON
+        if why is not None:
+            return why
+    elif not isinstance(module, nn.Linear):
+        return f"{type(module).__name__} is not a Linear layer"
     why = _ineligible(module)
     if why is not None:
         return why
@@ -63,6 +83,22 @@ def damped_factor(H, damp):
     L = torch.linalg.cholesky(Hd)
     U = torch.linalg.cholesky(torch.cholesky_inverse(L), upper=True)
     return U.contiguous(), Hd
+
+
+def act_order_perm(H):
+    """The act-order of a captured (undamped) Hessian: int32 [K] on H's device, the columns by decreasing fp64 diagonal, ties to the
+    lower index (a stable sort).  A dead column counts with the diagonal damped_factor gives it, 1, not with its 0."""
+    d = torch.diagonal(H).detach().to("cpu", torch.float64).clone()
+    d[d == 0] = 1.0
+    return torch.argsort(d, descending=True, stable=True).to(torch.int32).to(H.device)
+
+
+def _gemm_rows(m, x):
+    """fp32 [tokens, K]: the rows of the GEMM the layer runs on its (quantised) input x -- flattened patches for a convolution"""
+    xq = m.quant_input(x)
+    if isinstance(m, nn.Conv2d):
+        return m._patches(xq)[0]
+    return xq.reshape(-1, m.in_features)
 
 
 def _quadratic(D, Hd):
@@ -92,7 +128,8 @@ def capture_hessians(model, modules, images, batch_size, rows_of):
         for m in moded:
             m.mode = "raw"
         for m in modules:
-            hess[id(m)] = torch.zeros((m.in_features, m.in_features), dtype=torch.float64, device=m.weight.device)
+            K = _rows_cols(m)[1]
+            hess[id(m)] = torch.zeros((K, K), dtype=torch.float64, device=m.weight.device)
             handles.append(m.register_forward_hook(capture))
         with torch.no_grad():
             for s in range(0, B, max(1, int(batch_size))):
@@ -106,17 +143,18 @@ def capture_hessians(model, modules, images, batch_size, rows_of):
     return hess
 
 
-def gptq_model(model, images, damp=0.01, batch_size=32, bias_correct=False):
+def gptq_model(model, images, damp=0.01, batch_size=32, bias_correct=False, act_order=False, sweep_conv=False):
     """GPTQ rounding of every eligible layer of a wrapped, calibrated ``model`` from ``images`` (on the model's device); see the module
     text.  Every module's ``mode`` is restored afterwards (quant_forward for a calibrated model).  ``bias_correct``: afterwards, the
     empirical bias correction of utils/bias_correct.py on the same images (its result under "bias_correct"), against FP biases fixed
-    before the sweep -- which also takes out of fc2's bias the shift fold the sweep made stale.
+    before the sweep -- which also takes out of fc2's bias the shift fold the sweep made stale.  ``act_order``: columns in the order of
+    decreasing diag H (act_order_perm).  ``sweep_conv``: the patch-embedding convolution is swept too.
     -> {"images", "damp", "layers": {name: {"R", "K", "n_bits", "objective_before" (round-to-nearest under the same damped H),
-    "objective_after", "seconds" (factor + sweep)}}, "skipped": {name: reason}, "seconds": {"capture", "factor", "sweep"}}."""
+    "objective_after", "seconds" (factor + sweep), "act_order"}}, "skipped": {name: reason}, "seconds": {"capture", "factor", "sweep"}}."""
     be = backend.get()
     skipped, todo = OrderedDict(), []
     for name, m in _quantised_layers(model):
-        why = _why_not(be, m)
+        why = _why_not(be, m, sweep_conv)
         if why is None:
             todo.append((name, m))
         else:
@@ -126,8 +164,7 @@ def gptq_model(model, images, damp=0.01, batch_size=32, bias_correct=False):
         remember_fp_biases(model)                          # the fold in fc2's bias is that of q(W) as it is now
     B = int(images.shape[0])
     t0 = time.perf_counter()
-    hess = capture_hessians(model, [m for _, m in todo], images, batch_size,
-                            lambda m, args: m.quant_input(args[0]).reshape(-1, m.in_features))
+    hess = capture_hessians(model, [m for _, m in todo], images, batch_size, lambda m, args: _gemm_rows(m, args[0]))
     _sync(images)
     seconds = {"capture": time.perf_counter() - t0, "factor": 0.0, "sweep": 0.0}
 
@@ -137,17 +174,23 @@ def gptq_model(model, images, damp=0.01, batch_size=32, bias_correct=False):
         rows, cols = _rows_cols(m)
         dev = m.weight.device
         t1 = time.perf_counter()
-        U, Hd = damped_factor(hess.pop(id(m)), damp)
+        H = hess.pop(id(m))
+        perm = act_order_perm(H) if act_order else None
+        U, Hd = damped_factor(H if perm is None else be.permute_sym(H, perm), damp)      # (Hd: in the sweep's column order)
         U, Hd = U.to(dev), Hd.to(dev)
         _sync(m.weight)
         t2 = time.perf_counter()
         with torch.no_grad():
             w2 = m.weight.data.reshape(rows, cols)
             scale, zp = wq.scale.data.reshape(-1), wq.zero_point.data.reshape(-1)
-            what, obj = be.gptq_sweep(w2, scale, zp, int(wq.n_bits), U, want_objective=True)
+            if perm is None:
+                what, obj = be.gptq_sweep(w2, scale, zp, int(wq.n_bits), U, want_objective=True)
+            else:
+                what, obj = be.gptq_sweep(w2, scale, zp, int(wq.n_bits), U, want_objective=True, perm=perm)
             _sync(what)
             t3 = time.perf_counter()
-            before = _quadratic(w2 - m.quant_weight_bias()[0].reshape(rows, cols), Hd)
+            d_rtn = w2 - m.quant_weight_bias()[0].reshape(rows, cols)
+            before = _quadratic(d_rtn if perm is None else d_rtn[:, perm.long()], Hd)
             after = float(obj.sum())
             m.weight.data.copy_(what.reshape(m.weight.shape))
         if hasattr(m, "invalidate_packed_weight"):
@@ -158,7 +201,7 @@ def gptq_model(model, images, damp=0.01, batch_size=32, bias_correct=False):
         seconds["factor"] += t2 - t1
         seconds["sweep"] += t3 - t2
         layers[name] = {"R": rows, "K": cols, "n_bits": int(wq.n_bits), "objective_before": before, "objective_after": after,
-                        "seconds": t3 - t1}
+                        "seconds": t3 - t1, "act_order": bool(act_order)}
         logging.info(f"gptq {name}: [{rows}, {cols}] {wq.n_bits}b  objective {before:.6g} -> {after:.6g}  "
                      f"factor (host) {t2 - t1:.3f} s, sweep {t3 - t2:.4f} s")
     logging.info(f"gptq: {len(layers)} layers swept, {len(skipped)} left; capture {seconds['capture']:.2f} s, factor (host) "
@@ -188,6 +231,8 @@ def main(argv=None):
     ap.add_argument("--bias-correct", action="store_true", help="after the sweep, correct the biases on the same images (utils/bias_correct.py)")
     ap.add_argument("--device", default="cuda")
     ap.add_argument("--bit-plan", default=None, help=BIT_PLAN_HELP)
+    ap.add_argument("--act-order", action="store_true", help="visit the columns in the order of decreasing diag H")
+    ap.add_argument("--sweep-conv", action="store_true", help="sweep the patch-embedding convolution too")
     args = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="%(message)s")
     device = torch.device(args.device)
@@ -198,7 +243,8 @@ def main(argv=None):
     else:
         size = args.img_size or getattr(getattr(model, "patch_embed", None), "img_size", (224, 224))[0]
         images = torch.randn(args.images, 3, size, size, generator=torch.Generator().manual_seed(args.seed)).to(device)
-    res = gptq_model(model, images, damp=args.damp, batch_size=args.batch_size, bias_correct=args.bias_correct)
+    res = gptq_model(model, images, damp=args.damp, batch_size=args.batch_size, bias_correct=args.bias_correct, act_order=args.act_order,
+                     sweep_conv=args.sweep_conv)
     if args.packed:
         save_packed(model, args.out)
     else:

@@ -601,6 +601,21 @@ int adalog_gptq_sweep_ok(int64_t R, int64_t K);
 int adalog_gptq_sweep_f32(const float* w, int64_t R, int64_t K, int64_t ldw, const float* scale, const float* zero_point,
                           int per_row, int n_bits, const double* U, int64_t ldu, float* what, uint8_t* codes, double* objective,
                           void* stream);
+/* Act-order: the same recurrence with the columns visited in the order perm (a DEVICE array of K entries, a permutation of 0 .. K-1).
+ * Step j works on column perm[j] of w -- run[j] = double(w[r][perm[j]]) is the only change to the recurrence, its rounding rule and its
+ * fp64 order -- and U is the upper factor of the inverse of the PERMUTED Hessian H[perm][:, perm].  what and codes are written in
+ * NATURAL order (q and c of step j at column perm[j]); objective[r] = sum of e^2 in ascending step order.  The gather and the scatter
+ * happen inside the kernel: one sweep launch, no workspace, no permuted copy of w.  In front of it a one-workgroup kernel checks perm
+ * and the call reads its verdict back (it waits for the stream and cannot be captured into a graph): -1 with the message set, and
+ * what / codes / objective untouched, when perm is null or not a permutation, and for every argument adalog_gptq_sweep_f32 rejects.
+ * The result equals tests/gptq_reference.py run on w[:, perm] with its outputs scattered back, bit for bit; with the identity perm it
+ * equals adalog_gptq_sweep_f32. */
+int adalog_gptq_sweep_perm_f32(const float* w, int64_t R, int64_t K, int64_t ldw, const float* scale, const float* zero_point,
+                               int per_row, int n_bits, const double* U, int64_t ldu, const int32_t* perm, float* what,
+                               uint8_t* codes, double* objective, void* stream);
+/* out[i][j] = H[perm[i]][perm[j]] for fp64 H [K][K] (rows ldh apart) -> out [K][K] (rows ldo apart, not H itself), 1 <= K <= 4096;
+ * perm as above, checked the same way before H is indexed with it (-1 with the message set, out untouched). */
+int adalog_permute_sym_f64(const double* H, int64_t K, int64_t ldh, const int32_t* perm, double* out, int64_t ldo, void* stream);
 
 /* ---- Hessian bit cost of a layer's weight at several widths in one launch (utils/bitplan.py; no counterpart in the reference)
  * For width i (bits[i], a HOST array of n_widths entries) and row r of w[R][K] (rows ldw elements apart), with H fp64 [K][K]
