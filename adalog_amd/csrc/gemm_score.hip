@@ -776,6 +776,25 @@ extern "C" int adalog_gemm_score_gen(int dtype, const void* A, int64_t sAg, int 
     return gemm_score_impl(c);
 }
 
+// ---- softmax.v searches with the candidate operand GENERATED inside the kernel (adalog_gemm_score_avq / _avw): what they share.
+// The Layout both are planned on -- the bf16 launch of the shape with P candidates per reference column
+static Layout av_layout(int M, int N, int G, int gmod, int P, int64_t k_valid, int64_t Kp) {
+    return layout_of(M, N * P, 1, G, gmod, P, 1, true, k_valid * 2, Kp * 2, true, 1);
+}
+// ... and the kernel arguments they share: C = 1, bf16 rows of A, transposed reference, column factors without a column stride,
+// per-workgroup fp64 accumulators, B generated from x [G][N][K].  Each entry point states its row lengths, its quantiser and its items
+// after this fill.
+static GemmArgs av_gen_args(const void* A, int64_t sAg, int M, int N, int64_t k_valid, int G, int gmod, const float* x, int64_t ldx,
+                            int64_t sg, const float* ref, int64_t sRg, int P, const float* sa, int64_t sa_c, int64_t sa_g, float sa_mul,
+                            const float* sb, int64_t sb_c, int64_t sb_g, float* partial) {
+    GemmArgs p{};
+    p.A = (const uint8_t*)A; p.sAg = sAg * 2; p.M = M; p.N = N * P; p.C = 1; p.G = G; p.gmod = gmod;
+    p.ref = ref; p.ldr = 1; p.sRg = sRg; p.ref_cs = M; p.ref_div = P;
+    p.sa = sa; p.sa_c = sa_c; p.sa_g = sa_g; p.sa_mul = sa_mul; p.sb = sb; p.sb_c = sb_c; p.sb_g = sb_g;
+    p.wg_acc = (double*)partial; p.partial = partial; p.gen_x = x; p.gen_ldx = ldx; p.gen_sg = sg; p.gen_K = (int)k_valid;
+    return p;
+}
+
 // softmax.v, log-base search of the post-softmax AdaLog quantiser (reference quant_layers/matmul.py:321-351): scores of the P = 128
 // candidate bases q against the reference, with the candidate operand (P AdaLog quantisations of the probabilities x [G][N][K]:
 // scale 1, no clamp) generated inside the kernel (k_gemm_avq) instead of packed by adalog_pack_adalog_bf16 and streamed.
@@ -783,15 +802,17 @@ extern "C" int adalog_gemm_score_gen(int dtype, const void* A, int64_t sAg, int 
 //   lut: dword table [2^n_bits + 1][P], entry [k][c] = bf16 bits of the value of bin k under base q[c] (numerator * 2^-t, what
 //        the packer writes), row 2^n_bits = 0 (the masked code);  ref [G][N][M];  sa / sb / sa_mul / partial as adalog_gemm_score
 //        (C = 1, ref_div = P, reduce_cols = 1: the per-workgroup fp64 accumulators of adalog_gemm_score_layout with dtype 1).
-static bool avq_ok(int M, int N, int G, int gmod, int P, int64_t k_valid, int64_t Kp, int n_bits) {
+// (L: where the launch's Layout goes, for the call)
+static bool avq_ok(int M, int N, int G, int gmod, int P, int64_t k_valid, int64_t Kp, int n_bits, Layout* L = nullptr) {
     static const int use_avq = getenv("ADALOG_GEMM_AVQ") ? atoi(getenv("ADALOG_GEMM_AVQ")) : 1;
     if (!use_avq || P != 128 || M < 1 || M > 64 || N < 1 || k_valid < 1 || k_valid > 208 || n_bits < 1 || n_bits > 6 || gmod < 1 || gmod > 16 ||
         G % gmod || G < 8)
         return false;
     const int nks = k_valid <= 64 ? 4 : 13;
     if (Kp < nks * 16 || (Kp * 2) % 16) return false;
-    const Layout L = layout_of(M, N * P, 1, G, gmod, P, 1, true, k_valid * 2, Kp * 2, true, 1);
-    return L.stream && L.acc && !L.slab && L.wgs * 4 >= gmod;
+    const Layout l = av_layout(M, N, G, gmod, P, k_valid, Kp);
+    if (L) *L = l;
+    return l.stream && l.acc && !l.slab && l.wgs * 4 >= gmod;
 }
 extern "C" int adalog_gemm_score_avq_ok(int M, int N, int G, int gmod, int P, int64_t k_valid, int64_t Kp, int n_bits) {
     return avq_ok(M, N, G, gmod, P, k_valid, Kp, n_bits) ? 1 : 0;
@@ -802,16 +823,12 @@ extern "C" int adalog_gemm_score_avq(const void* A, int64_t sAg, int M, int N, i
                                      const float* sb, int64_t sb_c, int64_t sb_g, float* partial, int64_t partial_elems,
                                      void* stream) {
     ADALOG_ARG_CHECK(A && x && q && lut && ref && sa && sb && partial, "gemm_score_avq: null pointer");
-    ADALOG_ARG_CHECK(avq_ok(M, N, G, gmod, P, k_valid, Kp, n_bits), "gemm_score_avq: shape not taken (adalog_gemm_score_avq_ok)");
+    Layout L{};
+    ADALOG_ARG_CHECK(avq_ok(M, N, G, gmod, P, k_valid, Kp, n_bits, &L), "gemm_score_avq: shape not taken (adalog_gemm_score_avq_ok)");
     ADALOG_ARG_CHECK((((uintptr_t)A) & 15) == 0 && (((uintptr_t)partial) & 7) == 0, "gemm_score_avq: operand / accumulator alignment");
-    const Layout L = layout_of(M, N * P, 1, G, gmod, P, 1, true, k_valid * 2, Kp * 2, true, 1);
     ADALOG_ARG_CHECK(partial_elems >= L.elems, "gemm_score_avq: partial buffer too small");
-    GemmArgs p{};
-    p.A = (const uint8_t*)A; p.sAg = sAg * 2; p.M = M; p.N = N * P; p.Kb = Kp * 2; p.Kvb = k_valid * 2; p.C = 1; p.G = G; p.gmod = gmod;
-    p.ref = ref; p.ldr = 1; p.sRg = sRg; p.ref_cs = M; p.ref_div = P;
-    p.sa = sa; p.sa_c = sa_c; p.sa_g = sa_g; p.sa_mul = sa_mul; p.sb = sb; p.sb_c = sb_c; p.sb_g = sb_g;
-    p.wg_acc = (double*)partial; p.partial = partial;
-    p.gen_x = x; p.gen_ldx = ldx; p.gen_sg = sg; p.gen_K = (int)k_valid; p.gen_q = q; p.gen_lut = lut; p.gen_nb = 1 << n_bits;
+    GemmArgs p = av_gen_args(A, sAg, M, N, k_valid, G, gmod, x, ldx, sg, ref, sRg, P, sa, sa_c, sa_g, sa_mul, sb, sb_c, sb_g, partial);
+    p.Kb = Kp * 2; p.Kvb = k_valid * 2; p.gen_q = q; p.gen_lut = lut; p.gen_nb = 1 << n_bits;
     wave_chunks(p, N, L.wgs, G, cdiv(N, AVQ_ROWS));                 // <= AVQ_ROWS attention rows per item (they are staged in LDS)
     const int nks = k_valid <= 64 ? 4 : 13;
     const size_t lut_b = (((size_t)(p.gen_nb + 1) * P + 3) & ~(size_t)3) * 4;
@@ -845,7 +862,7 @@ static int avw_wgs(int M, int N, int G, int gmod, int P, int64_t k_valid, int64_
     if (!(P == 64 || P == 128 || P == 256) || M < 1 || M > 224 || N < 32 || N % 32 || k_valid < 1 || k_valid > 200 || Kp < k_valid || Kp % 8 ||
         n_bits < 1 || n_bits > 4 || gmod < 1 || G < 1 || G % gmod || (int64_t)N * P >= ((int64_t)1 << 30))
         return 0;
-    const Layout L = layout_of(M, N * P, 1, G, gmod, P, 1, true, k_valid * 2, Kp * 2, true, 1);
+    const Layout L = av_layout(M, N, G, gmod, P, k_valid, Kp);
     return (L.stream && L.acc && !L.slab && L.wgs >= 1) ? L.wgs : 0;
 }
 extern "C" int adalog_gemm_score_avw_ok(int M, int N, int G, int gmod, int P, int64_t k_valid, int64_t Kp, int n_bits) {
@@ -862,12 +879,8 @@ extern "C" int adalog_gemm_score_avw(const void* A, int64_t sAg, int M, int N, i
                      "gemm_score_avw: operand / accumulator alignment");
     ADALOG_ARG_CHECK(ldx >= k_valid && (int64_t)N * ldx * 4 < ((int64_t)1 << 31), "gemm_score_avw: rows of x shorter than K, or a group of x beyond 32-bit addressing");
     ADALOG_ARG_CHECK(partial_elems >= (int64_t)2 * wgs * gmod * BN2, "gemm_score_avw: partial buffer too small");
-    GemmArgs p{};
-    p.A = (const uint8_t*)A; p.sAg = sAg * 2; p.M = M; p.N = N * P; p.Kb = Kp; p.KbA = Kp * 2; p.Kvb = k_valid; p.C = 1; p.G = G; p.gmod = gmod;
-    p.ref = ref; p.ldr = 1; p.sRg = sRg; p.ref_cs = M; p.ref_div = P;
-    p.sa = sa; p.sa_c = sa_c; p.sa_g = sa_g; p.sa_mul = sa_mul; p.sb = sb; p.sb_c = sb_c; p.sb_g = sb_g;
-    p.wg_acc = (double*)partial; p.partial = partial;
-    p.gen_x = x; p.gen_ldx = ldx; p.gen_sg = sg; p.gen_K = (int)k_valid; p.gen_zp = zp; p.gen_qmax = (float)((1 << n_bits) - 1);
+    GemmArgs p = av_gen_args(A, sAg, M, N, k_valid, G, gmod, x, ldx, sg, ref, sRg, P, sa, sa_c, sa_g, sa_mul, sb, sb_c, sb_g, partial);
+    p.Kb = Kp; p.KbA = Kp * 2; p.Kvb = k_valid; p.gen_zp = zp; p.gen_qmax = (float)((1 << n_bits) - 1);
     grp_chunks(p, N * P, wgs, G);                                  // k_gemm_grpk8t's items
     const size_t shm = (size_t)(M + 1) * 400 + 64;            // [M + 1 rows][25 slots] and a zero tail
     hipStream_t st = (hipStream_t)stream;
@@ -886,6 +899,34 @@ extern "C" int adalog_gemm_score_gen_ok(int dtype, int M, int N, int G, int gmod
     const MmCall c = shape_call(dtype, M, N, G, gmod, ref_div, k_valid, Kp, 1);
     const Route r = route_of(c, call_layout(c, true));
     return (r == R_WIN || r == R_GRPW) ? 1 : 0;
+}
+
+// ---- the two scoring calls with the candidate operand GENERATED inside the slab kernel (k_gemm_slab<.., GEN>): what they share.
+// One group, the packed fixed operand A [rows][Kp] against cols x P columns generated from x [cols][ldx] (K valid) with the
+// candidates (scale, zp), transposed reference [cols][rows], the slab items of the Layout.  Each entry point states its epilogue
+// factors and the candidates' strides (sa / sb_c / sb_n / row_* / bias / gen_sc / gen_sn / gen_sa) after this fill.
+static GemmArgs slab_gen_args(const Layout& L, const void* A, int rows, int64_t cols, int64_t Kp, const float* x, int64_t ldx, int K,
+                              const float* scale, const float* zp, int P, int n_bits, const float* ref, float* partial) {
+    GemmArgs p{};
+    p.A = (const uint8_t*)A; p.M = rows; p.N = (int)(cols * P); p.Kb = Kp; p.Kvb = K; p.C = 1; p.G = 1; p.gmod = 1;
+    p.ref = ref; p.ldr = 1; p.ref_cs = rows; p.ref_div = P; p.sa_mul = 1.0f; p.sb = scale;
+    p.MT = L.MT; p.NT = L.NT; p.Npad = L.Npad; p.order = 2; p.reduce_cols = 0; p.timeline = g_timeline;
+    p.partial = partial; p.slab_U = L.slab_U; p.slab_R = L.slab_R;
+    p.gen_x = x; p.gen_ldx = ldx; p.gen_K = K; p.gen_scale = scale; p.gen_zp = zp; p.gen_qmax = (float)((1 << n_bits) - 1);
+    // tie zone: the reciprocal-multiply quotient is within ~2 ulp of the IEEE one; only |quotient| <= 2^bits matters (beyond it
+    // both clamp alike), so 6e-7 * 2^bits bounds the difference with a factor of 2.5 to spare; never narrower than 1e-5
+    const float zone = 6e-7f * (float)(1 << n_bits);
+    p.gen_tie = 0.5f - (zone > 1e-5f ? zone : 1e-5f);
+    return p;
+}
+// ... and their launch.  SCORE_ACT: the kernel's second template argument (per-row factors: the activation search); form: slab_label's
+template <bool SCORE_ACT>
+static int slab_gen_launch(int form, int dtype, const Layout& L, int P, hipStream_t st, const GemmArgs& p) {
+    const size_t shm = slab_lds(p.Kvb, L.slab_nb);
+    return with_slab(dtype, L.slab_nb, P, [&](auto nr, auto dt, auto nb) {
+        constexpr int NREF = decltype(nr)::value, DT = decltype(dt)::value, NB = decltype(nb)::value;
+        return adalog_launch<k_gemm_slab<NREF, SCORE_ACT, DT, NB, true>>(slab_label(form, DT, NB), 160 * 1024, (unsigned)L.wgs, 512, shm, st, p);
+    });
 }
 
 // ---- activation-candidate scoring call with the candidate operand GENERATED inside the slab kernel (k_gemm_slab<.., GEN>)
@@ -937,27 +978,10 @@ extern "C" int adalog_score_act_gen(int dtype, const void* Wp, int M, int64_t Kp
         if (me != hipSuccess) { adalog_set_error("adalog_score_act_gen (zero bias)", me); return (int)me; }
         row_bias = zero_bias;
     }
-    GemmArgs p{};
-    p.A = (const uint8_t*)Wp; p.B = nullptr;
-    p.M = M; p.N = (int)(T * P); p.Kb = Kp; p.Kvb = K; p.C = 1; p.G = 1; p.gmod = 1;
-    p.ref = ref; p.ldr = 1; p.sRg = 0; p.ref_cs = M; p.ref_div = P;
+    GemmArgs p = slab_gen_args(L, Wp, M, T, Kp, x, ldx, K, scale, zp, P, n_bits, ref, partial);
     ADALOG_ARG_CHECK((int64_t)(T - 1) * M + M < ((int64_t)1 << 31), "score_act_gen: reference exceeds 32-bit addressing");
-    p.sa = scale; p.sa_c = 0; p.sa_mul = 1.0f; p.sb = scale; p.sb_c = 1; p.sb_n = 0;
-    p.row_scale = row_scale; p.row_bias = row_bias;
-    p.MT = L.MT; p.NT = L.NT; p.Npad = L.Npad; p.order = 2; p.reduce_cols = 0;
-    p.partial = partial; p.wg_acc = (double*)partial; p.timeline = g_timeline;
-    p.slab_U = L.slab_U; p.slab_R = L.slab_R;
-    p.gen_x = x; p.gen_ldx = ldx; p.gen_K = K; p.gen_scale = scale; p.gen_zp = zp; p.gen_sc = 1; p.gen_sn = 0; p.gen_sa = nullptr;
-    p.gen_qmax = (float)((1 << n_bits) - 1);
-    // tie zone: the reciprocal-multiply quotient is within ~2 ulp of the IEEE one; only |quotient| <= 2^bits matters (beyond it
-    // both clamp alike), so 6e-7 * 2^bits bounds the difference with a factor of 2.5 to spare; never narrower than 1e-5
-    const float zone = 6e-7f * (float)(1 << n_bits);
-    p.gen_tie = 0.5f - (zone > 1e-5f ? zone : 1e-5f);
-    const size_t shm = slab_lds(p.Kvb, L.slab_nb);
-    if (const int e = with_slab(dtype, L.slab_nb, P, [&](auto nr, auto dt, auto nb) {
-            constexpr int NREF = decltype(nr)::value, DT = decltype(dt)::value, NB = decltype(nb)::value;
-            return adalog_launch<k_gemm_slab<NREF, true, DT, NB, true>>(slab_label(1, DT, NB), 160 * 1024, (unsigned)L.wgs, 512, shm, st, p);
-        })) return e;
+    p.sa = scale; p.sb_c = 1; p.row_scale = row_scale; p.row_bias = row_bias; p.wg_acc = (double*)partial; p.gen_sc = 1;
+    if (const int e = slab_gen_launch<true>(1, dtype, L, P, st, p)) return e;
     ADALOG_LAUNCH_CHECK("adalog_score_act_gen");
     // fixed-order fp64 finish of the per-workgroup accumulators [wgs][1][256] (scores == null: left to the caller, who hands the
     // accumulators -- the start of the workspace -- to adalog_finish_scores / adalog_finish_topk_next with MT = adalog_score_act_gen_wgs)
@@ -996,29 +1020,14 @@ extern "C" int adalog_score_w_gen(int dtype, const void* Xp, int T, int64_t Kp, 
     ADALOG_ARG_CHECK(L.slab && !L.acc && Kp % BK3 == 0, "score_w_gen: shape not taken by the slab kernel (adalog_score_w_gen_ok)");
     ADALOG_ARG_CHECK(partial_elems >= L.elems, "score_w_gen: partial buffer too small");
     hipStream_t st = (hipStream_t)stream;
-    GemmArgs p{};
-    p.A = (const uint8_t*)Xp; p.B = nullptr;
-    p.M = T; p.N = O * P; p.Kb = Kp; p.Kvb = K; p.C = 1; p.G = 1; p.gmod = 1;
-    p.ref = ref; p.ldr = 1; p.sRg = 0; p.ref_cs = T; p.ref_div = P;
+    GemmArgs p = slab_gen_args(L, Xp, T, O, Kp, W, ldw, K, scale, zp, P, n_bits, ref, partial);
     ADALOG_ARG_CHECK((int64_t)(O - 1) * T + T < ((int64_t)1 << 31), "score_w_gen: reference exceeds 32-bit addressing");
-    p.sa = sa; p.sa_c = 0; p.sa_mul = 1.0f; p.sb = scale; p.sb_c = O; p.sb_n = 1;
-    p.bias = bias; p.bi_c = 0; p.bi_g = 0; p.bi_n = 1;
-    p.MT = L.MT; p.NT = L.NT; p.Npad = L.Npad; p.order = 2; p.reduce_cols = 0;
-    p.partial = partial; p.timeline = g_timeline;
-    p.slab_U = L.slab_U; p.slab_R = L.slab_R;
-    p.gen_x = W; p.gen_ldx = ldw; p.gen_K = K; p.gen_scale = scale; p.gen_zp = zp; p.gen_sc = O; p.gen_sn = 1; p.gen_sa = sa;
-    p.gen_qmax = (float)((1 << n_bits) - 1);
-    const float zone = 6e-7f * (float)(1 << n_bits);
-    p.gen_tie = 0.5f - (zone > 1e-5f ? zone : 1e-5f);
-    const size_t shm = slab_lds(p.Kvb, L.slab_nb);
+    p.sa = sa; p.sb_c = O; p.sb_n = 1; p.bias = bias; p.bi_n = 1; p.gen_sc = O; p.gen_sn = 1; p.gen_sa = sa;
     {   // a slab that is not cut has unused pieces: they must read as zero
         const hipError_t me = hipMemsetAsync(partial, 0, (size_t)L.elems * sizeof(float), st);
         if (me != hipSuccess) { adalog_set_error("adalog_score_w_gen (clear partials)", me); return (int)me; }
     }
-    if (const int e = with_slab(dtype, L.slab_nb, P, [&](auto nr, auto dt, auto nb) {
-            constexpr int NREF = decltype(nr)::value, DT = decltype(dt)::value, NB = decltype(nb)::value;
-            return adalog_launch<k_gemm_slab<NREF, false, DT, NB, true>>(slab_label(2, DT, NB), 160 * 1024, (unsigned)L.wgs, 512, shm, st, p);
-        })) return e;
+    if (const int e = slab_gen_launch<false>(2, dtype, L, P, st, p)) return e;
     ADALOG_LAUNCH_CHECK("adalog_score_w_gen");
     return 0;
 }

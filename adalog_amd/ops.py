@@ -16,8 +16,9 @@ from . import _lib, _torch_ops
 
 I8, BF16, F32, FP8 = 0, 1, 2, 3        # FP8: e4m3 bytes holding q - z of <= 4-bit layers exactly (same MFMA rate as int8)
 BF16_FP8 = 4                           # gemm_score only: bf16 rows x fp8 candidate columns, converted in registers (gemm_mixed_ok)
-# bench.py sets this to a list to time the scoring GEMM launches: (dtype, M, N, Kp, C, G, A.data_ptr(), start, end) with
-# the two events recorded on the launch stream immediately around the adalog_gemm_score kernel (not the finish kernel)
+# bench.py sets this to a list to time the scoring launches: every site appends (dtype, M, N, K, C_or_P, G, start, end, label)
+# through _timed -- the sizes as the site counts its work (un-padded K), the two events recorded on the launch stream immediately
+# around the site's launch, the label of the kernel it ran
 GEMM_EVENTS = None
 _ESZ = {I8: 1, BF16: 2, F32: 4, FP8: 1}
 _TORCH_DT = {I8: torch.int8, BF16: torch.bfloat16, F32: torch.float32, FP8: torch.float8_e4m3fn}
@@ -37,16 +38,16 @@ def _top(name, *args):
         raise
 
 
-def _timed(meta, call):
+def _timed(meta, call, label=None):
     """bench.py's per-launch timing (GEMM_EVENTS is a list while it runs): events on the current stream around the launch,
-    on whichever route the launch takes"""
+    on whichever route the launch takes.  ``label``: recorded instead of adalog_last_kernel() (launches of several kernels)."""
     if GEMM_EVENTS is None:
         return call()
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     ev0.record()
     r = call()
     ev1.record()
-    GEMM_EVENTS.append(meta + (ev0, ev1, _lib.load().adalog_last_kernel().decode()))
+    GEMM_EVENTS.append(meta + (ev0, ev1, label or _lib.load().adalog_last_kernel().decode()))
     return r
 
 
@@ -667,21 +668,14 @@ def gemm_score(dtype: int, A, B, M: int, N: int, C: int, G: int, gmod: int, ref,
                              mode, norm, N)
     n_part, MT, Npad, mode, n_last = layout()
     partial = torch.empty((n_part + 1) // 2, dtype=torch.float64, device=A.device).view(torch.float32)   # 8-byte aligned
-    if GEMM_EVENTS is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    rc = lib.adalog_gemm_score(dtype, A.data_ptr(), B.data_ptr(), sAc, sAg, sBc, sBg, M, n_cols, Kp, k_valid, c_grid, G, gmod,
-                               ref.data_ptr(), ldr, sRg, ref_cs, ref_div, sa.t.data_ptr(), sa.c, sa.g, float(sa_mul),
-                               sb.t.data_ptr(), sb.c, sb.g, sb.n,
-                               None if bias is None else bias.t.data_ptr(),
-                               0 if bias is None else bias.c, 0 if bias is None else bias.g,
-                               0 if bias is None else bias.n,
-                               _ptr(None if row_scale is None else _f32c(row_scale, "row_scale")),
-                               _ptr(None if row_bias is None else _f32c(row_bias, "row_bias")),
-                               partial.data_ptr(), n_part, None, 0, 0, 0, int(order), reduce_cols, _stream())
-    if GEMM_EVENTS is not None:
-        ev1.record()
-        GEMM_EVENTS.append((dtype, M, N, k_alg, C, G, ev0, ev1, lib.adalog_last_kernel().decode()))     # un-padded, algorithmic K
+    row_scale = None if row_scale is None else _f32c(row_scale, "row_scale")
+    row_bias = None if row_bias is None else _f32c(row_bias, "row_bias")
+    rc = _timed(meta, lambda: lib.adalog_gemm_score(
+        dtype, A.data_ptr(), B.data_ptr(), sAc, sAg, sBc, sBg, M, n_cols, Kp, k_valid, c_grid, G, gmod, ref.data_ptr(), ldr, sRg,
+        ref_cs, ref_div, sa.t.data_ptr(), sa.c, sa.g, float(sa_mul), sb.t.data_ptr(), sb.c, sb.g, sb.n,
+        None if bias is None else bias.t.data_ptr(), 0 if bias is None else bias.c, 0 if bias is None else bias.g,
+        0 if bias is None else bias.n, _ptr(row_scale), _ptr(row_bias), partial.data_ptr(), n_part, None, 0, 0, 0, int(order),
+        reduce_cols, _stream()))
     _lib.check(rc, "adalog_gemm_score")
     pend = PendingScores(partial, MT, n_last, Npad, C, G, gmod, keep_h, keep_n, mode, norm, N)
     return pend if defer else pend.finish()
@@ -718,6 +712,31 @@ def gemm_win_ok(dtype: int, M: int, N: int, G: int, gmod: int, ref_div: int, k_v
     return bool(_lib.load().adalog_gemm_win_ok(int(dtype), int(M), int(N) * int(ref_div), int(G), int(gmod), int(ref_div), int(k_valid)))
 
 
+def _score_attn_gen(c_name: str, dtype: int, A, src3, mid, M: int, N: int, P: int, G: int, gmod: int, ref, sa: Strided, sb: Strided,
+                    keep_h: bool, norm: float, sa_mul: float, layout=None, head=(), n_cols: Optional[int] = None):
+    """What gemm_score_gen, gemm_score_avq and gemm_score_avw share: the packed fixed operand A [G|1, M, Kp] against P candidates
+    generated inside the kernel from src3 [G, N, K] fp32, transposed reference [G, N, M] -> PendingScores over [P, gmod | 1].
+    ``c_name``: the C entry; ``head`` / ``mid``: its own arguments in front of A / between the source's strides and the reference;
+    ``n_cols``: its column count where that is not N; ``layout(K, Kp)`` -> (floats, MT, Npad, mode) of its partial buffer where
+    that is not what _layout gives for the launch of ``dtype``."""
+    sa, sb = sa.checked(), sb.checked()
+    src3, ref = _f32c(src3, "src"), _f32c(ref, "ref")
+    Gs, Ns, K = src3.shape
+    Kp = A.shape[-1]
+    assert (Gs, Ns) == (G, N) and A.shape[-2] == M and A.is_contiguous() and A.dtype == _TORCH_DT[BF16 if dtype == BF16_FP8 else dtype]
+    assert ref.shape[-1] == M and ref.shape[-2] == N
+    sAg = 0 if A.shape[1] == 1 and G > 1 else A.stride(1)
+    sRg = 0 if G == 1 else M * N
+    n_part, MT, Npad, mode = layout(K, Kp) if layout else _layout(M, N * P, 1, G, gmod, P, 1, dtype, Kp, K, True)
+    partial = torch.empty((n_part + 1) // 2, dtype=torch.float64, device=A.device).view(torch.float32)   # 8-byte aligned
+    fn = getattr(_lib.load(), c_name)
+    rc = _timed((dtype, M, N, K, P, G), lambda: fn(
+        *head, A.data_ptr(), sAg, M, N if n_cols is None else n_cols, Kp, K, G, gmod, src3.data_ptr(), K, N * K, *mid, ref.data_ptr(),
+        sRg, P, sa.t.data_ptr(), sa.c, sa.g, float(sa_mul), sb.t.data_ptr(), sb.c, sb.g, partial.data_ptr(), n_part, _stream()))
+    _lib.check(rc, c_name)
+    return PendingScores(partial, MT, Npad if mode != 1 else N, Npad, P, G, gmod, keep_h, False, mode, norm, N)
+
+
 def gemm_score_gen_ok(dtype: int, M: int, N: int, G: int, gmod: int, ref_div: int, k_valid: int, Kp: int) -> bool:
     """True when gemm_score_gen takes this attention-search shape (N = source rows; ref_div candidates)."""
     return bool(_lib.load().adalog_gemm_score_gen_ok(int(dtype), int(M), int(N) * int(ref_div), int(G), int(gmod), int(ref_div),
@@ -730,31 +749,10 @@ def gemm_score_gen(dtype: int, A, src3, zp, n_bits: int, M: int, N: int, P: int,
     the packed candidate operand: src3 [G, N, K] fp32 is quantised inside the kernel (adalog_gemm_score_gen).  sb: the candidates'
     scales as the epilogue's column factors (Strided(scale [P, H], c=H, g=0|1)); zp: their zero points, same layout.
     -> PendingScores."""
-    lib = _lib.load()
-    sa, sb = sa.checked(), sb.checked()
-    src3 = _f32c(src3, "src")
     zp = _f32c(zp, "zero_point")
-    Gs, Ns, K = src3.shape
-    Kp = A.shape[-1]
-    assert (Gs, Ns) == (G, N) and A.shape[-2] == M and A.is_contiguous() and A.dtype == _TORCH_DT[dtype] and zp.shape == sb.t.shape
-    ref = _f32c(ref, "ref")
-    assert ref.shape[-1] == M and ref.shape[-2] == N
-    sAg = 0 if A.shape[1] == 1 and G > 1 else A.stride(1)
-    sRg = 0 if G == 1 else M * N
-    n_part, MT, Npad, mode = _layout(M, N * P, 1, G, gmod, P, 1, dtype, Kp, K, True)
-    n_last = Npad if mode != 1 else N
-    partial = torch.empty((n_part + 1) // 2, dtype=torch.float64, device=A.device).view(torch.float32)
-    if GEMM_EVENTS is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    rc = lib.adalog_gemm_score_gen(int(dtype), A.data_ptr(), sAg, M, N * P, Kp, K, G, gmod, src3.data_ptr(), K, N * K, zp.data_ptr(),
-                                   int(n_bits), ref.data_ptr(), sRg, P, sa.t.data_ptr(), sa.c, sa.g, float(sa_mul), sb.t.data_ptr(),
-                                   sb.c, sb.g, partial.data_ptr(), n_part, _stream())
-    if GEMM_EVENTS is not None:
-        ev1.record()
-        GEMM_EVENTS.append((dtype, M, N, K, P, G, ev0, ev1, lib.adalog_last_kernel().decode()))
-    _lib.check(rc, "adalog_gemm_score_gen")
-    return PendingScores(partial, MT, n_last, Npad, P, G, gmod, keep_h, False, mode, norm, N)
+    assert zp.shape == sb.t.shape
+    return _score_attn_gen("adalog_gemm_score_gen", dtype, A, src3, (zp.data_ptr(), int(n_bits)), M, N, P, G, gmod, ref, sa, sb, keep_h,
+                           norm, sa_mul, head=(int(dtype),), n_cols=N * P)
 
 
 def adalog_value_lut(q_all: torch.Tensor, n_bits: int, mant37: torch.Tensor) -> torch.Tensor:
@@ -781,29 +779,10 @@ def gemm_score_avq(A, src3, q_all, lut, n_bits: int, M: int, N: int, P: int, G: 
     """The log-base search's scoring call (gemm_score(BF16, A, pack_adalog(src3, 1, q_all, ...), M, N, P, ..., keep_h=False)) without
     the packed candidate operand: src3 [G, N, K] fp32 probabilities are quantised inside the kernel (adalog_gemm_score_avq).
     -> scores [P, 1]."""
-    lib = _lib.load()
-    sa, sb = sa.checked(), sb.checked()
-    src3, q_all, ref = _f32c(src3, "src"), _f32c(q_all, "q"), _f32c(ref, "ref")
-    Gs, Ns, K = src3.shape
-    Kp = A.shape[-1]
-    assert (Gs, Ns) == (G, N) and A.shape[-2] == M and A.is_contiguous() and A.dtype == torch.bfloat16
+    q_all = _f32c(q_all, "q")
     assert lut.dtype == torch.int32 and lut.is_contiguous() and lut.shape == ((1 << n_bits) + 1, P)
-    assert ref.shape[-1] == M and ref.shape[-2] == N
-    sAg = 0 if A.shape[1] == 1 and G > 1 else A.stride(1)
-    sRg = 0 if G == 1 else M * N
-    n_part, MT, Npad, mode = _layout(M, N * P, 1, G, gmod, P, 1, BF16, Kp, K, True)
-    partial = torch.empty((n_part + 1) // 2, dtype=torch.float64, device=A.device).view(torch.float32)
-    if GEMM_EVENTS is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    rc = lib.adalog_gemm_score_avq(A.data_ptr(), sAg, M, N, Kp, K, G, gmod, src3.data_ptr(), K, N * K, q_all.data_ptr(), lut.data_ptr(),
-                                   int(n_bits), ref.data_ptr(), sRg, P, sa.t.data_ptr(), sa.c, sa.g, float(sa_mul), sb.t.data_ptr(),
-                                   sb.c, sb.g, partial.data_ptr(), n_part, _stream())
-    if GEMM_EVENTS is not None:
-        ev1.record()
-        GEMM_EVENTS.append((BF16, M, N, K, P, G, ev0, ev1, lib.adalog_last_kernel().decode()))
-    _lib.check(rc, "adalog_gemm_score_avq")
-    return PendingScores(partial, MT, Npad if mode != 1 else N, Npad, P, G, gmod, False, False, mode, norm, N).finish()
+    return _score_attn_gen("adalog_gemm_score_avq", BF16, A, src3, (q_all.data_ptr(), lut.data_ptr(), int(n_bits)), M, N, P, G, gmod, ref,
+                           sa, sb, False, norm, sa_mul).finish()
 
 
 def gemm_score_avw_ok(M: int, N: int, G: int, gmod: int, P: int, k_valid: int, Kp: int, n_bits: int) -> int:
@@ -819,31 +798,16 @@ def gemm_score_avw(A, src3, zp, n_bits: int, M: int, N: int, P: int, G: int, gmo
     defer=True) of the softmax.v weight search without the packed candidate operand: src3 [G, N, K] fp32 (v^T, K-contiguous) is
     quantised inside the kernel (adalog_gemm_score_avw), the same scores bit for bit.  sb: the candidates' scales as the epilogue's
     column factors (Strided(scale [P, H], c=H, g=0|1)); zp: their zero points, same layout.  -> PendingScores."""
-    lib = _lib.load()
-    sa, sb = sa.checked(), sb.checked()
-    src3, zp, ref = _f32c(src3, "src"), _f32c(zp, "zero_point"), _f32c(ref, "ref")
-    Gs, Ns, K = src3.shape
-    Kp = A.shape[-1]
-    assert (Gs, Ns) == (G, N) and A.shape[-2] == M and A.is_contiguous() and A.dtype == torch.bfloat16 and zp.shape == sb.t.shape
-    assert ref.shape[-1] == M and ref.shape[-2] == N
-    wgs = gemm_score_avw_ok(M, N, G, gmod, P, K, Kp, n_bits)
-    if not wgs:
-        raise ValueError("gemm_score_avw: shape not taken (gemm_score_avw_ok)")
-    sAg = 0 if A.shape[1] == 1 and G > 1 else A.stride(1)
-    sRg = 0 if G == 1 else M * N
-    n_part = 2 * wgs * gmod * 256
-    partial = torch.empty(n_part // 2, dtype=torch.float64, device=A.device).view(torch.float32)
-    if GEMM_EVENTS is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    rc = lib.adalog_gemm_score_avw(A.data_ptr(), sAg, M, N, Kp, K, G, gmod, src3.data_ptr(), K, N * K, zp.data_ptr(), int(n_bits),
-                                   ref.data_ptr(), sRg, P, sa.t.data_ptr(), sa.c, sa.g, float(sa_mul), sb.t.data_ptr(), sb.c, sb.g,
-                                   partial.data_ptr(), n_part, _stream())
-    if GEMM_EVENTS is not None:
-        ev1.record()
-        GEMM_EVENTS.append((BF16_FP8, M, N, K, P, G, ev0, ev1, lib.adalog_last_kernel().decode()))
-    _lib.check(rc, "adalog_gemm_score_avw")
-    return PendingScores(partial, wgs, 256, 256, P, G, gmod, keep_h, False, 2, norm, N)
+    zp = _f32c(zp, "zero_point")
+    assert zp.shape == sb.t.shape
+
+    def layout(K, Kp):
+        wgs = gemm_score_avw_ok(M, N, G, gmod, P, K, Kp, n_bits)
+        if not wgs:
+            raise ValueError("gemm_score_avw: shape not taken (gemm_score_avw_ok)")
+        return 2 * wgs * gmod * 256, wgs, 256, 2                      # per-workgroup fp64 accumulators [wgs][gmod][256]
+    return _score_attn_gen("adalog_gemm_score_avw", BF16_FP8, A, src3, (zp.data_ptr(), int(n_bits)), M, N, P, G, gmod, ref, sa, sb,
+                           keep_h, norm, sa_mul, layout)
 
 
 def gemm_out(dtype: int, A, B, M: int, N: int, G: int, gmod: int, sa: Strided, sb: Strided, bias: Optional[Strided],
@@ -1174,18 +1138,12 @@ def score_act_fused(wp, x2, lx2, ref2, row_scale, row_bias, scale, qv, n_bits: i
     ws_bytes = lib.adalog_score_act_fused_workspace_bytes(T, Kp)
     ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.float64, device=x2.device)
     scores = torch.empty((P, 1), dtype=torch.float32, device=x2.device)
-    if GEMM_EVENTS is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    rc = lib.adalog_score_act_fused(wp.data_ptr(), M, Kp, x2.data_ptr(), lx2.data_ptr(), T, K, ref2.data_ptr(),
-                                    _f32c(row_scale, "row_scale").data_ptr(),
-                                    _ptr(None if row_bias is None else _f32c(row_bias, "row_bias")),
-                                    _f32c(scale, "scale").data_ptr(), _f32c(qv, "qv").data_ptr(), P, int(n_bits),
-                                    _f32c(mant37, "mant37").data_ptr(), float(shift), int(bool(clamp_u)), float(sa_mul),
-                                    float(norm), ws.data_ptr(), ws_bytes, scores.data_ptr(), _stream())
-    if GEMM_EVENTS is not None:
-        ev1.record()
-        GEMM_EVENTS.append((BF16, M, T, K, P, 1, ev0, ev1, lib.adalog_last_kernel().decode()))
+    row_scale, scale, qv, mant37 = _f32c(row_scale, "row_scale"), _f32c(scale, "scale"), _f32c(qv, "qv"), _f32c(mant37, "mant37")
+    row_bias = None if row_bias is None else _f32c(row_bias, "row_bias")
+    rc = _timed((BF16, M, T, K, P, 1), lambda: lib.adalog_score_act_fused(
+        wp.data_ptr(), M, Kp, x2.data_ptr(), lx2.data_ptr(), T, K, ref2.data_ptr(), row_scale.data_ptr(), _ptr(row_bias),
+        scale.data_ptr(), qv.data_ptr(), P, int(n_bits), mant37.data_ptr(), float(shift), int(bool(clamp_u)), float(sa_mul),
+        float(norm), ws.data_ptr(), ws_bytes, scores.data_ptr(), _stream()))
     _lib.check(rc, "adalog_score_act_fused")
     return scores
 
@@ -1210,8 +1168,8 @@ def score_act_gen(dtype: int, wp, x2, scale, zp, n_bits: int, ref2, row_scale, r
     wgs = lib.adalog_score_act_gen_wgs(dtype, M, T, K, Kp, P)
     if wgs < 0:
         raise _lib.AdalogHipError("score_act_gen: shape not supported (score_act_gen_ok)")
+    meta = (dtype, M, T, K, P, 1)
     if _torch_ops.available():
-        meta = (dtype, M, T, K, P, 1)
         if not defer:
             return _timed(meta, lambda: _top("score_act_gen", int(dtype), wp, x2, scale, zp, int(n_bits), ref2, row_scale, row_bias,
                                              float(norm)))
@@ -1220,15 +1178,9 @@ def score_act_gen(dtype: int, wp, x2, scale, zp, n_bits: int, ref2, row_scale, r
     wsb = lib.adalog_score_act_gen_workspace_bytes(dtype, M, T, K, Kp, P)
     ws = torch.empty((wsb + 15) // 16 * 2, dtype=torch.float64, device=x2.device)
     scores = None if defer else torch.empty((P, 1), dtype=torch.float32, device=x2.device)
-    if GEMM_EVENTS is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    rc = lib.adalog_score_act_gen(dtype, wp.data_ptr(), M, Kp, x2.data_ptr(), T, K, K, scale.data_ptr(), zp.data_ptr(), P,
-                                  int(n_bits), ref2.data_ptr(), row_scale.data_ptr(), _ptr(row_bias), float(norm),
-                                  ws.data_ptr(), ws.numel() * 8, _ptr(scores), _stream())
-    if GEMM_EVENTS is not None:
-        ev1.record()
-        GEMM_EVENTS.append((dtype, M, T, K, P, 1, ev0, ev1, lib.adalog_last_kernel().decode()))
+    rc = _timed(meta, lambda: lib.adalog_score_act_gen(
+        dtype, wp.data_ptr(), M, Kp, x2.data_ptr(), T, K, K, scale.data_ptr(), zp.data_ptr(), P, int(n_bits), ref2.data_ptr(),
+        row_scale.data_ptr(), _ptr(row_bias), float(norm), ws.data_ptr(), ws.numel() * 8, _ptr(scores), _stream()))
     _lib.check(rc, "adalog_score_act_gen")
     # (the accumulators [wgs][1][256] fp64 sit at the start of the workspace: the per-workgroup layout of gemm_score)
     return PendingScores(ws, wgs, 256, 256, P, 1, 1, False, False, 2, norm, T) if defer else scores
@@ -1260,14 +1212,9 @@ def score_w_gen(dtype: int, xp, w2, scale, zp, n_bits: int, ref_t, sa, bias, nor
         _WGEN_LAYOUT[key] = _layout(T, O * P, 1, 1, 1, P, 0, dtype, Kp, K, True)
     n_part, MT, Npad, mode = _WGEN_LAYOUT[key]
     partial = torch.empty((n_part + 1) // 2, dtype=torch.float64, device=w2.device).view(torch.float32)
-    if GEMM_EVENTS is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    rc = lib.adalog_score_w_gen(dtype, xp.data_ptr(), T, Kp, w2.data_ptr(), O, K, K, scale.data_ptr(), zp.data_ptr(), P, int(n_bits),
-                                ref_t.data_ptr(), sa.data_ptr(), _ptr(bias), partial.data_ptr(), n_part, _stream())
-    if GEMM_EVENTS is not None:
-        ev1.record()
-        GEMM_EVENTS.append((dtype, T, O, K, P, 1, ev0, ev1, lib.adalog_last_kernel().decode()))
+    rc = _timed((dtype, T, O, K, P, 1), lambda: lib.adalog_score_w_gen(
+        dtype, xp.data_ptr(), T, Kp, w2.data_ptr(), O, K, K, scale.data_ptr(), zp.data_ptr(), P, int(n_bits), ref_t.data_ptr(),
+        sa.data_ptr(), _ptr(bias), partial.data_ptr(), n_part, _stream()))
     _lib.check(rc, "adalog_score_w_gen")
     pend = PendingScores(partial, MT, O, Npad, P, 1, 1, False, True, mode, norm, O)
     return pend if defer else pend.finish()
@@ -1344,15 +1291,10 @@ class GramState:
         self.ws = torch.empty((nb + 255) // 8 + 32, dtype=torch.float64, device=x2.device)
         off = (-self.ws.data_ptr()) % 256                     # the kernels want a 256-byte aligned base
         self.ws = self.ws.view(torch.uint8)[off:off + nb]
-        if GEMM_EVENTS is not None:
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev0.record()
-        rc = lib.adalog_gram_build(x2.data_ptr(), self.T, self.K, x2.stride(0), self.sa.data_ptr(), za.data_ptr(), self.a_bits,
-                                   ref_t.data_ptr(), self.O, _ptr(bias), self.ws.data_ptr(), nb, _stream())
-        if GEMM_EVENTS is not None:
-            ev1.record()
-            # issued work: G (K x K, symmetry not used) + four reference limbs x (O x K), each over the T tokens
-            GEMM_EVENTS.append((I8, self.T, self.K + 4 * self.O, self.K, 1, 1, ev0, ev1, "k_gram_build"))
+        # issued work: G (K x K, symmetry not used) + four reference limbs x (O x K), each over the T tokens
+        rc = _timed((I8, self.T, self.K + 4 * self.O, self.K, 1, 1), lambda: lib.adalog_gram_build(
+            x2.data_ptr(), self.T, self.K, x2.stride(0), self.sa.data_ptr(), za.data_ptr(), self.a_bits, ref_t.data_ptr(), self.O,
+            _ptr(bias), self.ws.data_ptr(), nb, _stream()), "k_gram_build")
         _lib.check(rc, "adalog_gram_build")
 
     def score_w(self, w2, scale, zp, w_bits: int, norm: float, tail=None):
@@ -1364,19 +1306,13 @@ class GramState:
         P = scale.shape[0]
         assert tuple(w2.shape) == (self.O, self.K) and scale.numel() == P * self.O and zp.numel() == P * self.O
         scores = torch.empty((P, self.O), dtype=torch.float32, device=w2.device)
-        if GEMM_EVENTS is not None:
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev0.record()
         assert tail is None or (tail.scale.data_ptr() == scale.data_ptr() and tail.zp is not None and tail.zp.data_ptr() == zp.data_ptr())
-        rc = lib.adalog_gram_score_w_tail(w2.data_ptr(), self.O, self.K, w2.stride(0), scale.data_ptr(), zp.data_ptr(), P, int(w_bits),
-                                          self.ws.data_ptr(), self.T, self.a_bits, self.sa.data_ptr(), float(norm), scores.data_ptr(),
-                                          None if tail is None else tail.ref(), _stream())
-        if GEMM_EVENTS is not None:
-            ev1.record()
-            # flops as ISSUED (limbs * K^2 + the 32-row w.c panel per candidate row), not the token form's 2 T K O P: a roofline
-            # fraction of this kernel is a fraction of the work it does
-            rows = lib.adalog_gram_limbs(self.T, self.a_bits) * self.K + 32
-            GEMM_EVENTS.append((I8, rows, self.O, self.K, P, 1, ev0, ev1, lib.adalog_last_kernel().decode()))
+        # flops as ISSUED (limbs * K^2 + the 32-row w.c panel per candidate row), not the token form's 2 T K O P: a roofline
+        # fraction of this kernel is a fraction of the work it does
+        rows = lib.adalog_gram_limbs(self.T, self.a_bits) * self.K + 32
+        rc = _timed((I8, rows, self.O, self.K, P, 1), lambda: lib.adalog_gram_score_w_tail(
+            w2.data_ptr(), self.O, self.K, w2.stride(0), scale.data_ptr(), zp.data_ptr(), P, int(w_bits), self.ws.data_ptr(), self.T,
+            self.a_bits, self.sa.data_ptr(), float(norm), scores.data_ptr(), None if tail is None else tail.ref(), _stream()))
         _lib.check(rc, "adalog_gram_score_w")
         return scores
 
@@ -1440,15 +1376,10 @@ class GramActState:
             raise _lib.AdalogHipError("gram_act_build: shape not supported (gram_act_ok)")
         self.ws = _aligned_bytes(nb, w2.device)
         self.qpart = torch.empty(self.P * lib.adalog_gram_act_splits(self.T, self.O, self.K, self.P), dtype=torch.float64, device=w2.device)
-        if GEMM_EVENTS is not None:
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev0.record()
-        rc = lib.adalog_gram_act_build(raw_out2.data_ptr(), self.T, self.O, _ptr(bias), w2.data_ptr(), self.K, w2.stride(0), sw.data_ptr(),
-                                       zw.data_ptr(), int(w_bits), prep.perm.data_ptr(), self.P, self.ws.data_ptr(), nb, _stream())
-        if GEMM_EVENTS is not None:
-            ev1.record()
-            # issued matrix work: four reference limbs x (T x O x K)
-            GEMM_EVENTS.append((I8, 4 * self.T, self.K, self.O, 1, 1, ev0, ev1, "k_gram_act_build"))
+        # issued matrix work: four reference limbs x (T x O x K)
+        rc = _timed((I8, 4 * self.T, self.K, self.O, 1, 1), lambda: lib.adalog_gram_act_build(
+            raw_out2.data_ptr(), self.T, self.O, _ptr(bias), w2.data_ptr(), self.K, w2.stride(0), sw.data_ptr(), zw.data_ptr(),
+            int(w_bits), prep.perm.data_ptr(), self.P, self.ws.data_ptr(), nb, _stream()), "k_gram_act_build")
         _lib.check(rc, "adalog_gram_act_build")
 
     def score(self, scale, zp, norm: float, tail=None):
@@ -1460,17 +1391,10 @@ class GramActState:
         P = scale.numel()
         assert P == self.P and zp.numel() == P
         scores = torch.empty((P, 1), dtype=torch.float32, device=scale.device)
-        if GEMM_EVENTS is not None:
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev0.record()
-        rc = lib.adalog_gram_act_score_tail(self.prep.xt.data_ptr(), self.prep.sorted.data_ptr(), self.T, self.O, self.K, scale.data_ptr(),
-                                            zp.data_ptr(), P, self.a_bits, self.ws.data_ptr(), float(norm), self.qpart.data_ptr(),
-                                            scores.data_ptr(), None if tail is None else tail.ref(), _stream())
-        if GEMM_EVENTS is not None:
-            ev1.record()
-            # flops as ISSUED: the upper triangle of X_p^T X_p in 32 x 32 blocks, per candidate
-            nj = self.K // 32
-            GEMM_EVENTS.append((I8, self.T, 32 * nj * (nj + 1) // 2, 32, P, 1, ev0, ev1, lib.adalog_last_kernel().decode()))
+        nj = self.K // 32                    # flops as ISSUED: the upper triangle of X_p^T X_p in 32 x 32 blocks, per candidate
+        rc = _timed((I8, self.T, 32 * nj * (nj + 1) // 2, 32, P, 1), lambda: lib.adalog_gram_act_score_tail(
+            self.prep.xt.data_ptr(), self.prep.sorted.data_ptr(), self.T, self.O, self.K, scale.data_ptr(), zp.data_ptr(), P, self.a_bits,
+            self.ws.data_ptr(), float(norm), self.qpart.data_ptr(), scores.data_ptr(), None if tail is None else tail.ref(), _stream()))
         _lib.check(rc, "adalog_gram_act_score")
         return scores
 
