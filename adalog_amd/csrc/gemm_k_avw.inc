@@ -21,9 +21,20 @@
 //     the same sums.
 // Items are k_gemm_grpk8t's (group, chunk of CB column blocks); the workgroup has NJ waves (one per 32 candidates), and with the
 // 79 KB image of a 197-row group two workgroups share a CU: two waves per SIMD, one generating while the other multiplies.
-//   LDS: [M + 1 rows][25 slots of 16 bytes] + 64 bytes: K < 200 of the packed bf16 rows, row M and the tail all zero (rows past M
-//   read row M; the upper half wave of MFMA 12 reads the 32 bytes behind its row against a zero B fragment).  25 slots: an odd
+//   LDS: [MI + 1 rows][25 slots of 16 bytes] + 64 bytes: K < 200 of the packed bf16 rows; rows from M on and the tail all zero.
+//   M > 192: MI = M, rows past M read row M; otherwise MI = M rounded up to 32, so every row block is whole and 12 800 bytes from
+//   the last (the upper half wave of MFMA 12 reads the 32 bytes behind its row against a zero B fragment).  25 slots: an odd
 //   stride, so the 16 rows of a ds_read_b128 lane group fall on 16 different slots of the 256-byte bank row.
+//   Behind the image: the fp32 REFERENCE COLUMN of the head-dim column in work, [224] floats, zero from row M on (such rows meet a
+//   zero accumulator and must add nothing): the quad of rows a lane's epilogue needs is one ds_read_b128.  The column depends on
+//   (row, d) only: staged once per workgroup, every wave and both half waves read it (the 32 lanes of a half wave the same address:
+//   a broadcast).  Two buffers, alternating over d, where two workgroups of that size still share a CU (M <= 199); one buffer
+//   and a second barrier per column otherwise.
+constexpr int AVW_REF_BYTES = 224 * 4;
+__host__ __device__ constexpr int avw_img_rows(int M) { return M > 192 ? M : (M + 31) & ~31; }
+__host__ __device__ constexpr int avw_img_bytes(int M) { return (avw_img_rows(M) + 1) * 400 + 64; }
+__host__ __device__ constexpr bool avw_ref_two(int M) { return 2 * (avw_img_bytes(M) + 2 * AVW_REF_BYTES) <= 160 * 1024; }
+__host__ __device__ constexpr int avw_lds_bytes(int M) { return avw_img_bytes(M) + (avw_ref_two(M) ? 2 : 1) * AVW_REF_BYTES; }
 struct AvwCand { float s, inv, lo, hi; };
 __device__ __forceinline__ uint4 avw_gen8(const v4u& xa, const v4u& xb, const AvwCand& c) {
 #pragma clang fp contract(off)
@@ -54,6 +65,8 @@ template <int NJ, bool R7>
 __global__ __launch_bounds__(NJ * 64, 2) void k_gemm_avw_gen(GemmArgs p) {
 #if defined(__HIP_DEVICE_COMPILE__)
     constexpr int NKS = 13, ASL = 25, ARB = ASL * 16, NT = NJ * 64, LA = 2;
+    constexpr int IU = 10;                                     // image slots a lane has in flight at once
+    constexpr int RPT = (224 + NT - 1) / NT;                   // reference rows a lane stages
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -68,25 +81,61 @@ __global__ __launch_bounds__(NJ * 64, 2) void k_gemm_avw_gen(GemmArgs p) {
     for (int i = tid; i < p.gmod * 256; i += NT) wacc[i] = 0.0;
 
     // LDS byte offset of this lane's fragment of row block rb for MFMA 0 (MFMA i: + 64 (i >> 1) + 16 (i & 1)); with 7 row blocks
-    // (M > 192) the first six are whole and 12 800 bytes apart, which is an instruction's immediate
+    // (M > 192) the first six are whole and 12 800 bytes apart, which is an instruction's immediate; with fewer all are whole
     const int base0 = frow * ARB + fkg * 32, base6 = min(192 + frow, M) * ARB + fkg * 32;
-    auto aoff = [&](int rb) { return R7 ? (rb < 6 ? base0 + rb * 32 * ARB : base6) : min(rb * 32 + frow, M) * ARB + fkg * 32; };
+    auto aoff = [&](int rb) { return rb < 6 ? base0 + rb * 32 * ARB : base6; };
     const int xvoff = fkg * 64;                                // MFMA i reads K = 32 (i >> 1) + 16 fkg + 8 (i & 1) + 0..7 of a row of v^T
+    // the image slots of this lane: tid, tid + NT, .. as (row, slot of the row), stepped without a division
+    const int ir0 = tid / ASL, is0 = tid - ir0 * ASL;
+    const int islots = (avw_img_rows(M) + 1) * ASL + 4;
+    const int nsl = min(ASL, KbA >> 4);                        // slots a packed row has (shorter rows: zeros behind them)
+    // the reference column(s) behind the image; a lane's row quad q of row block rb is rows 32 rb + 8 q + 4 fkg + 0..3
+    const int refo = avw_img_bytes(M) + fkg * 16;
+    const bool two = avw_ref_two(M);
 
     for (int item = blockIdx.x; item < items; item += gridDim.x) {
         const int g = item / NCH, c = item - g * NCH, gh = g % p.gmod;
         const int blk0 = c * CB, nblk = min(CB, NB - blk0);
         const int d0 = blk0 / NJ, nd = nblk / NJ;
-        __syncthreads();                                       // the previous item's fragment reads are done (and wacc is zeroed)
-        {
-            const uint8_t* ag = p.A + (int64_t)g * p.sAg;
-            const int nsl = min(ASL, KbA >> 4);                // slots a packed row has (shorter rows: zeros behind them)
-            for (int idx = tid; idx < (M + 1) * ASL + 4; idx += NT) {
-                const int r = idx / ASL, s = idx - r * ASL;
-                uint4 v = make_uint4(0, 0, 0, 0);
-                if (r < M && s < nsl) v = *reinterpret_cast<const uint4*>(ag + (int64_t)r * KbA + s * 16);
-                *reinterpret_cast<uint4*>(lds + r * ARB + s * 16) = v;
+        const float* refg = p.ref + (int64_t)g * p.sRg;
+        // rows 0 .. 223 of the reference column d (zero from M on): this lane's, from memory / into buffer b
+        auto ref_fetch = [&](int d, float (&r)[RPT]) {
+            const float* rp = refg + (int64_t)d * p.ref_cs;
+#pragma unroll
+            for (int u = 0; u < RPT; ++u) {
+                const int t = tid + u * NT;
+                r[u] = t < M ? rp[t] : 0.0f;
             }
+        };
+        auto ref_put = [&](int b, const float (&r)[RPT]) {
+#pragma unroll
+            for (int u = 0; u < RPT; ++u) {
+                const int t = tid + u * NT;
+                if (t < 224) *reinterpret_cast<float*>(lds + avw_img_bytes(M) + b * AVW_REF_BYTES + t * 4) = r[u];
+            }
+        };
+        __syncthreads();                                       // the previous item's fragment and reference reads are done (and wacc is zeroed)
+        {
+            // IU loads in flight per lane and round trip; a slot outside the packed rows reads slot 0 and is stored as zero
+            const uint8_t* ag = p.A + (int64_t)g * p.sAg;
+            float r0[RPT];
+            ref_fetch(d0, r0);
+            int r = ir0, s = is0;
+            for (int idx = tid; idx < islots; idx += IU * NT) {
+                uint4 v[IU];
+#pragma unroll
+                for (int u = 0; u < IU; ++u) {
+                    const bool in = r < M && s < nsl;
+                    v[u] = *reinterpret_cast<const uint4*>(ag + (in ? r * KbA + s * 16 : 0));
+                    if (!in) v[u] = make_uint4(0, 0, 0, 0);
+                    r += NT / ASL; s += NT % ASL;
+                    if (s >= ASL) { s -= ASL; ++r; }
+                }
+#pragma unroll
+                for (int u = 0; u < IU; ++u)
+                    if (idx + u * NT < islots) *reinterpret_cast<uint4*>(lds + (idx + u * NT) * 16) = v[u];   // slot idx = 25 row + slot
+            }
+            ref_put(0, r0);
         }
         __syncthreads();
 
@@ -100,7 +149,6 @@ __global__ __launch_bounds__(NJ * 64, 2) void k_gemm_avw_gen(GemmArgs p) {
         const int64_t xbytes = ((int64_t)(p.N / (NJ * 32)) * p.gen_ldx) * 4;      // one group of v^T: past it a load reads zeros
         const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)(p.gen_x + (int64_t)g * p.gen_sg), 0,
                                                                             (int)min(xbytes, (int64_t)0x7ffffffe), 0x00020000);
-        const float* refg = p.ref + (int64_t)g * p.sRg;
         // 16-byte loads at the 4-byte alignment of a row of K floats.  MFMA i reads elements up to 32 (i >> 1) + 16 fkg + 8 (i & 1) + 7 <= 215
         // of row d: past K they are the next row's values (zeros past the group), and candidates are generated from them all the same.
         // That is harmless on two conditions: x is finite, and the fixed operand is zero from K on (the packer's padding up to element
@@ -117,18 +165,11 @@ __global__ __launch_bounds__(NJ * 64, 2) void k_gemm_avw_gen(GemmArgs p) {
             for (int rb = 0; rb < 7; ++rb)
                 if (R7 || rb < nrb) af[rb] = *reinterpret_cast<const uint4*>(lds + aoff(rb) + (i >> 1) * 64 + (i & 1) * 16);
         };
-        auto load_ref = [&](int d, int rb, float (&r)[16]) {
-            const float* rp = refg + (int64_t)d * p.ref_cs;
+        auto load_ref = [&](int b, int rb, float (&r)[16]) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const int rr = rb * 32 + 8 * q + 4 * fkg;
-                if (rr + 4 <= M) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) r[4 * q + e] = rp[rr + e];
-                } else {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) r[4 * q + e] = rr + e < M ? rp[rr + e] : 0.0f;
-                }
+                const float4 t = *reinterpret_cast<const float4*>(lds + refo + b * AVW_REF_BYTES + (rb * 32 + 8 * q) * 4);
+                r[4 * q + 0] = t.x; r[4 * q + 1] = t.y; r[4 * q + 2] = t.z; r[4 * q + 3] = t.w;
             }
         };
 
@@ -142,6 +183,9 @@ __global__ __launch_bounds__(NJ * 64, 2) void k_gemm_avw_gen(GemmArgs p) {
         for (int i = 0; i < LA; ++i) load_x(d0, i, xq[i][0], xq[i][1]);
         for (int dd = 0; dd < nd; ++dd) {
             const int d = d0 + dd, dn = d0 + min(dd + 1, nd - 1);
+            // the reference column of the next d travels during this block's MFMAs (two buffers)
+            float rnx[RPT];
+            if (two && dd + 1 < nd) ref_fetch(d + 1, rnx);
             v16f acc[7];
 #pragma unroll
             for (int rb = 0; rb < 7; ++rb)
@@ -166,13 +210,25 @@ __global__ __launch_bounds__(NJ * 64, 2) void k_gemm_avw_gen(GemmArgs p) {
             }
 #pragma unroll
             for (int i = 0; i < LA; ++i) { xq[i][0] = xq[NKS + i][0]; xq[i][1] = xq[NKS + i][1]; }
-            // epilogue of the seven 32 x 32 tiles: reference rows one row block ahead
-            float rc[16], rn[16];
-            load_ref(d, 0, rc);
+            // the reference column of this block is buffer dd & 1, staged one block ago; the barrier hands the other buffer (read
+            // by the last block's epilogue) over to the next column.  One buffer: wait for the last epilogue, stage, wait again.
+            int rbuf = 0;
+            if (two) {
+                __syncthreads();
+                if (dd + 1 < nd) ref_put((dd + 1) & 1, rnx);
+                rbuf = dd & 1;
+            } else if (dd > 0) {
+                __syncthreads();
+                ref_fetch(d, rnx);
+                ref_put(0, rnx);
+                __syncthreads();
+            }
+            // epilogue of the seven 32 x 32 tiles
 #pragma unroll
             for (int rb = 0; rb < 7; ++rb) {
                 if (R7 || rb < nrb) {
-                    if (rb + 1 < 7 && (R7 || rb + 1 < nrb)) load_ref(d, rb + 1, rn);
+                    float rc[16];
+                    load_ref(rbuf, rb, rc);
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
                         const float e0 = __builtin_fmaf(acc[rb][q * 4 + 0], nal, rc[q * 4 + 0]);
@@ -182,8 +238,6 @@ __global__ __launch_bounds__(NJ * 64, 2) void k_gemm_avw_gen(GemmArgs p) {
                         csr[rb].x = __builtin_fmaf(e0, e0, csr[rb].x); csr[rb].y = __builtin_fmaf(e1, e1, csr[rb].y);
                         csr[rb].x = __builtin_fmaf(e2, e2, csr[rb].x); csr[rb].y = __builtin_fmaf(e3, e3, csr[rb].y);
                     }
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) rc[e] = rn[e];
                 }
             }
         }

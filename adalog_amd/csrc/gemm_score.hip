@@ -882,7 +882,7 @@ extern "C" int adalog_gemm_score_avw(const void* A, int64_t sAg, int M, int N, i
     GemmArgs p = av_gen_args(A, sAg, M, N, k_valid, G, gmod, x, ldx, sg, ref, sRg, P, sa, sa_c, sa_g, sa_mul, sb, sb_c, sb_g, partial);
     p.Kb = Kp; p.KbA = Kp * 2; p.Kvb = k_valid; p.gen_zp = zp; p.gen_qmax = (float)((1 << n_bits) - 1);
     grp_chunks(p, N * P, wgs, G);                                  // k_gemm_grpk8t's items
-    const size_t shm = (size_t)(M + 1) * 400 + 64;            // [M + 1 rows][25 slots] and a zero tail
+    const size_t shm = (size_t)avw_lds_bytes(M);              // [M + 1 rows][25 slots], a zero tail, the reference column(s)
     hipStream_t st = (hipStream_t)stream;
     if (const int e = with_nj(P, [&](auto nj) {
             constexpr int NJ = decltype(nj)::value;
