@@ -115,6 +115,9 @@ __global__ __launch_bounds__(256) void k_candidate_grid(const float* __restrict_
 
 // ---------------------------------------------------------------------------------------------- K9
 // scores[p][row] = -mean_i (w - fq_p(w))^2 ; one workgroup per weight row, one thread per candidate.
+// The dequantised value is the reference's fp32 one; the difference, its square and the sum are fp64, as in sorted_score.hip, so
+// that both routes give the exact score rounded once to fp32: the last FPCS grids are finer than fp32 sums of fp32 terms resolve,
+// and a layer has to commit the same winner whichever route it takes.
 __global__ __launch_bounds__(256) void k_score_w_self(const float* __restrict__ w, int rows, int I,
                                                       const float* __restrict__ scale, const float* __restrict__ zp,
                                                       int P, float qmax, float* __restrict__ scores) {
@@ -125,24 +128,25 @@ __global__ __launch_bounds__(256) void k_score_w_self(const float* __restrict__ 
     const int p = threadIdx.x;
     if (p >= P) return;
     const float s = scale[(int64_t)p * rows + row], z = zp[(int64_t)p * rows + row];
-    float acc = 0.0f;
+    double acc = 0.0;
     for (int i = 0; i < I; ++i) {
         const float v = wrow[i];
         const float dq = (fminf(fmaxf(rintf(v / s) + z, 0.0f), qmax) - z) * s;
-        const float e = v - dq;
+        const double e = (double)v - (double)dq;
         acc += e * e;
     }
-    scores[(int64_t)p * rows + row] = -(acc / (float)I);
+    scores[(int64_t)p * rows + row] = (float)(-(1.0 / (double)I) * acc);
 }
 
 // ---------------------------------------------------------------------------------------------- K10
 // partial[p][slab][ch] = sum over the slab's rows of (x - fq_p(x))^2 ; x is read from HBM once for all P candidates.
+// As in K9 the dequantised value is the fp32 one and everything after it (difference, square, sums, partials) is fp64.
 constexpr int SLAB_ROWS_PER_THREAD = 32, SLAB_ROWS = 4 * SLAB_ROWS_PER_THREAD;
 __global__ __launch_bounds__(256) void k_score_a_self(const float* __restrict__ x, int64_t rows, int I,
                                                       const float* __restrict__ scale, const float* __restrict__ zp,
-                                                      int P, int pstride_ch, float qmax, float* __restrict__ partial,
+                                                      int P, int pstride_ch, float qmax, double* __restrict__ partial,
                                                       int n_slab, int Cpad) {
-    __shared__ float red[2][4][64];              // double-buffered by candidate parity: one barrier per candidate
+    __shared__ double red[2][4][64];              // double-buffered by candidate parity: one barrier per candidate
     const int chl = threadIdx.x & 63, rg = threadIdx.x >> 6;
     const int ch = blockIdx.x * 64 + chl;
     const int slab = blockIdx.y;
@@ -152,7 +156,7 @@ __global__ __launch_bounds__(256) void k_score_a_self(const float* __restrict__ 
 #pragma unroll
     for (int r = 0; r < SLAB_ROWS_PER_THREAD; ++r) {
         const int64_t row = r0 + 4 * r;
-        xv[r] = (cv && row < rows) ? x[row * I + ch] : __builtin_nanf("");
+        xv[r] = (cv && row < rows) ? x[row * I + ch] : 0.0f;        // absent rows are skipped by their index below, not by a marker
     }
     const int cols = pstride_ch ? I : 1;
     const bool slab_full = cv && (r0 + 4 * (SLAB_ROWS_PER_THREAD - 1) < rows);
@@ -161,16 +165,16 @@ __global__ __launch_bounds__(256) void k_score_a_self(const float* __restrict__ 
     for (int p = 0; p < P; ++p) {
         const float s = s_n, z = z_n;
         if (p + 1 < P) { s_n = scale[(int64_t)(p + 1) * cols + pcol]; z_n = zp[(int64_t)(p + 1) * cols + pcol]; }
-        float acc = 0.0f;
+        double acc = 0.0;
         if (slab_full && rintf(z) == z) {
             // reciprocal fast path; inside the tie zone (|frac - 0.5| < 1e-4) the exact IEEE quotient decides, so the bin
             // is the one rintf(v / s) gives.  clamp(k + z, 0, qmax) - z == med3(k, -z, qmax - z) for integral z.
-            // Two rows per step on packed fp32 math (v_pk_mul / v_pk_add; no contraction in this file): 6 VALU per
-            // element-candidate instead of 9.
+            // Two rows per step on packed fp32 math (v_pk_mul / v_pk_add; no contraction in this file) up to the dequantised
+            // value; the two error terms are fp64.
             typedef float v2f __attribute__((ext_vector_type(2)));
             const float inv_s = __builtin_amdgcn_rcpf(s), lo = -z, hi = qmax - z;
             const v2f inv2 = {inv_s, inv_s}, s2 = {s, s};
-            v2f acc2 = {0.0f, 0.0f};
+            double acc0 = 0.0, acc1 = 0.0;
 #pragma unroll
             for (int r = 0; r < SLAB_ROWS_PER_THREAD; r += 2) {
                 const v2f v = {xv[r], xv[r + 1]};
@@ -182,20 +186,22 @@ __global__ __launch_bounds__(256) void k_score_a_self(const float* __restrict__ 
                     k.y = rintf(v.y / s);
                 }
                 const v2f kq = {__builtin_amdgcn_fmed3f(k.x, lo, hi), __builtin_amdgcn_fmed3f(k.y, lo, hi)};
-                const v2f e = v - kq * s2;
-                acc2 += e * e;
+                const v2f c = kq * s2;
+                const double e0 = (double)v.x - (double)c.x, e1 = (double)v.y - (double)c.y;
+                acc0 += e0 * e0;
+                acc1 += e1 * e1;
             }
-            acc = acc2.x + acc2.y;
+            acc = acc0 + acc1;
         } else {
 #pragma unroll
             for (int r = 0; r < SLAB_ROWS_PER_THREAD; ++r) {
                 const float v = xv[r];
                 const float dq = (fminf(fmaxf(rintf(v / s) + z, 0.0f), qmax) - z) * s;
-                const float e = v - dq;
-                acc += (v == v) ? e * e : 0.0f;
+                const double e = (double)v - (double)dq;
+                acc += (cv && r0 + 4 * r < rows) ? e * e : 0.0;    // a NaN of the input propagates, here as in a full slab
             }
         }
-        float (*rb)[64] = red[p & 1];
+        double (*rb)[64] = red[p & 1];
         rb[rg][chl] = acc;
         __syncthreads();                          // the buffer of candidate p - 1 is free again after this barrier
         if (rg == 0 && cv)
@@ -204,7 +210,7 @@ __global__ __launch_bounds__(256) void k_score_a_self(const float* __restrict__ 
 }
 
 // generic fp64 finishing reduction over partial[c][mt][Npad]: scores[c][n?] = -norm * sum
-__global__ __launch_bounds__(256) void k_finish_simple(const float* __restrict__ partial, float* __restrict__ scores,
+__global__ __launch_bounds__(256) void k_finish_simple(const double* __restrict__ partial, float* __restrict__ scores,
                                                        int MT, int N, int Npad, int keep_n, double norm) {
     __shared__ double sm[256];
     const int nn = keep_n ? N : 1;
@@ -214,7 +220,7 @@ __global__ __launch_bounds__(256) void k_finish_simple(const float* __restrict__
     double acc = 0.0;
     for (int64_t i = threadIdx.x; i < total; i += 256) {
         const int ni = (int)(i % n_cnt), mt = (int)(i / n_cnt);
-        acc += (double)partial[((int64_t)c * MT + mt) * Npad + (keep_n ? n : ni)];
+        acc += partial[((int64_t)c * MT + mt) * Npad + (keep_n ? n : ni)];
     }
     sm[threadIdx.x] = acc;
     __syncthreads();
@@ -291,7 +297,7 @@ extern "C" int adalog_score_w_self(const float* w, int rows, int I, const float*
 extern "C" int64_t adalog_score_a_self_partial_elems(int64_t rows, int I, int P) {
     const int64_t n_slab = (rows + SLAB_ROWS - 1) / SLAB_ROWS;
     const int64_t Cpad = ((I + 63) / 64) * 64;
-    return (int64_t)P * n_slab * Cpad;
+    return 2 * (int64_t)P * n_slab * Cpad;                        // in floats: the partial sums are doubles
 }
 
 // scores: [P][I] when channel_wise, else [P][1].  norm = 1/T (channel-wise) or 1/(T*I) (per tensor).
@@ -301,15 +307,17 @@ extern "C" int adalog_score_a_self(const float* x, int64_t rows, int I, const fl
     ADALOG_ARG_CHECK(x && scale && zp && partial && scores && rows >= 1 && I >= 1 && P >= 1, "score_a_self: bad arguments");
     const int n_slab = (int)((rows + SLAB_ROWS - 1) / SLAB_ROWS);
     const int Cpad = ((I + 63) / 64) * 64;
-    ADALOG_ARG_CHECK(partial_elems >= (int64_t)P * n_slab * Cpad, "score_a_self: partial buffer too small");
+    ADALOG_ARG_CHECK(partial_elems >= 2 * (int64_t)P * n_slab * Cpad, "score_a_self: partial buffer too small");
+    ADALOG_ARG_CHECK(((uintptr_t)partial & 7) == 0, "score_a_self: partial buffer must be 8-byte aligned");
+    double* part = (double*)partial;
     ADALOG_ARG_CHECK(n_slab <= 65535, "score_a_self: too many rows for one launch");
     const float qmax = (float)((1 << n_bits) - 1);
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(k_score_a_self, dim3(Cpad / 64, n_slab), dim3(256), 0, st, x, rows, I, scale, zp, P,
-                       channel_wise ? 1 : 0, qmax, partial, n_slab, Cpad);
+                       channel_wise ? 1 : 0, qmax, part, n_slab, Cpad);
     ADALOG_LAUNCH_CHECK("adalog_score_a_self");
     const int nout = P * (channel_wise ? I : 1);
-    hipLaunchKernelGGL(k_finish_simple, dim3(nout), dim3(256), 0, st, partial, scores, n_slab, I, Cpad, channel_wise ? 1 : 0, norm);
+    hipLaunchKernelGGL(k_finish_simple, dim3(nout), dim3(256), 0, st, part, scores, n_slab, I, Cpad, channel_wise ? 1 : 0, norm);
     ADALOG_LAUNCH_CHECK("adalog_score_a_self/finish");
     return 0;
 }

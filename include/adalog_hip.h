@@ -377,7 +377,8 @@ int adalog_score_w_self(const float* w, int rows, int I, const float* scale, con
 
 /* ---- K10  _search_best_a_scale_self                                   reference linear.py:320-345
  * x: [rows][I] read ONCE for all P candidates.  channel_wise: scale/zp [P][I] -> scores [P][I], norm = 1/T;
- * else scale/zp [P][1] -> scores [P][1], norm = 1/(T*I).  partial: scratch of adalog_score_a_self_partial_elems floats. */
+ * else scale/zp [P][1] -> scores [P][1], norm = 1/(T*I).  partial: scratch of adalog_score_a_self_partial_elems floats,
+ * 8-byte aligned (it holds the slabs' partial sums as doubles). */
 int adalog_score_a_self(const float* x, int64_t rows, int I, const float* scale, const float* zp, int P, int channel_wise,
                         int n_bits, double norm, float* partial, int64_t partial_elems, float* scores, void* stream);
 int64_t adalog_score_a_self_partial_elems(int64_t rows, int I, int P);
