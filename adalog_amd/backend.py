@@ -26,6 +26,13 @@ def get():
     return _backend
 
 
+def route_ok(route: str, *shape) -> bool:
+    """The backend has the kernel route ``route`` and its ``<route>_ok(*shape)`` takes the call (the stand-in backend of the host-logic
+    tests lacks some routes; the HIP backend has them all)."""
+    ok = getattr(get(), route + "_ok", None)
+    return ok is not None and bool(ok(*shape))
+
+
 def set_backend(impl):
     """Test hook (host-logic unit tests only).  Pass None to restore strict HIP resolution."""
     global _backend

@@ -15,6 +15,7 @@ import torch.nn.functional as F
 from .. import backend, search, train_mm
 from ..ops import BF16, F32, Strided, pad_k
 from ..quantizers.uniform import UniformQuantizer
+from .linear import score_chunks
 
 MAX_PACK_BYTES = int(os.environ.get('ADALOG_MAX_PACK_GIB', '8')) << 30
 SPLIT3_INPUT = os.environ.get('ADALOG_CONV_SPLIT3', '1') != '0'   # unquantised input as three exact bf16 terms (else fp32 MFMA)
@@ -163,18 +164,14 @@ class AsymmetricallyBatchingQuantConv2d(PTQSLBatchingQuantConv2d):
         chunk = max(1, min(P, MAX_PACK_BYTES // max(1, oc * pad_k(K, F32) * (6 if split3 else 4))))
         ones = search.const_tensor([1.0], xp.device)
         bias = None if self.bias is None else Strided(self.bias.data, n=1)
-        out = []
-        for s in range(0, P, chunk):
-            e = min(P, s + chunk)
-            sc, zc = scale[s:e].contiguous(), zp[s:e].contiguous()
-            wp = be.pack_uniform(self._w2().unsqueeze(0), sc, zc, e - s, oc, 1, 0, 1, self.w_quantizer.n_bits, dt,
-                                 c_inner=True)
+
+        def score(n, defer, sc, zc):
+            wp = be.pack_uniform(self._w2().unsqueeze(0), sc, zc, n, oc, 1, 0, 1, self.w_quantizer.n_bits, dt, c_inner=True)
             if split3:
                 wp = wp.repeat(1, 1, 1, 3)              # [hi | mid | lo] of x each meet the same integers
-            out.append(be.gemm_score(dt, xp, wp, M, oc, e - s, 1, 1, ref, Strided(ones), Strided(sc, c=oc, n=1), bias,
-                                     False, True, 1.0 / fmap, ref_div=e - s, order=2, ref_transposed=True,
-                                     defer=defer and chunk >= P))
-        return out[0] if len(out) == 1 else torch.cat(out, 0)
+            return be.gemm_score(dt, xp, wp, M, oc, n, 1, 1, ref, Strided(ones), Strided(sc, c=oc, n=1), bias,
+                                 False, True, 1.0 / fmap, ref_div=n, order=2, ref_transposed=True, defer=defer)
+        return score_chunks(P, chunk, defer, (scale, zp), score)
 
     def weight_fpcs(self, fpcs_width=16, steps=4):
         """conv.py:292-311."""
@@ -185,7 +182,7 @@ class AsymmetricallyBatchingQuantConv2d(PTQSLBatchingQuantConv2d):
         xp = self._pack_x(patches)
         ref = self.raw_out.permute(1, 0, 2, 3).reshape(1, self.out_channels, M).contiguous()      # [1, oc, tokens]
         scale, zp, delta = search.weight_grid(self._w2(), self.w_quantizer.n_bits, self.eq_n, conv=True)
-        fn = lambda s, z, t: self._score_w(xp, ref, M, gh * gw, s, z, defer=True)
+        fn = search.Scorer(lambda s, z, t: self._score_w(xp, ref, M, gh * gw, s, z, defer=True))
         wq = self.w_quantizer
         res = search.fpcs(scale, zp, None, delta, fn, steps, fpcs_width, self.eq_n, None,
                           commit_to=search.commit_targets(wq.scale, wq.zero_point, None))
@@ -196,19 +193,12 @@ class AsymmetricallyBatchingQuantConv2d(PTQSLBatchingQuantConv2d):
     def hyperparameter_searching(self):
         """conv.py:313-334 for the shipped configuration (qconv_a_bit = 8: the input is not quantised and the loop
         breaks after the first weight FPCS, conv.py:328-331)."""
-        search.forget_grids()                     # percentile grids are memoised per search call only
-        if not self.fpcs:
-            raise NotImplementedError("non-FPCS search is not part of the accelerated path")
-        if self.a_quantizer.n_bits < 8:
-            raise NotImplementedError("input quantisation of the patch embedding (<8 bit) is dead code in the reference "
-                                      "(conv.py:267,329 reference undefined names) and is not implemented")
-        self._initialize_calib_parameters()
-        scale, zp, _ = search.weight_grid(self._w2(), self.w_quantizer.n_bits, self.eq_n, conv=True)
-        self.w_quantizer.scale.data.copy_(scale[-2].view(-1, 1))           # conv.py:319-320
-        self.w_quantizer.zero_point.data.copy_(zp[-2].view(-1, 1))
-        self.w_quantizer.inited = True
-        self.weight_fpcs(steps=self.steps)
-        self.calibrated = True
-        search.forget_grids()
-        del self.raw_input, self.raw_out
-        return None
+        with search.search_scope(self):
+            if self.a_quantizer.n_bits < 8:
+                raise NotImplementedError("input quantisation of the patch embedding (<8 bit) is dead code in the reference "
+                                          "(conv.py:267,329 reference undefined names) and is not implemented")
+            scale, zp, _ = search.weight_grid(self._w2(), self.w_quantizer.n_bits, self.eq_n, conv=True)
+            self.w_quantizer.scale.data.copy_(scale[-2].view(-1, 1))           # conv.py:319-320
+            self.w_quantizer.zero_point.data.copy_(zp[-2].view(-1, 1))
+            self.w_quantizer.inited = True
+            self.weight_fpcs(steps=self.steps)

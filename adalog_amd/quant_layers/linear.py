@@ -28,8 +28,7 @@ from ..quantizers.uniform import UniformQuantizer
 
 GELU_SHIFT = 0.16997124254703522      # -min(gelu(x)), reference linear.py:749
 GELU_SHIFT32 = float(torch.tensor(GELU_SHIFT, dtype=torch.float32))     # the Parameter's fp32 value
-import os as _os
-FUSED_ACT_SEARCH = _os.environ.get("ADALOG_FUSED_ACT", "1") != "0"      # A/B switch: 0 = pack + streaming GEMM (round 1)
+FUSED_ACT_SEARCH = os.environ.get("ADALOG_FUSED_ACT", "1") != "0"      # A/B switch: 0 = pack + streaming GEMM (round 1)
 # candidates are scored in chunks when a packed operand would exceed this (8 GiB of 288: vit_large's fc2 activation search --
 # 51.6 MB per candidate -- stays whole; a chunk of 124 is not a candidate count the streaming kernel takes)
 MAX_PACK_BYTES = int(os.environ.get('ADALOG_MAX_PACK_GIB', '8')) << 30
@@ -38,17 +37,30 @@ MAX_PACK_BYTES = int(os.environ.get('ADALOG_MAX_PACK_GIB', '8')) << 30
 # activation searches (row scale in the epilogue) 2-4 % -- in round 1 the latter lost 4 %, the compiler spilled there
 FP8_WEIGHT_SEARCH_MAX_K = int(os.environ.get('ADALOG_FP8_WEIGHT_MAX_K', '768'))
 FIXED_GRID_ONLY = os.environ.get('ADALOG_FIXED_GRID_ONLY', '1') != '0'   # fp8 decided by the fixed operand's quantiser alone (_int_dt)
-# self-MSE searches scored from the sorted tensor (csrc/sorted_score.hip); 0 = one pass over the tensor per step (round 1/2)
 # uniform activation searches: candidate operand generated in the slab kernel (1) or packed to HBM first (0, rounds 1-2)
 GEN_ACT_SEARCH = os.environ.get('ADALOG_GEN_ACT', '1') != '0'
 # uniform weight searches on the slab kernel: candidate operand generated in the kernel from the fp32 weight rows (1) or packed (0)
 GEN_W_SEARCH = os.environ.get('ADALOG_GEN_W', '1') != '0'
-# output-MSE weight searches against a per-tensor uniform activation quantiser: scored from the Gram matrix of the quantised
-# activation (csrc/gram.hip: built once per weight_fpcs call, K^2 instead of tokens * K multiply-adds per candidate row) where
-# backend.gram_ok says it pays; ADALOG_GRAM_W=0 keeps every such search on the token-form kernels
+# self-MSE searches scored from the sorted tensor (csrc/sorted_score.hip); 0 = one pass over the tensor per step (round 1/2)
 SORTED_SELF_SEARCH = os.environ.get('ADALOG_SORTED_SELF', '1') != '0'
 RUN_DEAD_W_SELF = os.environ.get('ADALOG_DEAD_W_SELF', '0') == '1'
 MIXED_W_SEARCH = os.environ.get('ADALOG_MIXED_W', '1') != '0'     # bf16 activations x fp8 weight candidates (wide streaming kernel)
+
+
+def _has_tails():
+    """the backend runs FPCS step tails inside scoring launches (the Gram scorers are fused_tail exactly then)"""
+    return getattr(backend.get(), "FpcsTail", None) is not None
+
+
+def score_chunks(P: int, chunk: int, defer: bool, planes, score):
+    """The P candidates of a scoring call in launches of at most ``chunk`` (what a packed operand may take of HBM):
+    ``score(n, defer, *planes[s:s + n])`` per chunk.  Partial sums are deferred only when one launch takes all candidates; one chunk
+    returns its result as it is, several are concatenated along the candidate axis."""
+    out = []
+    for s in range(0, P, chunk):
+        e = min(P, s + chunk)
+        out.append(score(e - s, defer and chunk >= P, *(p[s:e].contiguous() for p in planes)))
+    return out[0] if len(out) == 1 else torch.cat(out, 0)
 
 
 class MinMaxQuantLinear(nn.Linear):
@@ -177,6 +189,8 @@ class AsymmetricallyBatchingQuantLinear(PTQSLBatchingQuantLinear):
         self.a_quantizer.forget_codes_fit()
 
     # ------------------------------------------------------------------ helpers
+    _SEARCH_CACHES = ("_ref_t", "_ref_t_key")        # keyed by the captures' storage address: dropped when a search ends or raises
+
     def _tokens_per_image(self):
         x = self.raw_input
         return x.numel() // (x.shape[0] * x.shape[-1])
@@ -251,38 +265,36 @@ class AsymmetricallyBatchingQuantLinear(PTQSLBatchingQuantLinear):
         M = xp.shape[2]
         P = scale.shape[0]
         wq = self.w_quantizer
-        out = []
         chunk = self._cand_chunk(self.out_features, pad_k(self.in_features, dt) * (2 if dt == BF16 else 1))
         # bf16 activations (AdaLog values) against <= 4-bit weight candidates: the candidates go out as fp8 (exact) and the wide
         # streaming kernel converts them in registers -- 3/4 of the bytes through the L2 -> LDS path that bounds it
         mixed = (dt == BF16 and MIXED_W_SEARCH and wq.n_bits <= 4 and chunk >= P and xp.shape[-1] % 64 == 0
-                 and hasattr(be, "gemm_mixed_ok") and be.gemm_mixed_ok(M, self.out_features, 1, 1, P, self.in_features))
+                 and backend.route_ok("gemm_mixed", M, self.out_features, 1, 1, P, self.in_features))
         cdt, gdt, kal = (FP8, BF16_FP8, 64) if mixed else (dt, dt, 128)
-        if (GEN_W_SEARCH and shift is None and dt in (I8, FP8) and chunk >= P and hasattr(be, "score_w_gen")
-                and be.score_w_gen_ok(dt, M, self.out_features, self.in_features, xp.shape[-1], P)):
+        if (GEN_W_SEARCH and shift is None and dt in (I8, FP8) and chunk >= P
+                and backend.route_ok("score_w_gen", dt, M, self.out_features, self.in_features, xp.shape[-1], P)):
             # the candidate operand is generated inside the slab kernel from the fp32 weight rows: nothing is packed
             return be.score_w_gen(dt, xp, self._w2(), scale, zp, wq.n_bits, self._ref2_t(), sa.t, None if self.bias is None else self.bias.data,
                                   1.0 / self._tokens_per_image(), defer=defer)
-        for s in range(0, P, chunk):
-            e = min(P, s + chunk)
-            sc, zc = scale[s:e].contiguous(), zp[s:e].contiguous()
+
+        def score(n, defer, sc, zc):
             bias = None if self.bias is None else Strided(self.bias.data, n=1)
-            # columns = (out channel, candidate): the e-s candidates of a channel share one reference column
+            # columns = (out channel, candidate): the n candidates of a channel share one reference column
             if shift is None:
-                wp = be.pack_uniform(self._w2().unsqueeze(0), sc, zc, e - s, self.out_features, 1, 0, 1, wq.n_bits, cdt,
+                wp = be.pack_uniform(self._w2().unsqueeze(0), sc, zc, n, self.out_features, 1, 0, 1, wq.n_bits, cdt,
                                      c_inner=True, k_align=kal)
             else:
                 # post-GELU operand is y*s - shift: the -shift term is a per-(candidate, row) constant
                 #   -shift * s_w[p,o] * sum_i (q_w - z_w)  folded into the bias (cf. reparam_bias, linear.py:999-1006)
-                wp, rowsum = be.pack_uniform(self._w2().unsqueeze(0), sc, zc, e - s, self.out_features, 1, 0, 1,
+                wp, rowsum = be.pack_uniform(self._w2().unsqueeze(0), sc, zc, n, self.out_features, 1, 0, 1,
                                              wq.n_bits, cdt, want_rowsum=True, c_inner=True, k_align=kal)
-                fold = be.shift_fold(rowsum.view(e - s, -1), sc, shift, None if self.bias is None else self.bias.data)
+                fold = be.shift_fold(rowsum.view(n, -1), sc, shift, None if self.bias is None else self.bias.data)
                 bias = Strided(fold, c=self.out_features, n=1)
-            out.append(be.gemm_score(gdt, xp, wp, M, self.out_features, e - s, 1, 1, self._ref2_t(), sa,
-                                     Strided(sc, c=self.out_features, n=1), bias, False, True,
-                                     1.0 / self._tokens_per_image(), sa_mul=sa_mul, ref_div=e - s, order=2,
-                                     ref_transposed=True, defer=defer and chunk >= P))
-        return out[0] if len(out) == 1 else torch.cat(out, 0)
+            return be.gemm_score(gdt, xp, wp, M, self.out_features, n, 1, 1, self._ref2_t(), sa,
+                                 Strided(sc, c=self.out_features, n=1), bias, False, True,
+                                 1.0 / self._tokens_per_image(), sa_mul=sa_mul, ref_div=n, order=2,
+                                 ref_transposed=True, defer=defer)
+        return score_chunks(P, chunk, defer, (scale, zp), score)
 
     def _pack_w_fixed(self, dt=I8, want_rowsum=False):
         be = backend.get()
@@ -319,27 +331,23 @@ class AsymmetricallyBatchingQuantLinear(PTQSLBatchingQuantLinear):
         x3 = self._x2().unsqueeze(0)
         M = x3.shape[1]
         P = scale.shape[0]
-        out = []
         dt = getattr(wp, "int_dt", I8)
         norm = 1.0 / (self._tokens_per_image() * self.out_features)
-        if GEN_ACT_SEARCH and scale.shape[1] == 1 and hasattr(be, "score_act_gen") and \
-                be.score_act_gen_ok(dt, self.out_features, M, self.in_features, wp.shape[-1], P):
+        if GEN_ACT_SEARCH and scale.shape[1] == 1 and \
+                backend.route_ok("score_act_gen", dt, self.out_features, M, self.in_features, wp.shape[-1], P):
             # the candidate operand is generated inside the slab kernel: nothing is packed (gemm_k_slab.inc, GEN form)
             return be.score_act_gen(dt, wp, x3[0], scale, zp, aq.n_bits, self.raw_out.reshape(-1, self.out_features),
                                     self.w_quantizer.scale.data.view(-1), None if self.bias is None else self.bias.data, norm,
                                     defer=defer)
-        chunk = self._cand_chunk(M, pad_k(self.in_features, I8))
-        for s in range(0, P, chunk):
-            e = min(P, s + chunk)
-            sc, zc = scale[s:e].contiguous(), zp[s:e].contiguous()
-            xp = be.pack_uniform(x3, sc, zc, e - s, 1, 1, 0, 0, aq.n_bits, dt, c_inner=True)
-            out.append(be.gemm_score(dt, wp, xp, self.out_features, M, e - s, 1, 1, self._ref2(),
-                                     Strided(search.const_tensor([1.0], x3.device)), Strided(sc, c=1), None,
-                                     False, False, 1.0 / (self._tokens_per_image() * self.out_features),
-                                     ref_div=e - s, order=2, ref_transposed=True,
-                                     row_scale=self.w_quantizer.scale.data.view(-1),
-                                     row_bias=None if self.bias is None else self.bias.data, defer=defer and chunk >= P))
-        return out[0] if len(out) == 1 else torch.cat(out, 0)
+
+        def score(n, defer, sc, zc):
+            xp = be.pack_uniform(x3, sc, zc, n, 1, 1, 0, 0, aq.n_bits, dt, c_inner=True)
+            return be.gemm_score(dt, wp, xp, self.out_features, M, n, 1, 1, self._ref2(),
+                                 Strided(search.const_tensor([1.0], x3.device)), Strided(sc, c=1), None,
+                                 False, False, norm, ref_div=n, order=2, ref_transposed=True,
+                                 row_scale=self.w_quantizer.scale.data.view(-1),
+                                 row_bias=None if self.bias is None else self.bias.data, defer=defer)
+        return score_chunks(P, self._cand_chunk(M, pad_k(self.in_features, I8)), defer, (scale, zp), score)
 
     def _score_w_self(self, scale, zp, tail=None):
         """linear.py:296-318: scores [P, O] = -mean_i (W - fq_p(W))^2 from the sorted weight rows (csrc/sorted_score.hip).
@@ -348,9 +356,7 @@ class AsymmetricallyBatchingQuantLinear(PTQSLBatchingQuantLinear):
         w2 = self._w2()
         if SORTED_SELF_SEARCH and be.sorted_prefix_ok(w2.shape[0], w2.shape[1], self.w_quantizer.n_bits):
             sp = search.memo_tensor_fn("spw", w2, (), lambda: be.sorted_prefix(w2))
-            if tail is not None:
-                return be.score_self_sorted(sp, scale, zp, self.w_quantizer.n_bits, 1.0 / w2.shape[1], tail=tail)
-            return be.score_self_sorted(sp, scale, zp, self.w_quantizer.n_bits, 1.0 / w2.shape[1])
+            return be.score_self_sorted(sp, scale, zp, self.w_quantizer.n_bits, 1.0 / w2.shape[1], **search.tail_kw(tail))
         return search.honour_tail(be.score_w_self(w2, scale, zp, self.w_quantizer.n_bits), tail)
 
     def _score_a_self(self, scale, zp, tail=None):
@@ -366,9 +372,7 @@ class AsymmetricallyBatchingQuantLinear(PTQSLBatchingQuantLinear):
         if SORTED_SELF_SEARCH and be.sorted_prefix_ok(S, n, self.a_quantizer.n_bits):
             sp = search.memo_tensor_fn("spa", self.raw_input, (cw,),
                                        lambda: be.sorted_prefix(x2.t().contiguous() if cw else x2.reshape(1, -1)))
-            if tail is not None:
-                return be.score_self_sorted(sp, scale, zp, self.a_quantizer.n_bits, norm, tail=tail)
-            return be.score_self_sorted(sp, scale, zp, self.a_quantizer.n_bits, norm)
+            return be.score_self_sorted(sp, scale, zp, self.a_quantizer.n_bits, norm, **search.tail_kw(tail))
         return search.honour_tail(be.score_a_self(x2, scale, zp, cw, self.a_quantizer.n_bits, norm), tail)
 
     # ------------------------------------------------------------------ FPCS (linear.py:483-523)
@@ -377,42 +381,31 @@ class AsymmetricallyBatchingQuantLinear(PTQSLBatchingQuantLinear):
             return                                 # the activation quantiser is what this search saw last round: same winner
         scale, zp, delta = search.weight_grid(self._w2(), self.w_quantizer.n_bits, self.eq_n)
         if search_strategy == "self":
-            fn = lambda s, z, t, tail=None: self._score_w_self(s, z, tail=tail)
-            fn.fused_tail = True
+            fn = search.Scorer(lambda s, z, t, tail=None: self._score_w_self(s, z, tail=tail), fused_tail=True)
         else:
-            score = self._w_scorer()
-            if getattr(score, "fused_tail", False):
-                fn = lambda s, z, t, tail=None: score(s, z, defer=True, tail=tail)
-                fn.fused_tail = True
-            else:
-                fn = lambda s, z, t: score(s, z, defer=True)
-            fn.global_scores = getattr(score, "global_scores", False)
+            fn = self._w_scorer(defer=True)
         wq = self.w_quantizer
         res = search.fpcs(scale, zp, None, delta, fn, steps, fpcs_width, self.eq_n, None,
                           commit_to=search.commit_targets(wq.scale, wq.zero_point, None))
         if res is not None:
             self._commit_w(res[0], res[1])
 
-    def _w_scorer(self):
-        """The scoring function (scale, zp, defer=False) -> scores [P, O] | PendingScores of one output-MSE weight_fpcs call, with
+    def _w_scorer(self, defer=False):
+        """The search.Scorer (scale, zp) -> scores [P, O] | PendingScores (``defer``) of one output-MSE weight_fpcs call, with
         whatever is fixed for the call (the activation quantiser: linear.py:483-503) prepared once: the Gram-form state where it
         pays, else the packed activation image of the token-form kernels."""
         gram = self._gram_state()
         if gram is not None:
             norm = 1.0 / self._tokens_per_image()
-            if getattr(backend.get(), "FpcsTail", None) is not None:
-                fn = lambda s, z, defer=False, tail=None: gram.score_w(self._w2(), s, z, self.w_quantizer.n_bits, norm, tail=tail)
-                fn.fused_tail = True                     # score_w runs the FPCS tail itself (same call)
-            else:
-                fn = lambda s, z, defer=False: gram.score_w(self._w2(), s, z, self.w_quantizer.n_bits, norm)
-            # under image sharding the state holds the all-reduced G, c, S0: the scores are final on every rank (search.fpcs)
-            fn.global_scores = bool(getattr(gram, "global_scores", False))
-            return fn
+            # score_w runs the FPCS tail itself (same call) where the backend has tails.  Under image sharding the state holds the
+            # all-reduced G, c, S0: the scores are final on every rank (search.fpcs)
+            return search.Scorer(lambda s, z, t, **tail: gram.score_w(self._w2(), s, z, self.w_quantizer.n_bits, norm, **tail),
+                                 fused_tail=_has_tails(), global_scores=getattr(gram, "global_scores", False))
         fixed = self._pack_x_fixed()
-        return lambda s, z, defer=False: self._score_w(fixed, s, z, defer=defer)
+        return search.Scorer(lambda s, z, t: self._score_w(fixed, s, z, defer=defer))
 
-    def _a_scorer(self):
-        """The scoring function (scale, zp, defer=False) -> scores [P, 1] | PendingScores of one output-MSE activation_fpcs call, with
+    def _a_scorer(self, defer=False):
+        """The search.Scorer (scale, zp) -> scores [P, 1] | PendingScores (``defer``) of one output-MSE activation_fpcs call, with
         whatever is fixed for the call (the weight quantiser: linear.py:505-523) prepared once: the Gram-form state (csrc/gram_act.hip:
         the candidates' own Gram matrices X_p^T X_p against H = Wq^T Wq, K^2 / 2 instead of O K multiply-adds per token) where
         backend.gram_act_ok takes the search, else the packed weight image of the token-form kernels."""
@@ -420,31 +413,29 @@ class AsymmetricallyBatchingQuantLinear(PTQSLBatchingQuantLinear):
         aq, wq = self.a_quantizer, self.w_quantizer
         x2 = self._x2()
         # (the weight image enters the build's int8 product as q - z: its zero point must lie on the grid, like _gram_state's)
-        if (hasattr(be, "gram_act_ok") and type(aq) is UniformQuantizer and not aq.channel_wise and aq.scale.numel() == 1
-                and getattr(wq, "_zp_on_grid", False)
-                and be.gram_act_ok(x2.shape[0], self.out_features, self.in_features, aq.n_bits, wq.n_bits, self.eq_n)):
+        if (type(aq) is UniformQuantizer and not aq.channel_wise and aq.scale.numel() == 1 and getattr(wq, "_zp_on_grid", False)
+                and backend.route_ok("gram_act", x2.shape[0], self.out_features, self.in_features, aq.n_bits, wq.n_bits, self.eq_n)):
             prep = search.memo_tensor_fn("gact", self.raw_input, (), lambda: be.GramActPrepared(x2))
             st = be.GramActState(prep, self.raw_out.reshape(-1, self.out_features), None if self.bias is None else self.bias.data,
                                  self._w2(), wq.scale.data.view(-1), wq.zero_point.data.view(-1), wq.n_bits, aq.n_bits, self.eq_n)
             norm = 1.0 / (self._tokens_per_image() * self.out_features)
-            if getattr(be, "FpcsTail", None) is not None:
-                fn = lambda s, z, defer=False, tail=None: st.score(s, z, norm, tail=tail)
-                fn.fused_tail = True                     # the finish kernel's last block ranks and writes the next grid
-                return fn
-            return lambda s, z, defer=False: st.score(s, z, norm)
+            # (where the backend has tails, the finish kernel's last block ranks and writes the next grid)
+            return search.Scorer(lambda s, z, t, **tail: st.score(s, z, norm, **tail), fused_tail=_has_tails())
         dt = self._int_dt(self.raw_input.numel() // self.in_features, prefer_fp8=self.in_features <= FP8_WEIGHT_SEARCH_MAX_K,
                           fixed=wq)
         wp = self._pack_w_fixed(dt)
         wp.int_dt = dt
-        return lambda s, z, defer=False: self._score_a(wp, s, z, defer=defer)
+        return search.Scorer(lambda s, z, t: self._score_a(wp, s, z, defer=defer))
 
     def _gram_state(self):
         """The Gram-form state of an output-MSE weight search (linear.py:355-392 with the activation quantiser fixed for the whole
         weight_fpcs call), or None where the token-form kernels serve the search: a non-uniform or per-channel activation
-        quantiser, a shape adalog_gram_ok declines (K not a multiple of 32, too few tokens per K for the form to pay)."""
+        quantiser, a shape adalog_gram_ok declines (K not a multiple of 32, too few tokens per K for the form to pay).  The state
+        (csrc/gram.hip) is built once per weight_fpcs call from the Gram matrix of the quantised activation: K^2 instead of tokens * K
+        multiply-adds per candidate row where backend.gram_ok says it pays; ADALOG_GRAM_W=0 keeps every such search on the token form."""
         be = backend.get()
         aq = self.a_quantizer
-        if not hasattr(be, "gram_ok") or type(aq) is not UniformQuantizer or aq.channel_wise or aq.scale.numel() != 1:
+        if type(aq) is not UniformQuantizer or aq.channel_wise or aq.scale.numel() != 1:
             return None
         # gram.hip stores (q - z) as int8 and bounds G by T (2^b - 1)^2: that needs the zero point inside [0, 2^bits - 1], which
         # only a committed FPCS grid point guarantees (a min/max initialisation still in force, or a loaded quantiser, may not)
@@ -454,8 +445,8 @@ class AsymmetricallyBatchingQuantLinear(PTQSLBatchingQuantLinear):
         # (image-sharded ranks: the state is built from ALL ranks' tokens -- ops.GramState all-reduces G, c, S0 once -- so the form is
         # priced on the global token count, not on this rank's share)
         from .. import parallel
-        if not be.gram_ok(x2.shape[0] * parallel.world_size(), self.out_features, self.in_features, aq.n_bits,
-                          self.w_quantizer.n_bits, self.eq_n):
+        if not backend.route_ok("gram", x2.shape[0] * parallel.world_size(), self.out_features, self.in_features, aq.n_bits,
+                                self.w_quantizer.n_bits, self.eq_n):
             return None
         return be.GramState(x2, aq.scale.data, aq.zero_point.data, aq.n_bits, self._ref2_t(),
                             None if self.bias is None else self.bias.data)
@@ -466,15 +457,9 @@ class AsymmetricallyBatchingQuantLinear(PTQSLBatchingQuantLinear):
             return
         scale, zp, delta = search.activation_grid(self.raw_input, aq.n_bits, self.eq_n, aq.channel_wise)
         if search_strategy == "self":
-            fn = lambda s, z, t, tail=None: self._score_a_self(s, z, tail=tail)
-            fn.fused_tail = True
+            fn = search.Scorer(lambda s, z, t, tail=None: self._score_a_self(s, z, tail=tail), fused_tail=True)
         else:
-            score = self._a_scorer()
-            if getattr(score, "fused_tail", False):
-                fn = lambda s, z, t, tail=None: score(s, z, defer=True, tail=tail)
-                fn.fused_tail = True
-            else:
-                fn = lambda s, z, t: score(s, z, defer=True)
+            fn = self._a_scorer(defer=True)
         res = search.fpcs(scale, zp, None, delta, fn, steps, fpcs_width, self.eq_n, 1e-4,
                           commit_to=search.commit_targets(aq.scale, aq.zero_point, None))
         if res is not None:
@@ -482,26 +467,16 @@ class AsymmetricallyBatchingQuantLinear(PTQSLBatchingQuantLinear):
 
     def hyperparameter_searching(self):
         """linear.py:525-545 with fpcs=True (the only mode the shipped configs use, configs/*.py:20)."""
-        search.forget_grids()                     # percentile grids are memoised per search call only
-        if not self.fpcs:
-            raise NotImplementedError("non-FPCS single-pass search is not part of the accelerated path (configs use fpcs=True)")
-        self._initialize_calib_parameters()
-        search.begin_rounds(self)
-        # linear.py:536: the weights' self-MSE search.  Its result is overwritten by the first round's output-MSE weight search
-        # (which reads the activation quantiser and the percentile grid, never the current weight parameters) before anything
-        # reads it, so with search_round >= 1 it is dead work and is not run (ADALOG_DEAD_W_SELF=1 runs it, as the reference does).
-        if self.search_round < 1 or RUN_DEAD_W_SELF:
-            self.weight_fpcs(steps=self.steps, search_strategy="self")
-        self.activation_fpcs(steps=self.steps, search_strategy="self")
-        for _ in range(self.search_round):
-            self.weight_fpcs(steps=self.steps, search_strategy="output")
-            self.activation_fpcs(steps=self.steps, search_strategy="output")
-        self.calibrated = True
-        search.begin_rounds(self)
-        search.forget_grids()
-        del self.raw_input, self.raw_out
-        self._ref_t = self._ref_t_key = None
-        return None
+        with search.search_scope(self, self._SEARCH_CACHES):
+            # linear.py:536: the weights' self-MSE search.  Its result is overwritten by the first round's output-MSE weight search
+            # (which reads the activation quantiser and the percentile grid, never the current weight parameters) before anything
+            # reads it, so with search_round >= 1 it is dead work and is not run (ADALOG_DEAD_W_SELF=1 runs it, as the reference does).
+            if self.search_round < 1 or RUN_DEAD_W_SELF:
+                self.weight_fpcs(steps=self.steps, search_strategy="self")
+            self.activation_fpcs(steps=self.steps, search_strategy="self")
+            for _ in range(self.search_round):
+                self.weight_fpcs(steps=self.steps, search_strategy="output")
+                self.activation_fpcs(steps=self.steps, search_strategy="output")
 
     # ------------------------------------------------------------------ quantised forward (linear.py:46-51), fused
     def quant_forward(self, x, addend=None):
@@ -693,6 +668,8 @@ class PostGeluLogBasedBatchingQuantLinear(AsymmetricallyBatchingQuantLinear):
         return cand, scales
 
     # ---- fixed operands
+    _SEARCH_CACHES = AsymmetricallyBatchingQuantLinear._SEARCH_CACHES + ("_lx", "_lx_key")
+
     def _pack_x_fixed(self):
         be = backend.get()
         aq = self.a_quantizer
@@ -728,26 +705,21 @@ class PostGeluLogBasedBatchingQuantLinear(AsymmetricallyBatchingQuantLinear):
         M = x3.shape[1]
         P = scale.shape[0]
         norm = 1.0 / (self._tokens_per_image() * self.out_features)
-        if FUSED_ACT_SEARCH and hasattr(be, "score_act_fused") and \
-                be.score_act_fused_ok(self.out_features, M, self.in_features, wp.shape[-1], P, aq.n_bits):
+        if FUSED_ACT_SEARCH and \
+                backend.route_ok("score_act_fused", self.out_features, M, self.in_features, wp.shape[-1], P, aq.n_bits):
             # quantise-in-the-loader kernel: the [M*P, K] candidate operand is never written (gemm_fused.hip)
             return be.score_act_fused(wp, x3[0], self._log2_x(), self.raw_out.reshape(-1, self.out_features),
                                       self.w_quantizer.scale.data.view(-1), bias_fold, scale.reshape(-1), qv.reshape(-1),
                                       aq.n_bits, self._mant37(dev), self._shift32(), True, self._ts32(), norm)
-        out = []
-        chunk = self._cand_chunk(M, pad_k(self.in_features, BF16) * 2)
-        for s in range(0, P, chunk):
-            e = min(P, s + chunk)
-            sc, qc = scale[s:e].contiguous(), qv[s:e].contiguous()
-            xp = be.pack_adalog(x3, sc, qc, e - s, 1, 1, 0, aq.n_bits, self._mant37(dev), shift=aq.shift.data, clamp_u=True,
+
+        def score(n, defer, sc, qc):
+            xp = be.pack_adalog(x3, sc, qc, n, 1, 1, 0, aq.n_bits, self._mant37(dev), shift=aq.shift.data, clamp_u=True,
                                 c_inner=True)
-            out.append(be.gemm_score(BF16, wp, xp, self.out_features, M, e - s, 1, 1, self._ref2(),
-                                     Strided(search.const_tensor([1.0], dev)), Strided(sc, c=1), None, False, False,
-                                     1.0 / (self._tokens_per_image() * self.out_features), sa_mul=self._ts32(),
-                                     ref_div=e - s, order=2, ref_transposed=True,
-                                     row_scale=self.w_quantizer.scale.data.view(-1), row_bias=bias_fold,
-                                     defer=defer and chunk >= P))
-        return out[0] if len(out) == 1 else torch.cat(out, 0)
+            return be.gemm_score(BF16, wp, xp, self.out_features, M, n, 1, 1, self._ref2(),
+                                 Strided(search.const_tensor([1.0], dev)), Strided(sc, c=1), None, False, False,
+                                 norm, sa_mul=self._ts32(), ref_div=n, order=2, ref_transposed=True,
+                                 row_scale=self.w_quantizer.scale.data.view(-1), row_bias=bias_fold, defer=defer)
+        return score_chunks(P, self._cand_chunk(M, pad_k(self.in_features, BF16) * 2), defer, (scale, qv), score)
 
     def activation_fpcs(self, ud_candidates, base_num=8, scale_num=16, fpcs_width=32, steps=6):
         """linear.py:941-967: 128 log bases -> top-8 bases x 16 scales -> width-32 FPCS with 4 neighbours."""
@@ -771,7 +743,7 @@ class PostGeluLogBasedBatchingQuantLinear(AsymmetricallyBatchingQuantLinear):
         delta = (scales16[1:2] - scales16[0:1]).view(1).contiguous()
         scale = scales16.repeat(base_num, 1).contiguous()                           # a.repeat(1, base_num) layout
         qv = top_q.repeat_interleave(scale_num, dim=0).contiguous()
-        fn = lambda s, z, t: self._score_scale_logbase(wp, bias_fold, s, t, defer=True)
+        fn = search.Scorer(lambda s, z, t: self._score_scale_logbase(wp, bias_fold, s, t, defer=True))
         res = search.fpcs(scale, None, qv, delta, fn, steps, fpcs_width, self.eq_n, None)
         if res is not None:
             aq.scale.data.copy_(res[0].view(aq.scale.shape))
@@ -781,13 +753,8 @@ class PostGeluLogBasedBatchingQuantLinear(AsymmetricallyBatchingQuantLinear):
 
     def hyperparameter_searching(self):
         """linear.py:969-997 with fpcs=True."""
-        search.forget_grids()                     # percentile grids are memoised per search call only
-        if not self.fpcs:
-            raise NotImplementedError("non-FPCS search is not part of the accelerated path")
-        self._initialize_calib_parameters()
-        self._shift_host = None
-        search.begin_rounds(self)
-        try:
+        with search.search_scope(self, self._SEARCH_CACHES):
+            self._shift_host = None
             self.weight_fpcs(steps=self.steps, search_strategy="self")
             ud_candidates, input_scale_candidates = self.calculate_percentile_activation_candidates()
             self.a_quantizer.scale.data.copy_(input_scale_candidates[:, -2])
@@ -796,14 +763,6 @@ class PostGeluLogBasedBatchingQuantLinear(AsymmetricallyBatchingQuantLinear):
             for _ in range(self.search_round):
                 self.activation_fpcs(ud_candidates=ud_candidates, steps=self.steps)
                 self.weight_fpcs(steps=self.steps, search_strategy="output")
-        finally:
-            # the caches are keyed by storage address: they must not outlive this search, whether it ends or raises
-            search.forget_grids()
-            search.begin_rounds(self)
-            self._ref_t = self._ref_t_key = None
-            self._lx = self._lx_key = None
-        self.calibrated = True
-        del self.raw_input, self.raw_out
 
     def reparam_bias(self):
         """linear.py:999-1006: bias += (-shift * 1^T) . q_w(W)^T, then the quantiser stops subtracting the shift."""

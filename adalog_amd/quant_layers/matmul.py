@@ -17,6 +17,7 @@ from ..ops import BF16, BF16_FP8, FP8, I8, Strided, pad_k  # noqa: F401
 from ..ops import mixed_k_align as ops_mixed_k_align
 from ..quantizers.logarithm import AdaLogQuantizer
 from ..quantizers.uniform import UniformQuantizer
+from .linear import score_chunks
 
 MAX_PACK_BYTES = int(os.environ.get('ADALOG_MAX_PACK_GIB', '8')) << 30
 # uniform attention candidates generated inside the scoring kernel instead of packed (adalog_gemm_score_gen): 'all' = wherever the
@@ -109,6 +110,8 @@ class AsymmetricallyBatchingQuantMatMul(PTQSLBatchingQuantMatMul):
         self.B_quantizer.zero_point = nn.Parameter(torch.zeros(*target_shape))
 
     # ------------------------------------------------------------------ views
+    _SEARCH_CACHES = ("_ref_t", "_ref_t_key", "_bt_c", "_bt_key")    # keyed by the captures' storage address (search.search_scope)
+
     def _heads(self):
         return self.num_heads if self.head_channel_wise else 1
 
@@ -219,59 +222,48 @@ class AsymmetricallyBatchingQuantMatMul(PTQSLBatchingQuantMatMul):
         G, S, K, Sp = self._dims()
         A, B = self.raw_input
         P = scale.shape[0]
-        src = self._a3(A) if which == "A" else self._bt3_packable(B)
-        bits = self.A_quantizer.n_bits if which == "A" else self.B_quantizer.n_bits
-        rows = S if which == "A" else Sp
+        pg = 1 if H > 1 else 0
+        # the GEMM of ``which``: the searched operand's source and bits, output rows / columns (the candidates' rows run along the columns)
+        if which == "A":
+            src, bits, mrows, ncols = self._a3(A), self.A_quantizer.n_bits, Sp, S
+        else:
+            src, bits, mrows, ncols = self._bt3_packable(B), self.B_quantizer.n_bits, S, Sp
         mixed = dt == BF16_FP8                     # fixed operand bf16 [.., Kp], candidates fp8 [.., Kp]: Kp = 64, 256 or 208 (ops.gemm_mixed_ok / _ktrim)
         cdt = FP8 if mixed else dt                 # what the candidates are packed as
         esz = 2 if dt == BF16 else 1
         # mixed: the candidates' rows are as long as those of the fixed operand the caller packed (gemm_score needs one Kp): the trimmed
         # 208 when it was packed with _mixed_kalign, 256 / 64 otherwise
         al = ops_mixed_k_align(K, fixed.shape[-1])[0] if mixed else self._kalign(dt)
-        chunk = self._cand_chunk(G * rows * pad_k(K, cdt, al) * esz)
+        chunk = self._cand_chunk(G * ncols * pad_k(K, cdt, al) * esz)
         if mixed and chunk < P:
             raise RuntimeError("the mixed softmax.v search scores all candidates in one launch")
-        pg = 1 if H > 1 else 0
-        mrows, ncols = (Sp, S) if which == "A" else (S, Sp)
-        if (GEN_MM != '0' and dt in (I8, FP8) and chunk >= P and K % 16 == 0 and K <= 64 and hasattr(be, "gemm_score_gen")
-                and (dt != FP8 or bits <= 4) and src.dtype == torch.float32
-                and be.gemm_score_gen_ok(dt, mrows, ncols, G, H, P, K, fixed.shape[-1])
-                and (GEN_MM == 'all' or be.gemm_win_ok(dt, mrows, ncols, G, H, P, K))):
-            sc, zc = scale.contiguous(), zp.contiguous()
-            sb = Strided(sc, c=H, g=pg)
-            if which == "A":
-                sa, ref = Strided(self.B_quantizer.scale.data.view(-1), g=pg), self._ref3()
-            else:
-                sa = fixed_sa if fixed_sa is not None else Strided(self.A_quantizer.scale.data.view(-1), g=pg)
-                ref = self._ref3_t()
-            pend = be.gemm_score_gen(dt, fixed, src, zc, bits, mrows, ncols, P, G, H, ref, sa, sb, self.head_channel_wise,
-                                     self._norm(A, S, Sp), sa_mul=sa_mul)
-            return pend if defer else pend.finish()
-        if (gen and mixed and which == "B" and hasattr(be, "gemm_score_avw") and src.dtype == torch.float32 and src.is_contiguous()
-                and be.gemm_score_avw_ok(S, Sp, G, H, P, K, fixed.shape[-1], bits)):
-            # the P quantisations of v are generated inside the kernel (adalog_gemm_score_avw): nothing is packed
-            sc, zc = scale.contiguous(), zp.contiguous()
+        # ... its reference (transposed in place for A) and the fixed operand's scale; the candidates' scales follow the chunk
+        if which == "A":
+            ref, sa = self._ref3(), Strided(self.B_quantizer.scale.data.view(-1), g=pg)
+        else:
+            ref = self._ref3_t()
             sa = fixed_sa if fixed_sa is not None else Strided(self.A_quantizer.scale.data.view(-1), g=pg)
-            pend = be.gemm_score_avw(fixed, src, zc, bits, S, Sp, P, G, H, self._ref3_t(), sa, Strided(sc, c=H, g=pg),
-                                     self.head_channel_wise, self._norm(A, S, Sp), sa_mul=sa_mul)
+        sb = lambda sc: Strided(sc, c=H, g=pg)
+        norm = self._norm(A, S, Sp)
+        if (GEN_MM != '0' and dt in (I8, FP8) and chunk >= P and K % 16 == 0 and K <= 64
+                and (dt != FP8 or bits <= 4) and src.dtype == torch.float32
+                and backend.route_ok("gemm_score_gen", dt, mrows, ncols, G, H, P, K, fixed.shape[-1])
+                and (GEN_MM == 'all' or be.gemm_win_ok(dt, mrows, ncols, G, H, P, K))):
+            pend = be.gemm_score_gen(dt, fixed, src, zp.contiguous(), bits, mrows, ncols, P, G, H, ref, sa, sb(scale.contiguous()),
+                                     self.head_channel_wise, norm, sa_mul=sa_mul)
             return pend if defer else pend.finish()
-        out = []
-        for s0 in range(0, P, chunk):
-            e = min(P, s0 + chunk)
-            sc, zc = scale[s0:e].contiguous(), zp[s0:e].contiguous()
-            cand = be.pack_uniform(src, sc, zc, e - s0, H, H, pg, 0, bits, cdt, c_inner=True, k_align=al)
-            sb = Strided(sc, c=H, g=pg)
-            if which == "A":
-                sa = Strided(self.B_quantizer.scale.data.view(-1), g=pg)
-                out.append(be.gemm_score(dt, fixed, cand, Sp, S, e - s0, G, H, self._ref3(), sa, sb, None,
-                                         self.head_channel_wise, False, self._norm(A, S, Sp), sa_mul=sa_mul,
-                                         ref_div=e - s0, order=2, ref_transposed=True, defer=defer and chunk >= P))
-            else:
-                sa = fixed_sa if fixed_sa is not None else Strided(self.A_quantizer.scale.data.view(-1), g=pg)
-                out.append(be.gemm_score(dt, fixed, cand, S, Sp, e - s0, G, H, self._ref3_t(), sa, sb, None,
-                                         self.head_channel_wise, False, self._norm(A, S, Sp), sa_mul=sa_mul,
-                                         ref_div=e - s0, order=2, ref_transposed=True, defer=defer and chunk >= P))
-        return out[0] if len(out) == 1 else torch.cat(out, 0)
+        if (gen and mixed and which == "B" and src.dtype == torch.float32 and src.is_contiguous()
+                and backend.route_ok("gemm_score_avw", mrows, ncols, G, H, P, K, fixed.shape[-1], bits)):
+            # the P quantisations of v are generated inside the kernel (adalog_gemm_score_avw): nothing is packed
+            pend = be.gemm_score_avw(fixed, src, zp.contiguous(), bits, mrows, ncols, P, G, H, ref, sa, sb(scale.contiguous()),
+                                     self.head_channel_wise, norm, sa_mul=sa_mul)
+            return pend if defer else pend.finish()
+
+        def score(n, defer, sc, zc):
+            cand = be.pack_uniform(src, sc, zc, n, H, H, pg, 0, bits, cdt, c_inner=True, k_align=al)
+            return be.gemm_score(dt, fixed, cand, mrows, ncols, n, G, H, ref, sa, sb(sc), None, self.head_channel_wise, False,
+                                 norm, sa_mul=sa_mul, ref_div=n, order=2, ref_transposed=True, defer=defer)
+        return score_chunks(P, chunk, defer, (scale, zp), score)
 
     def _commit(self, quantizer, scale, zp):
         search.commit_param(quantizer.scale, scale)             # (no copy when the search's last kernel wrote them in place)
@@ -293,7 +285,7 @@ class AsymmetricallyBatchingQuantMatMul(PTQSLBatchingQuantMatMul):
         scale, zp, delta = search.matmul_grid(x, self.B_quantizer.n_bits, self.eq_n, self.head_channel_wise)
         if fixed is None:
             fixed = self._pack_fixed("B" if which == "A" else "A", dt)
-        fn = lambda s, z, t: self._score(which, fixed, s, z, dt, fixed_sa, sa_mul, defer=True, gen=gen)
+        fn = search.Scorer(lambda s, z, t: self._score(which, fixed, s, z, dt, fixed_sa, sa_mul, defer=True, gen=gen))
         q = self.A_quantizer if which == "A" else self.B_quantizer
         res = search.fpcs(scale, zp, None, delta, fn, steps, fpcs_width, self.eq_n, None,
                           commit_to=search.commit_targets(q.scale, q.zero_point, None))
@@ -310,27 +302,16 @@ class AsymmetricallyBatchingQuantMatMul(PTQSLBatchingQuantMatMul):
 
     def hyperparameter_searching(self):
         """matmul.py:264-283 with fpcs=True."""
-        search.forget_grids()                     # percentile grids are memoised per search call only
-        if not self.fpcs:
-            raise NotImplementedError("non-FPCS search is not part of the accelerated path")
-        self._initialize_calib_parameters()
-        search.begin_rounds(self)
-        self._init_from_grid("A")
-        self._init_from_grid("B")
-        G, S, K, Sp = self._dims()
-        # both zero points come from the percentile grid (_init_from_grid, then FPCS commits): fp8 storage when <= 4 bit
-        dt = search.int_operand_dtype(self.A_quantizer.n_bits, self.B_quantizer.n_bits,
-                                      self._cand_chunk(G * max(S, Sp) * pad_k(K, I8)), prefer_fp8=K <= 64)
-        for _ in range(self.search_round):
-            self._fpcs("A", steps=self.steps, dt=dt)
-            self._fpcs("B", steps=self.steps, dt=dt)
-        self.calibrated = True
-        search.begin_rounds(self)
-        search.forget_grids()
-        del self.raw_input, self.raw_out
-        self._ref_t = self._ref_t_key = None
-        self._bt_c = self._bt_key = None
-        return None
+        with search.search_scope(self, self._SEARCH_CACHES):
+            self._init_from_grid("A")
+            self._init_from_grid("B")
+            G, S, K, Sp = self._dims()
+            # both zero points come from the percentile grid (_init_from_grid, then FPCS commits): fp8 storage when <= 4 bit
+            dt = search.int_operand_dtype(self.A_quantizer.n_bits, self.B_quantizer.n_bits,
+                                          self._cand_chunk(G * max(S, Sp) * pad_k(K, I8)), prefer_fp8=K <= 64)
+            for _ in range(self.search_round):
+                self._fpcs("A", steps=self.steps, dt=dt)
+                self._fpcs("B", steps=self.steps, dt=dt)
 
     # ------------------------------------------------------------------ fused quantised forward (matmul.py:43-45)
     def _training(self):
@@ -397,8 +378,8 @@ class PostSoftmaxAsymmetricallyBatchingQuantMatMul(AsymmetricallyBatchingQuantMa
         q_all = search.const_tensor([float(i) for i in range(10, 11 + self.eq_n)], dev)[:self.eq_n]
         P = self.eq_n
         ones = search.const_tensor([1.0] * P, dev)
-        if (GEN_AVQ and hasattr(be, "gemm_score_avq") and A.dtype == torch.float32
-                and be.gemm_score_avq_ok(Sp, S, G, H, P, K, bp.shape[-1], self.A_quantizer.n_bits)):
+        if (GEN_AVQ and A.dtype == torch.float32
+                and backend.route_ok("gemm_score_avq", Sp, S, G, H, P, K, bp.shape[-1], self.A_quantizer.n_bits)):
             # the 128 quantisations of the probabilities are generated inside the kernel (adalog_gemm_score_avq): nothing is packed
             key = (P, self.A_quantizer.n_bits, str(dev))
             if getattr(self, "_avq_lut_key", None) != key:
@@ -406,18 +387,16 @@ class PostSoftmaxAsymmetricallyBatchingQuantMatMul(AsymmetricallyBatchingQuantMa
             return q_all, be.gemm_score_avq(bp, self._a3(A), q_all, self._avq_lut, self.A_quantizer.n_bits, Sp, S, P, G, H,
                                             self._ref3(), Strided(self.B_quantizer.scale.data.view(-1), g=pg), Strided(ones, c=1),
                                             1.0 / (A.shape[1] * S * Sp), sa_mul=self._ts32())
-        chunk = self._cand_chunk(G * S * pad_k(K, BF16, self._kalign()) * 2)
-        out = []
-        for s0 in range(0, P, chunk):
-            e = min(P, s0 + chunk)
+
+        def score(n, defer, qc, oc):
             # transposed product: rows = head-dim columns of v, GEMM columns = (attention row, candidate base)
-            ap = self._pack_A_adalog(self._a3(A), q_all[s0:e].contiguous(), ones[s0:e].contiguous(), e - s0, False,
-                                     c_inner=True, k_align=self._kalign())
-            out.append(be.gemm_score(BF16, bp, ap, Sp, S, e - s0, G, H, self._ref3(),
-                                     Strided(self.B_quantizer.scale.data.view(-1), g=pg), Strided(ones[s0:e].contiguous(), c=1),
-                                     None, False, False, 1.0 / (A.shape[1] * S * Sp), sa_mul=self._ts32(),
-                                     ref_div=e - s0, order=2, ref_transposed=True))
-        return q_all, (out[0] if len(out) == 1 else torch.cat(out, 0))
+            ap = self._pack_A_adalog(self._a3(A), qc, oc, n, False, c_inner=True, k_align=self._kalign())
+            return be.gemm_score(BF16, bp, ap, Sp, S, n, G, H, self._ref3(),
+                                 Strided(self.B_quantizer.scale.data.view(-1), g=pg), Strided(oc, c=1),
+                                 None, False, False, 1.0 / (A.shape[1] * S * Sp), sa_mul=self._ts32(),
+                                 ref_div=n, order=2, ref_transposed=True)
+        chunk = self._cand_chunk(G * S * pad_k(K, BF16, self._kalign()) * 2)
+        return q_all, score_chunks(P, chunk, False, (q_all, ones), score)
 
     def _mixed_B_search(self):
         """bf16 rows x fp8 candidate columns for the B (v) search: needs exact fp8 candidates (<= 4 bit), one of the kernels' shape
@@ -425,11 +404,10 @@ class PostSoftmaxAsymmetricallyBatchingQuantMatMul(AsymmetricallyBatchingQuantMa
         one launch."""
         if not MIXED_B_SEARCH or self.B_quantizer.n_bits > 4 or self.eq_n not in (64, 128, 256):
             return False
-        be = backend.get()
         G, S, K, Sp = self._dims()
-        if not hasattr(be, "gemm_mixed_ok") or self._cand_chunk(G * Sp * (64 if K <= 64 else 256)) < self.eq_n:
+        if self._cand_chunk(G * Sp * (64 if K <= 64 else 256)) < self.eq_n:
             return False
-        return bool(be.gemm_mixed_ok(S, Sp, G, self._heads(), self.eq_n, K))
+        return backend.route_ok("gemm_mixed", S, Sp, G, self._heads(), self.eq_n, K)
 
     def _search_best_A_log_base(self):
         """matmul.py:321-358: score the 128 bases, commit the best."""
@@ -446,36 +424,25 @@ class PostSoftmaxAsymmetricallyBatchingQuantMatMul(AsymmetricallyBatchingQuantMa
 
     def hyperparameter_searching(self):
         """matmul.py:360-378."""
-        search.forget_grids()                     # percentile grids are memoised per search call only
-        if not self.fpcs:
-            raise NotImplementedError("non-FPCS search is not part of the accelerated path")
-        self._initialize_calib_parameters()
-        search.begin_rounds(self)
-        self._init_from_grid("B")
-        A = self.raw_input[0]
-        dev = A.device
-        for _ in range(self.search_round):
-            self._search_best_A_log_base()
-            if search.round_is_redundant(self, "B", self.A_quantizer):
-                continue                           # same log base as last round: the B search would repeat itself
-            # B search against q_A(A): eval-form AdaLog of A (clamped, scale 1) is the fixed bf16 operand.  When the shape allows
-            # (197 keys, <= 4-bit v) the 128 x candidates are packed as fp8 and converted to bf16 inside the kernel: the operand
-            # a launch streams is 256 instead of 448 bytes per column
-            mixed = self._mixed_B_search()
-            qv = search.const_tensor([float(self._q_host)], dev)
-            K = A.shape[-1]
-            ap = self._pack_A_adalog(self._a3(A), qv, self.A_quantizer.scale.data.view(-1), 1, True,
-                                     k_align=self._mixed_kalign()[1] if mixed else self._kalign())
-            self._fpcs("B", steps=self.steps, fixed=ap, dt=BF16_FP8 if mixed else BF16,
-                       fixed_sa=Strided(self.A_quantizer.scale.data.view(-1)), sa_mul=self._ts32(), checked=True,
-                       gen=mixed and AV_GEN and K > 64)    # (K <= 64: windows, the mixed launch there is k_gemm_winb and stays)
-        self.calibrated = True
-        search.begin_rounds(self)
-        search.forget_grids()
-        del self.raw_input, self.raw_out
-        self._ref_t = self._ref_t_key = None
-        self._bt_c = self._bt_key = None
-        return None
+        with search.search_scope(self, self._SEARCH_CACHES):
+            self._init_from_grid("B")
+            A = self.raw_input[0]
+            dev = A.device
+            for _ in range(self.search_round):
+                self._search_best_A_log_base()
+                if search.round_is_redundant(self, "B", self.A_quantizer):
+                    continue                           # same log base as last round: the B search would repeat itself
+                # B search against q_A(A): eval-form AdaLog of A (clamped, scale 1) is the fixed bf16 operand.  When the shape allows
+                # (197 keys, <= 4-bit v) the 128 x candidates are packed as fp8 and converted to bf16 inside the kernel: the operand
+                # a launch streams is 256 instead of 448 bytes per column
+                mixed = self._mixed_B_search()
+                qv = search.const_tensor([float(self._q_host)], dev)
+                K = A.shape[-1]
+                ap = self._pack_A_adalog(self._a3(A), qv, self.A_quantizer.scale.data.view(-1), 1, True,
+                                         k_align=self._mixed_kalign()[1] if mixed else self._kalign())
+                self._fpcs("B", steps=self.steps, fixed=ap, dt=BF16_FP8 if mixed else BF16,
+                           fixed_sa=Strided(self.A_quantizer.scale.data.view(-1)), sa_mul=self._ts32(), checked=True,
+                           gen=mixed and AV_GEN and K > 64)    # (K <= 64: windows, the mixed launch there is k_gemm_winb and stays)
 
     def quant_forward(self, A, B, a_pre=False, b_pre=False):
         assert self.calibrated, f"Module should be calibrated before run quant_forward for {self}"

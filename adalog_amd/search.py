@@ -11,6 +11,7 @@ scores (RCCL over xGMI) and then run the identical deterministic top-k -- no bro
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Callable, Optional
 
 import torch
@@ -187,6 +188,45 @@ def fpcs(scale, zp, third, delta, score_fn: Callable, steps: int, width: int = 1
         remain -= 1
         first = False
     return None
+
+
+def tail_kw(tail):
+    """keyword arguments that pass an FPCS tail on only when one was given (a backend without tails has no such parameter)"""
+    return {} if tail is None else {"tail": tail}
+
+
+class Scorer:
+    """The scoring function of one FPCS call, ``scorer(scale, zp, third=None, tail=None)`` -> scores [P, cols] | PendingScores, around
+    ``fn(scale, zp, third[, tail=])`` with whatever is fixed for the call bound in.  ``fused_tail``: fn takes ``tail=`` and runs the
+    FPCS tail in its own launch; ``global_scores``: the scores are final on every rank (fpcs reads both)."""
+    __slots__ = ("fn", "fused_tail", "global_scores")
+
+    def __init__(self, fn, fused_tail=False, global_scores=False):
+        self.fn, self.fused_tail, self.global_scores = fn, bool(fused_tail), bool(global_scores)
+
+    def __call__(self, scale, zp, third=None, tail=None):
+        return self.fn(scale, zp, third, **tail_kw(tail))
+
+
+@contextlib.contextmanager
+def search_scope(module, caches=()):
+    """A module's hyperparameter search.  The memoised grids, the rounds' snapshots and the module's ``caches`` (attribute names) are
+    keyed by storage address: they must not outlive this search, whether it ends or raises.  Only a search that ends marks the module
+    calibrated and releases its captures."""
+    forget_grids()                                # percentile grids are memoised per search call only
+    if not module.fpcs:
+        raise NotImplementedError("non-FPCS search is not part of the accelerated path (configs use fpcs=True)")
+    module._initialize_calib_parameters()
+    begin_rounds(module)
+    try:
+        yield
+    finally:
+        forget_grids()
+        begin_rounds(module)
+        for name in caches:
+            setattr(module, name, None)
+    module.calibrated = True
+    del module.raw_input, module.raw_out
 
 
 def commit_param(param, value):
