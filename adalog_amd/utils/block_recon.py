@@ -11,9 +11,13 @@ regulariser are fused HIP kernels (csrc/brecq.hip); block inputs/outputs stay in
 mini-batch is split over the ranks and the gradients of alpha / activation scales are all-reduced every iteration
 (RCCL over xGMI; identical seeds keep randperm in lock-step).
 """
+import collections
+import contextlib
+import functools
 import logging
 import math
 import os
+import types
 
 import torch
 import torch.nn.functional as F
@@ -88,6 +92,342 @@ class HipAdam(torch.optim.Optimizer):
             self._hstep[id(p)] = self._hstep.get(id(p), 0) + n
 
 
+def adaround_modules(block):
+    """The modules of ``block`` whose weight quantiser is an AdaRoundQuantizer, in named_modules() order."""
+    return [m for _, m in block.named_modules() if isinstance(getattr(m, 'w_quantizer', None), AdaRoundQuantizer)]
+
+
+def _trained_by_module(block, quant_act):
+    """What a block's reconstruction trains (block_recon.py:97-108): per module, in named_modules() order, (alphas, activation scales)."""
+    for _, module in block.named_modules():
+        if hasattr(module, 'mode'):
+            if isinstance(module, (MinMaxQuantLinear, MinMaxQuantConv2d)):
+                yield [module.w_quantizer.alpha], ([module.a_quantizer.scale] if quant_act else [])
+            elif isinstance(module, MinMaxQuantMatMul) and quant_act:
+                yield [], [module.A_quantizer.scale, module.B_quantizer.scale]
+
+
+def _trained(block, quant_act):
+    """-> (w_params, a_params): the two optimisers' tensors"""
+    pairs = list(_trained_by_module(block, quant_act))
+    return [t for w, _ in pairs for t in w], [t for _, a in pairs for t in a]
+
+
+def finish_block(block, end_training=True):
+    """The state a reconstructed block is left in, whether its training ended or raised."""
+    # ``end_training=False``: a block this rank does not own was never put in training mode (and end_training() would also drop a
+    # quantiser's kept codes_fit() answer)
+    for _, module in block.named_modules():
+        if hasattr(module, 'w_quantizer'):
+            module.w_quantizer.soft_targets = False
+        if hasattr(module, 'mode'):
+            module.mode = 'raw'
+        if end_training and hasattr(module, 'training_mode'):
+            module.end_training()
+
+
+# The routes of one reconstruct_single_block call, decided once by _plan(): this rank's share of the mini-batch; iterations from the
+# fourth on are one captured HIP graph (use_graph), with both optimiser steps inside it (full_graph); HipAdam, not torch.optim.Adam;
+# b, the warm-up gate and the scales' learning rate come from a _ScheduleTable (table_mode); hipBLASLt "fast fp32"; the
+# reconstruction loss on fixed images before and after (report); torch.optim.Adam's keyword arguments.
+_Plan = collections.namedtuple("_Plan", "local_bs use_graph full_graph hip_adam table_mode fast_mm report optim_kw")
+
+
+def _plan(device, ws, n_local, batch_size, iters):
+    cuda = device.type == 'cuda'
+    local_bs = max(1, batch_size // ws)
+    # One iteration is ~85 kernel launches (1.7 ms of GPU time on MI355X for a deit_small block, 58 % of it the fp32
+    # GEMMs), issued eagerly in 2.0 ms.  The iteration is captured once in a HIP graph over static batch buffers and
+    # replayed: forward, reconstruction loss, rounding regulariser (its exponent b and on/off weight live in device
+    # scalars), backward and -- single process -- both Adam steps (capturable).  20 000 iterations of the block:
+    # 496 it/s eager, 568 it/s replayed, same reached error.  With several ranks the gradient all-reduce and the
+    # optimiser steps stay eager and the graph is opt-in (ADALOG_BRECQ_GRAPH=1); ADALOG_BRECQ_GRAPH=0 forces eager.
+    use_graph = cuda and os.environ.get("ADALOG_BRECQ_GRAPH", "1" if ws == 1 else "0") == "1" and n_local >= local_bs and iters > 8
+    full_graph = use_graph and ws == 1
+    optim_kw = dict(capturable=True) if full_graph else {}
+    if cuda:
+        optim_kw['fused'] = True                         # one kernel per optimiser step instead of six foreach passes
+    # the optimiser steps: one hand-written launch per optimiser (HipAdam) on the HIP device; ADALOG_BRECQ_ADAM=torch (and the
+    # CPU tier by default) keeps torch.optim.Adam
+    hip_adam = os.environ.get("ADALOG_BRECQ_ADAM", "hip" if cuda else "torch") == "hip"
+    # ADALOG_BRECQ_FAST_MM=1: the block's plain GEMMs (linear / bmm, forward and both backward products) use hipBLASLt's
+    # "fast fp32" mode (bf16 three-term split products, relative error 4e-6 against 4e-7).  Measured on a deit_small
+    # block it is worth 4 % of the iteration (some shapes get slower kernels), so the default stays plain fp32.
+    fast_mm = cuda and os.environ.get("ADALOG_BRECQ_FAST_MM", "0") == "1"
+    report = os.environ.get("ADALOG_BRECQ_REPORT", "1") != "0" and n_local > 0
+    return _Plan(local_bs, use_graph, full_graph, hip_adam, full_graph and hip_adam, fast_mm, report, optim_kw)
+
+
+# Per-iteration rows (mini-batch indices, schedule values) are made ``ahead`` iterations at a time on the host and uploaded in one
+# non-blocking copy from pinned memory: a pageable host-to-device copy per iteration blocks the host until the previous
+# iteration's kernels have drained, i.e. the GPU idles through the host's ~0.2 ms of per-iteration work.
+# ``make_rows(it, cnt)`` -> host tensor [cnt, ...] of iterations it .. it + cnt - 1: called once per chunk, in iteration order.
+class _RowsAhead:
+    def __init__(self, make_rows, total, device, ahead=256):
+        self.make_rows, self.total, self.device, self.ahead = make_rows, total, torch.device(device), ahead
+        self.block, self.base = None, 0
+
+    def row(self, it):
+        if self.block is None or it >= self.base + self.block.shape[0]:
+            host = self.make_rows(it, min(self.ahead, self.total - it))
+            if self.device.type == 'cuda':
+                host = host.pin_memory()
+            self.block, self.base = host.to(self.device, non_blocking=True), it
+        return self.block[it - self.base]
+
+
+def _index_rows(index_source, gen, n_local, local_bs, it, cnt):
+    """The mini-batch indices of iterations it .. it + cnt - 1: one draw each, in order, from ``index_source`` or randperm on ``gen``."""
+    return torch.stack([index_source(it + k, n_local, local_bs) if index_source is not None
+                        else torch.randperm(n_local, generator=gen)[:local_bs] for k in range(cnt)])
+
+
+# Captured iterations with HipAdam: what changes from one iteration to the next besides the mini-batch -- the regulariser's
+# exponent b, its 0 / 1 warm-up gate and the cosine learning rate of the activation scales -- lives in ONE device triple the
+# captured kernels read, refreshed by one 12-byte copy per iteration from a table uploaded 256 rows at a time (two fills and the
+# scheduler's tensor arithmetic, ~7 launches, before).  The rows are computed on the host in python floats by the reference's own
+# objects (LinearTempDecay, torch's CosineAnnealingLR on a float learning rate: that of a twin SGD optimiser that trains nothing).
+# QDrop (``seed`` given): the masks' key and the iteration number live in an int32 device triple {seed_lo, seed_hi, iteration} the
+# quantisers' kernels read.  The triple and the schedule then share ONE buffer -- words {seed_lo, seed_hi, iteration, b, gate, lr}
+# -- and the schedule row grows a leading column, the iteration number (its int32 bits in a float), that lands on word 2: the
+# copy / adalog_brecq_prepare launch that refreshes the schedule before a replay advances the iteration too.
+class _ScheduleTable:
+    """The schedule's device words behind the one-element views ``b``, ``gate``, ``lr`` (and QDrop's ``drop_state``), and their rows."""
+
+    def __init__(self, loss_func, iters, lr, device, seed=None, ahead=256):
+        self.loss_func, self.drop_state = loss_func, None
+        self.twin_opt = torch.optim.SGD([torch.nn.Parameter(torch.zeros(1))], lr=lr)
+        self.twin = torch.optim.lr_scheduler.CosineAnnealingLR(self.twin_opt, T_max=iters, eta_min=0.)
+        if seed is None:
+            self.words = torch.zeros(3, dtype=torch.float32, device=device)
+        else:
+            words = torch.zeros(6, dtype=torch.int32, device=device)
+            words[:3] = _drop.make_state(seed, 0, device)
+            self.drop_state, self.words = words[0:3], words.view(torch.float32)[2:6]
+        self.b, self.gate, self.lr = self.words[-3:].split(1)  # (the words a row is copied to: [iteration,] b, gate, lr)
+        self.lr.fill_(lr)
+        self.rows = _RowsAhead(self.make_rows, iters, device, ahead)
+
+    def make_rows(self, it, cnt):
+        rows = []
+        for k in range(cnt):
+            count = it + k + 1                               # LossFunction.advance(): the counter of that iteration
+            active = not (count < self.loss_func.loss_start or self.loss_func.round_loss == 'none')
+            rows.append([float(self.loss_func.temp_decay(count)) if active else 0.0, 1.0 if active else 0.0,
+                         float(self.twin_opt.param_groups[0]['lr'])])
+            self.twin.step()                                 # (block_recon.py:124-125: the scheduler steps after the optimiser)
+        host = torch.tensor(rows, dtype=torch.float32)
+        if self.drop_state is not None:                      # QDrop: the iteration number in front (bit pattern, see above)
+            host = torch.cat([torch.arange(it, it + cnt, dtype=torch.int32).view(torch.float32).unsqueeze(1), host], dim=1)
+        return host
+
+    def row(self, it, copy=True):
+        # row ``it`` (b of iteration it, its gate, the learning rate it steps with) -> the device words; returned (and not copied)
+        # with ``copy=False``: the replay path hands it to adalog_brecq_prepare together with the mini-batch gather
+        row = self.rows.row(it)
+        if copy:
+            self.words.copy_(row)
+        return row
+
+
+class _Optimisers:
+    """Both Adam optimisers of a block (alpha; the activation scales: none without ``quant_act``) and the scales' cosine schedule."""
+
+    def __init__(self, w_params, a_params, plan, a_lr, iters, ws):
+        self.w_params, self.a_params, self.params, self.ws = w_params, a_params, w_params + a_params, ws
+        adam = HipAdam if plan.hip_adam else functools.partial(torch.optim.Adam, **plan.optim_kw)
+        self.w = adam(w_params)
+        self.a = adam(a_params, lr=a_lr) if a_params else None
+        # (in table mode the _ScheduleTable's learning-rate word carries the schedule)
+        self.a_scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(self.a, T_max=iters, eta_min=0.) \
+            if a_params and not plan.table_mode else None
+
+    def zero_grad(self):
+        for prm in self.params:
+            prm.grad = None
+
+    def step(self):
+        if self.ws > 1:                                      # data-parallel: mean of the per-rank batch-mean gradients
+            parallel.all_reduce_mean_bucket([prm.grad for prm in self.params if prm.grad is not None])
+        self.w.step()
+        if self.a is not None:
+            self.a.step()
+
+    def schedule(self):
+        if self.a_scheduler is not None:
+            self.a_scheduler.step()
+
+
+def _alpha_collector(block, loss_func, w_optimizer, w_params):
+    """The one-launch alpha update of a captured iteration (quantizers/adaround.py AlphaCollector), or None when it does not
+    apply: HipAdam over exactly the block's soft-target AdaRound alphas (<= 16, fp32, contiguous), ADALOG_BRECQ_ALPHA_STEP != 0."""
+    be = backend.get()
+    if os.environ.get("ADALOG_BRECQ_ALPHA_STEP", "1") == "0" or not isinstance(w_optimizer, HipAdam) \
+            or not hasattr(be, "alpha_step_multi") or loss_func.round_loss != 'relaxation':
+        return None
+    qs = [m.w_quantizer for m in adaround_modules(block)]
+    if not (1 <= len(qs) <= 16) or len(w_optimizer.param_groups) != 1:
+        return None
+    if {id(q_.alpha) for q_ in qs} != {id(p_) for p_ in w_params} or len(w_params) != len(qs):
+        return None
+    if not all(q_.soft_targets and q_.round_mode == 'learned_hard_sigmoid' and not q_.sym and q_.alpha.is_cuda
+               and q_.alpha.dtype == torch.float32 and q_.alpha.is_contiguous() for q_ in qs):
+        return None
+    group = w_optimizer.param_groups[0]
+    counter = w_optimizer.step_counter(group['params'])  # all alphas in one chunk, in the optimiser's order (<= 16 tensors)
+    if counter is None or any(not w_optimizer.state[q_.alpha] for q_ in qs):
+        return None                                      # the eager warm-up iterations create the Adam state
+    return adaround_mod.AlphaCollector(qs, lambda p_: w_optimizer.state[p_], counter, group['lr'],
+                                       group['betas'], group['eps'])
+
+
+# One iteration -- forward, both loss terms, backward and, with ``full_graph``, the optimiser steps -- captured in a HIP graph over
+# static batch buffers.  ``b`` / ``gate``: the one-element device tensors the regulariser reads (the schedule table's, or two of
+# its own that the loop fills).
+class _CapturedIteration:
+    """The captured iteration of one reconstruct_single_block call: its static buffers, graph, collector and loss tensors."""
+
+    def __init__(self, block, loss_func, opt, table, full_graph, device, undo):
+        from .. import _lib                              # the ticket counters are allocated (with a device sync) before any capture
+        _lib.check(_lib.load().adalog_brecq_init(), "adalog_brecq_init")
+        self.block, self.loss_func, self.opt, self.table = block, loss_func, opt, table
+        self.full_graph, self.device = full_graph, device
+        self.b, self.gate = (table.b, table.gate) if table is not None else (None, None)
+        self.static_inp = self.static_out = self.graph = self.collector = self.rec = self.rnd = None
+        self.captured_now = False
+        undo.callback(setattr, self, 'graph', None)
+
+    def load_batch(self, idx, sched_row):
+        # the mini-batch ``idx`` -> the static buffers (allocated by the first call, the capture iteration's) and, before a replay,
+        # ``sched_row`` -> the table's device words: one adalog_brecq_prepare launch where it applies
+        block = self.block
+        if self.static_inp is None:
+            self.static_inp, self.static_out = block.raw_input[idx].to(self.device).clone(), block.raw_out[idx].to(self.device).clone()
+            if self.b is None:
+                self.b, self.gate = (torch.zeros(1, dtype=torch.float32, device=self.device) for _ in range(2))
+            return
+        be = backend.get()
+        words = self.table.words if self.table is not None else None
+        resident = block.raw_input.device == self.static_inp.device
+        if PREPARE_FUSED and hasattr(be, "brecq_prepare") and resident \
+                and be.brecq_prepare(block.raw_input, block.raw_out, idx, self.static_inp, self.static_out, sched_row, words):
+            return
+        if sched_row is not None:                            # (gather + gather + schedule copy as separate launches)
+            words.copy_(sched_row)
+        if resident:
+            torch.index_select(block.raw_input, 0, idx, out=self.static_inp)
+            torch.index_select(block.raw_out, 0, idx, out=self.static_out)
+        else:                                                # keep_gpu=False: block data lives on the host
+            self.static_inp.copy_(block.raw_input[idx])
+            self.static_out.copy_(block.raw_out[idx])
+
+    def capture(self):
+        self.opt.zero_grad()
+        torch.cuda.synchronize()
+        self.graph = torch.cuda.CUDAGraph()
+        train_mm.reset_offers()
+        self.collector = _alpha_collector(self.block, self.loss_func, self.opt.w, self.opt.w_params) if self.full_graph else None
+        with torch.cuda.graph(self.graph):
+            adaround_mod.COLLECT = self.collector
+            try:
+                self.rec = self.loss_func.rec_term(self.block(self.static_inp), self.static_out)
+                self.rnd = self.loss_func.round_sum(self.b, gate=self.gate)
+                (self.rec + self.rnd).backward()
+            finally:
+                adaround_mod.COLLECT = None
+            if self.full_graph:
+                if self.collector is not None:
+                    self.collector.flush()                   # d/d alpha of every layer and its Adam step: one launch
+                self.opt.step()                              # (opt.w finds no gradient on the collected alphas)
+        self.captured_now = True
+
+    def replay(self):
+        self.graph.replay()                                  # grads are overwritten, not accumulated (none existed at capture)
+        if self.full_graph:
+            # the replay stepped the optimisers' DEVICE counters; keep HipAdam's host mirror (which decides chunk membership and
+            # seeds new counters) in step: every trained tensor, except that in the capture iteration step() itself already
+            # counted the tensors it saw a gradient on (all but the collected alphas)
+            for o, prms in ((self.opt.w, self.opt.w_params), (self.opt.a, self.opt.a_params)):
+                if isinstance(o, HipAdam) and (not self.captured_now or (self.collector is not None and o is self.opt.w)):
+                    o.note_external_steps(prms)
+        self.captured_now = False
+
+
+@contextlib.contextmanager
+def _training_scope(rec, name, block, device, quant_act, drop_prob, fast_mm, new_table):
+    """Everything a reconstruct_single_block call changes on the block and in the process, undone on every way out."""
+    # Yields the trained tensors, the QDrop quantisers and their device state, the schedule table (``new_table(seed or None)`` makes
+    # it in table mode; None otherwise) and ``undo``: what only the iterations need -- frozen parameters, the tf32 switch, QDrop's
+    # fields, the graph -- goes back when ``undo.close()`` is called (the report after the iterations quantises every element) and
+    # on every way out; finish_block then leaves the block as after a finished call (minus, after an exception, the training).
+    global _DROP_IGNORED_LOGGED
+    undo = contextlib.ExitStack()
+    try:
+        rec.wrap_quantizers_in_net(block, name)
+        rec.set_block_mode(block, 'quant_forward')
+        for _, module in block.named_modules():
+            if hasattr(module, 'training_mode'):
+                module.init_training()
+        w_params, a_params = _trained(block, quant_act)
+        drop_qs, drop_state, seed = [], None, None
+        if quant_act:
+            a_qs = _drop.activation_quantizers(block)
+            for q_ in a_qs:
+                undo.callback(setattr, q_, 'drop_prob', q_.drop_prob)
+                if float(drop_prob) < 1.0:
+                    q_.drop_prob = float(drop_prob)
+            if any(q_.drop_prob < 1.0 for q_ in a_qs):
+                drop_qs = a_qs                               # (the position in a_qs is the quantiser's Philox stream)
+        else:
+            for _, module in block.named_modules():
+                if hasattr(module, 'mode') and isinstance(module, (MinMaxQuantLinear, MinMaxQuantConv2d, MinMaxQuantMatMul)):
+                    module.mode = 'raw' if isinstance(module, MinMaxQuantMatMul) else 'debug_only_quant_weight'
+            if (float(drop_prob) < 1.0 or any(q_.drop_prob < 1.0 for q_ in _drop.activation_quantizers(block))) \
+                    and not _DROP_IGNORED_LOGGED:
+                logging.info('drop_prob={} is ignored: activation quantisers are off (quant_act=False)'.format(drop_prob))
+                _DROP_IGNORED_LOGGED = True
+        if drop_qs:
+            names = list(getattr(rec, 'blocks', {}).keys())
+            seed = drop_seed(names.index(name) if name in names else 0, parallel.rank())
+        table = new_table(seed) if new_table is not None else None
+        if drop_qs:
+            drop_state = table.drop_state if table is not None else _drop.make_state(seed, 0, device)
+            for i, q_ in enumerate(drop_qs):
+                undo.callback(setattr, q_, 'drop_state', None)
+                if q_.drop_prob < 1.0:
+                    q_.attach_drop_state(drop_state, i)
+        # Only alpha and the activation scales are optimised (block_recon.py:97-108).  The reference leaves every other
+        # parameter of the block with requires_grad=True and autograd fills their .grad each iteration (bias sums,
+        # LayerNorm gamma/beta, ~40 accumulations) although nothing reads them; freezing them for the duration of the
+        # reconstruction changes no trained value and drops those kernels.
+        trained = {id(prm) for prm in w_params + a_params}
+        for prm in block.parameters():
+            if prm.requires_grad and id(prm) not in trained:
+                undo.callback(prm.requires_grad_, True)
+                prm.requires_grad_(False)
+        undo.callback(setattr, torch.backends.cuda.matmul, 'allow_tf32', torch.backends.cuda.matmul.allow_tf32)
+        if fast_mm:
+            torch.backends.cuda.matmul.allow_tf32 = True
+        yield types.SimpleNamespace(w_params=w_params, a_params=a_params, drop_qs=drop_qs, drop_state=drop_state, table=table, undo=undo)
+    finally:
+        undo.close()
+        finish_block(block)
+
+
+def _fixed_rec_loss(block, loss_func, drop_qs, device, n_eval):
+    """the block's reconstruction loss as it stands (soft rounding targets, training-form quantisers: the forward values of an
+    iteration) on a FIXED set of its optimisation images -- what the iterations are meant to lower (block_recon.py:189-198)"""
+    train_mm.reset_offers()
+    with contextlib.ExitStack() as held:
+        for q_ in drop_qs:                               # QDrop: the report quantises every element
+            held.callback(setattr, q_, 'drop_state', q_.drop_state)
+            q_.drop_state = None
+        with torch.enable_grad():                        # the iteration's own forward path (contractions on csrc/brecq_gemm.hip)
+            pred = block(block.raw_input[:n_eval].to(device)).detach()
+    with torch.no_grad():
+        return float(loss_func.rec_term(pred, block.raw_out[:n_eval].to(device)))
+
+
 class BlockReconstructor(QuantCalibrator):
     drop_prob = None                   # QDrop keep probability of a reconstruct_model() call that gives none (quant_qdrop.py sets it)
 
@@ -110,30 +450,6 @@ class BlockReconstructor(QuantCalibrator):
     def _prepare_module_data_init(module):
         module.raw_input = module.tmp_input = None
         module.raw_out = module.tmp_out = None
-
-    @staticmethod
-    def _alpha_collector(block, loss_func, w_optimizer, w_params):
-        """The one-launch alpha update of a captured iteration (quantizers/adaround.py AlphaCollector), or None when it does not
-        apply: HipAdam over exactly the block's soft-target AdaRound alphas (<= 16, fp32, contiguous), ADALOG_BRECQ_ALPHA_STEP != 0."""
-        be = backend.get()
-        if os.environ.get("ADALOG_BRECQ_ALPHA_STEP", "1") == "0" or not isinstance(w_optimizer, HipAdam) \
-                or not hasattr(be, "alpha_step_multi") or loss_func.round_loss != 'relaxation':
-            return None
-        qs = [m.w_quantizer for _, m in block.named_modules()
-              if hasattr(m, 'w_quantizer') and isinstance(m.w_quantizer, AdaRoundQuantizer)]
-        if not (1 <= len(qs) <= 16) or len(w_optimizer.param_groups) != 1:
-            return None
-        if {id(q_.alpha) for q_ in qs} != {id(p_) for p_ in w_params} or len(w_params) != len(qs):
-            return None
-        if not all(q_.soft_targets and q_.round_mode == 'learned_hard_sigmoid' and not q_.sym and q_.alpha.is_cuda
-                   and q_.alpha.dtype == torch.float32 and q_.alpha.is_contiguous() for q_ in qs):
-            return None
-        group = w_optimizer.param_groups[0]
-        counter = w_optimizer.step_counter(group['params'])  # all alphas in one chunk, in the optimiser's order (<= 16 tensors)
-        if counter is None or any(not w_optimizer.state[q_.alpha] for q_ in qs):
-            return None                                      # the eager warm-up iterations create the Adam state
-        return adaround_mod.AlphaCollector(qs, lambda p_: w_optimizer.state[p_], counter, group['lr'],
-                                           group['betas'], group['eps'])
 
     def set_block_mode(self, block, mode='raw'):
         for _, module in block.named_modules():
@@ -178,324 +494,69 @@ class BlockReconstructor(QuantCalibrator):
         """``drop_prob`` < 1 (QDrop, quantizers/_drop.py; with ``quant_act`` only): every activation quantiser of the block keeps a
         fake-quantised element with that probability during the iterations.  Quantisers whose ``drop_prob`` the caller set below 1
         drop as well.  1.0 (and no such quantiser): the code path of a call without the argument."""
-        self.wrap_quantizers_in_net(block, name)
-        self.set_block_mode(block, 'quant_forward')
-        for _, module in block.named_modules():
-            if hasattr(module, 'training_mode'):
-                module.init_training()
-        w_params, a_params = [], []
-        for _, module in block.named_modules():
-            if hasattr(module, 'mode'):
-                if isinstance(module, (MinMaxQuantLinear, MinMaxQuantConv2d)):
-                    w_params += [module.w_quantizer.alpha]
-                    if quant_act:
-                        a_params += [module.a_quantizer.scale]
-                    else:
-                        module.mode = 'debug_only_quant_weight'
-                elif isinstance(module, MinMaxQuantMatMul):
-                    if quant_act:
-                        a_params += [module.A_quantizer.scale, module.B_quantizer.scale]
-                    else:
-                        module.mode = 'raw'
-        drop_qs, drop_prev = [], []
-        if quant_act:
-            a_qs = _drop.activation_quantizers(block)
-            drop_prev = [(q_, q_.drop_prob) for q_ in a_qs]
-            if float(drop_prob) < 1.0:
-                for q_ in a_qs:
-                    q_.drop_prob = float(drop_prob)
-            if any(q_.drop_prob < 1.0 for q_ in a_qs):
-                drop_qs = a_qs                               # (the position in a_qs is the quantiser's Philox stream)
-        elif float(drop_prob) < 1.0 or any(q_.drop_prob < 1.0 for q_ in _drop.activation_quantizers(block)):
-            global _DROP_IGNORED_LOGGED
-            if not _DROP_IGNORED_LOGGED:
-                logging.info('drop_prob={} is ignored: activation quantisers are off (quant_act=False)'.format(drop_prob))
-                _DROP_IGNORED_LOGGED = True
-        ws = parallel.world_size()
-        local_bs = max(1, batch_size // ws)
-        n_local = block.raw_input.size(0)
-        # One iteration is ~85 kernel launches (1.7 ms of GPU time on MI355X for a deit_small block, 58 % of it the fp32
-        # GEMMs), issued eagerly in 2.0 ms.  The iteration is captured once in a HIP graph over static batch buffers and
-        # replayed: forward, reconstruction loss, rounding regulariser (its exponent b and on/off weight live in device
-        # scalars), backward and -- single process -- both Adam steps (capturable).  20 000 iterations of the block:
-        # 496 it/s eager, 568 it/s replayed, same reached error.  With several ranks the gradient all-reduce and the
-        # optimiser steps stay eager and the graph is opt-in (ADALOG_BRECQ_GRAPH=1); ADALOG_BRECQ_GRAPH=0 forces eager.
-        want_graph = os.environ.get("ADALOG_BRECQ_GRAPH", "1" if ws == 1 else "0") == "1"
-        use_graph = (torch.device(device).type == 'cuda' and want_graph and n_local >= local_bs and iters > 8)
-        full_graph = use_graph and ws == 1
-        if use_graph:
-            from .. import _lib                          # the ticket counters are allocated (with a device sync) before any capture
-            _lib.check(_lib.load().adalog_brecq_init(), "adalog_brecq_init")
-        okw = dict(capturable=True) if full_graph else {}
-        if torch.device(device).type == 'cuda':
-            okw['fused'] = True                          # one kernel per optimiser step instead of six foreach passes
-        # the optimiser steps: one hand-written launch per optimiser (HipAdam) on the HIP device; ADALOG_BRECQ_ADAM=torch (and the
-        # CPU tier by default) keeps torch.optim.Adam
-        hip_adam = os.environ.get("ADALOG_BRECQ_ADAM", "hip" if torch.device(device).type == 'cuda' else "torch") == "hip"
-        a_lr = torch.tensor(lr, dtype=torch.float32, device=device) if full_graph else lr
-        # Captured iterations with HipAdam: what changes from one iteration to the next besides the mini-batch -- the
-        # regulariser's exponent b, its 0 / 1 warm-up gate and the cosine learning rate of the activation scales -- lives in ONE
-        # device triple the captured kernels read, refreshed by one 12-byte copy per iteration from a table uploaded 256 rows at
-        # a time (two fills and the scheduler's tensor arithmetic, ~7 launches, before).  The rows are computed on the host in
-        # python floats by the reference's own objects (LinearTempDecay, torch's CosineAnnealingLR on a float learning rate).
-        table_mode = full_graph and hip_adam
-        sched_dev = torch.zeros(3, dtype=torch.float32, device=device) if table_mode else None
-        # QDrop: the masks' key and the iteration number live in an int32 device triple {seed_lo, seed_hi, iteration} the quantisers'
-        # kernels read.  In table mode the triple and the schedule share ONE buffer -- words {seed_lo, seed_hi, iteration, b, gate, lr}
-        # -- and the schedule row grows a leading column, the iteration number (its int32 bits in a float), that lands on word 2: the
-        # copy / adalog_brecq_prepare launch that refreshes the schedule before a replay advances the iteration too.
-        drop_state, so = None, 0
-        if drop_qs:
-            names = list(getattr(self, 'blocks', {}).keys())
-            blk_index = names.index(name) if name in names else 0
-            drop_state = _drop.make_state(drop_seed(blk_index, parallel.rank()), 0, device)
-            if table_mode:
-                words = torch.zeros(6, dtype=torch.int32, device=device)
-                words[:3] = drop_state
-                drop_state, sched_dev, so = words[0:3], words.view(torch.float32)[2:6], 1
-            for i, q_ in enumerate(drop_qs):
-                if q_.drop_prob < 1.0:
-                    q_.attach_drop_state(drop_state, i)
-        if table_mode:
-            a_lr = sched_dev[2 + so:3 + so]
-            a_lr.fill_(lr)
-        if hip_adam:
-            w_optimizer = HipAdam(w_params)
-            a_optimizer = HipAdam(a_params, lr=a_lr) if len(a_params) != 0 else None
-        else:
-            w_optimizer = torch.optim.Adam(w_params, **okw)
-            a_optimizer = torch.optim.Adam(a_params, lr=a_lr, **okw) if len(a_params) != 0 else None
-        a_scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(a_optimizer, T_max=iters, eta_min=0.) \
-            if len(a_params) != 0 and not table_mode else None
-        twin_opt = twin = None
-        if table_mode:
-            twin_opt = torch.optim.SGD([torch.nn.Parameter(torch.zeros(1))], lr=lr)
-            twin_opt.step()
-            twin = torch.optim.lr_scheduler.CosineAnnealingLR(twin_opt, T_max=iters, eta_min=0.)
+        # whether the iterations end or one raises, the block is left as a finished call leaves it (_training_scope); only a call
+        # that ends releases the block's captured inputs and targets
+        device = torch.device(device)
+        ws, n_local = parallel.world_size(), block.raw_input.size(0)
+        plan = _plan(device, ws, n_local, batch_size, iters)
         loss_func = LossFunction(block, round_loss='relaxation', weight=weight, max_count=iters,
                                  rec_loss='mse' if 'head' not in name else 'kl_div', b_range=b_range, decay_start=0,
                                  warmup=warmup, p=p)
-        gen = torch.Generator().manual_seed(1234 + parallel.rank())
+        new_table = functools.partial(_ScheduleTable, loss_func, iters, lr, device) if plan.table_mode else None
         # test hooks (tests/golden/brecq_traj.npz replays the reference's own mini-batch sequence and compares the trained
         # values after given iterations): index_source(it, n, bs) -> LongTensor of bs indices; iter_hook(it) after iteration it
-        index_source = getattr(self, 'index_source', None)
-        iter_hook = getattr(self, 'iter_hook', None)
-        # Only alpha and the activation scales are optimised (block_recon.py:97-108).  The reference leaves every other
-        # parameter of the block with requires_grad=True and autograd fills their .grad each iteration (bias sums,
-        # LayerNorm gamma/beta, ~40 accumulations) although nothing reads them; freezing them for the duration of the
-        # reconstruction changes no trained value and drops those kernels.
-        trained = {id(prm) for prm in w_params + a_params}
-        frozen = [prm for prm in block.parameters() if prm.requires_grad and id(prm) not in trained]
-        for prm in frozen:
-            prm.requires_grad_(False)
-        # ADALOG_BRECQ_FAST_MM=1: the block's plain GEMMs (linear / bmm, forward and both backward products) use hipBLASLt's
-        # "fast fp32" mode (bf16 three-term split products, relative error 4e-6 against 4e-7).  Measured on a deit_small
-        # block it is worth 4 % of the iteration (some shapes get slower kernels), so the default stays plain fp32.
-        fast_mm = torch.device(device).type == 'cuda' and os.environ.get("ADALOG_BRECQ_FAST_MM", "0") == "1"
-        prev_tf32 = torch.backends.cuda.matmul.allow_tf32
-        if fast_mm:
-            torch.backends.cuda.matmul.allow_tf32 = True
-        graph, static_inp, static_out, static_rec, static_rnd = None, None, None, None, None
-        b_dev = rw_dev = None
-        captured_now, collector = False, None
-        params = w_params + a_params
-
-        def optim_steps():
-            w_optimizer.step()
-            if a_optimizer is not None:
-                a_optimizer.step()
-
-        def eager_step(cur_inp, cur_out):
-            train_mm.reset_offers()
-            for prm in params:
-                prm.grad = None
-            out_quant = block(cur_inp)
-            err = loss_func(out_quant, cur_out)
-            err.backward()
-            if ws > 1:                                   # data-parallel: mean of the per-rank batch-mean gradients
-                parallel.all_reduce_mean_bucket([prm.grad for prm in params if prm.grad is not None])
-            optim_steps()
-            if a_scheduler is not None:
-                a_scheduler.step()
-
-        # The mini-batch indices of the next IDX_AHEAD iterations are drawn together (the same randperm sequence) and uploaded
-        # in one non-blocking copy from pinned memory: a pageable host-to-device copy per iteration blocks the host until the
-        # previous iteration's kernels have drained, i.e. the GPU idles through the host's ~0.2 ms of per-iteration work.
-        IDX_AHEAD = 256
-        idx_dev = block.raw_input.device
-        idx_block, idx_base = None, 0
-
-        def next_indices(it):
-            nonlocal idx_block, idx_base
-            if idx_block is None or it >= idx_base + idx_block.shape[0]:
-                cnt = min(IDX_AHEAD, iters - it)
-                rows = [(index_source(it + k, n_local, local_bs) if index_source is not None
-                         else torch.randperm(n_local, generator=gen)[:local_bs]) for k in range(cnt)]
-                host = torch.stack(rows)
-                if idx_dev.type == 'cuda':
-                    host = host.pin_memory()
-                idx_block, idx_base = host.to(idx_dev, non_blocking=True), it
-            return idx_block[it - idx_base]
-
-        sched_block, sched_base = None, 0
-
-        def next_schedule(it, copy=True):
-            """Row `it` of the schedule table -> sched_dev (b of iteration it, its gate, the learning rate it steps with); returned (and
-            not copied) with ``copy=False``: the replay path hands it to adalog_brecq_prepare together with the mini-batch gather."""
-            nonlocal sched_block, sched_base
-            if sched_block is None or it >= sched_base + sched_block.shape[0]:
-                cnt = min(IDX_AHEAD, iters - it)
-                rows = []
-                for k in range(cnt):
-                    count = it + k + 1                       # LossFunction.advance(): the counter of that iteration
-                    active = not (count < loss_func.loss_start or loss_func.round_loss == 'none')
-                    rows.append([float(loss_func.temp_decay(count)) if active else 0.0, 1.0 if active else 0.0,
-                                 float(twin_opt.param_groups[0]['lr'])])
-                    twin.step()                              # (block_recon.py:124-125: the scheduler steps after the optimiser)
-                host = torch.tensor(rows, dtype=torch.float32)
-                if so:                                       # QDrop: the iteration number in front (bit pattern, see drop_state)
-                    host = torch.cat([torch.arange(it, it + cnt, dtype=torch.int32).view(torch.float32).unsqueeze(1), host], dim=1)
-                host = host.pin_memory()
-                sched_block, sched_base = host.to(device, non_blocking=True), it
-            if copy:
-                sched_dev.copy_(sched_block[it - sched_base])
-            return sched_block[it - sched_base]
-
-        def fixed_rec_loss():
-            """the block's reconstruction loss as it stands (soft rounding targets, training-form quantisers: the forward values of an
-            iteration) on a FIXED set of its optimisation images -- what the iterations are meant to lower (block_recon.py:189-198)"""
-            n_eval = min(n_local, 2 * local_bs)
-            train_mm.reset_offers()
-            held = [(q_, q_.drop_state) for q_ in drop_qs]   # QDrop: the report quantises every element
-            for q_ in drop_qs:
-                q_.drop_state = None
-            try:
-                with torch.enable_grad():                    # the iteration's own forward path (contractions on csrc/brecq_gemm.hip)
-                    pred = block(block.raw_input[:n_eval].to(device)).detach()
-            finally:
-                for q_, st_ in held:
-                    q_.drop_state = st_
-            with torch.no_grad():
-                return float(loss_func.rec_term(pred, block.raw_out[:n_eval].to(device)))
-
-        report = os.environ.get("ADALOG_BRECQ_REPORT", "1") != "0" and n_local > 0
-        rec_before = fixed_rec_loss() if report else None
-        try:
+        index_source, iter_hook = getattr(self, 'index_source', None), getattr(self, 'iter_hook', None)
+        gen = torch.Generator().manual_seed(1234 + parallel.rank())
+        indices = _RowsAhead(functools.partial(_index_rows, index_source, gen, n_local, plan.local_bs), iters, block.raw_input.device)
+        n_eval = min(n_local, 2 * plan.local_bs)
+        with _training_scope(self, name, block, device, quant_act, drop_prob, plan.fast_mm, new_table) as tr:
+            table = tr.table
+            a_lr = table.lr if table is not None else torch.tensor(lr, dtype=torch.float32, device=device) if plan.full_graph else lr
+            opt = _Optimisers(tr.w_params, tr.a_params, plan, a_lr, iters, ws)
+            cap = _CapturedIteration(block, loss_func, opt, table, plan.full_graph, device, tr.undo) if plan.use_graph else None
+            rec_before = _fixed_rec_loss(block, loss_func, tr.drop_qs, device, n_eval) if plan.report else None
             for it in range(iters):
-                idx = next_indices(it)
-                replaying = use_graph and graph is not None and it >= 3
+                idx = indices.row(it)
                 sched_row = None
-                if table_mode:
-                    sched_row = next_schedule(it, copy=not replaying)
-                elif drop_state is not None:
-                    drop_state[2:3].fill_(it)                # (table mode: the schedule row carries it)
-                if not use_graph or it < 3:                  # eager (and the warm-up iterations before the capture)
-                    eager_step(block.raw_input[idx].to(device), block.raw_out[idx].to(device))
-                    if iter_hook is not None:
-                        iter_hook(it + 1, loss_func)
-                    continue
-                if graph is None:
-                    static_inp, static_out = block.raw_input[idx].to(device).clone(), block.raw_out[idx].to(device).clone()
-                    if table_mode:
-                        b_dev, rw_dev = sched_dev[so:so + 1], sched_dev[so + 1:so + 2]
-                    else:
-                        b_dev = torch.zeros(1, dtype=torch.float32, device=device)
-                        rw_dev = torch.zeros(1, dtype=torch.float32, device=device)
-                else:
-                    be_ = backend.get() if device.type == 'cuda' else None
-                    one = (PREPARE_FUSED and be_ is not None and hasattr(be_, "brecq_prepare")
-                           and block.raw_input.device == static_inp.device
-                           and be_.brecq_prepare(block.raw_input, block.raw_out, idx, static_inp, static_out, sched_row, sched_dev))
-                    if not one:                                  # (gather + gather + schedule copy as separate launches)
-                        if sched_row is not None:
-                            sched_dev.copy_(sched_row)
-                        if block.raw_input.device == static_inp.device:
-                            torch.index_select(block.raw_input, 0, idx, out=static_inp)
-                            torch.index_select(block.raw_out, 0, idx, out=static_out)
-                        else:                                    # keep_gpu=False: block data lives on the host
-                            static_inp.copy_(block.raw_input[idx])
-                            static_out.copy_(block.raw_out[idx])
-                active = loss_func.advance()                 # iteration counter, b of this iteration
-                if not table_mode:
-                    b_dev.fill_(float(loss_func.b))
-                    rw_dev.fill_(1.0 if active else 0.0)
-                if graph is None:
-                    for prm in params:
-                        prm.grad = None
-                    torch.cuda.synchronize()
-                    graph = torch.cuda.CUDAGraph()
+                if table is not None:                        # (copied by load_batch's launch before a replay)
+                    sched_row = table.row(it, copy=cap.graph is None)
+                elif tr.drop_state is not None:
+                    tr.drop_state[2:3].fill_(it)             # (table mode: the schedule row carries it)
+                if cap is None or it < 3:                    # eager (and the warm-up iterations before the capture)
+                    cur_inp, cur_out = block.raw_input[idx].to(device), block.raw_out[idx].to(device)
                     train_mm.reset_offers()
-                    collector = self._alpha_collector(block, loss_func, w_optimizer, w_params) if full_graph else None
-                    with torch.cuda.graph(graph):
-                        adaround_mod.COLLECT = collector
-                        try:
-                            static_rec = loss_func.rec_term(block(static_inp), static_out)
-                            static_rnd = loss_func.round_sum(b_dev, gate=rw_dev)
-                            (static_rec + static_rnd).backward()
-                        finally:
-                            adaround_mod.COLLECT = None
-                        if full_graph:
-                            if collector is not None:
-                                collector.flush()            # d/d alpha of every layer and its Adam step: one launch
-                            optim_steps()                    # (w_optimizer finds no gradient on the collected alphas)
-                    captured_now = True
-                graph.replay()                               # grads are overwritten, not accumulated (none existed at capture)
-                if full_graph:
-                    # the replay stepped the optimisers' DEVICE counters; keep HipAdam's host mirror (which decides chunk
-                    # membership and seeds new counters) in step: every trained tensor, except that in the capture iteration
-                    # step() itself already counted the tensors it saw a gradient on (all but the collected alphas)
-                    for opt, prms in ((w_optimizer, w_params), (a_optimizer, a_params)):
-                        if isinstance(opt, HipAdam):
-                            if not captured_now:
-                                opt.note_external_steps(prms)
-                            elif collector is not None and opt is w_optimizer:
-                                opt.note_external_steps(prms)
-                    captured_now = False
-                if not full_graph:
-                    parallel.all_reduce_mean_bucket([prm.grad for prm in params if prm.grad is not None])
-                    optim_steps()
-                if a_scheduler is not None:
-                    a_scheduler.step()
-                loss_func.cur = (static_rec.detach(), static_rnd.detach())
-                loss_func.log(static_rec, static_rnd)
+                    opt.zero_grad()
+                    loss_func(block(cur_inp), cur_out).backward()
+                    opt.step()
+                    opt.schedule()
+                else:
+                    cap.load_batch(idx, sched_row)
+                    active = loss_func.advance()             # iteration counter, b of this iteration
+                    if table is None:
+                        cap.b.fill_(float(loss_func.b))
+                        cap.gate.fill_(1.0 if active else 0.0)
+                    if cap.graph is None:
+                        cap.capture()
+                    cap.replay()
+                    if not plan.full_graph:                  # (several ranks: the all-reduce and the steps stay eager)
+                        opt.step()
+                    opt.schedule()
+                    loss_func.cur = (cap.rec.detach(), cap.rnd.detach())
+                    loss_func.log(cap.rec, cap.rnd)
                 if iter_hook is not None:
                     iter_hook(it + 1, loss_func)
-        finally:                                         # (also when an iteration raises: leave the block as it was found)
-            graph = None
-            torch.backends.cuda.matmul.allow_tf32 = prev_tf32
-            for prm in frozen:
-                prm.requires_grad_(True)
-            for q_ in drop_qs:                               # the iterations are over: the report below quantises every element
-                q_.drop_state = None
-            for q_, prev in drop_prev:
-                q_.drop_prob = prev
-        if report:
-            rec_after = fixed_rec_loss()
-            self.__dict__.setdefault('rec_report', {})[name] = (rec_before, rec_after)
-            logging.info('{}: reconstruction loss on its first {} images {:.6g} -> {:.6g} after {} iterations'.format(
-                name, min(n_local, 2 * local_bs), rec_before, rec_after, iters))
-        for _, module in block.named_modules():
-            if hasattr(module, 'w_quantizer'):
-                module.w_quantizer.soft_targets = False
-            if hasattr(module, 'mode'):
-                module.mode = 'raw'
-            if hasattr(module, 'training_mode'):
-                module.end_training()
+            tr.undo.close()
+            if plan.report:
+                rec_after = _fixed_rec_loss(block, loss_func, tr.drop_qs, device, n_eval)
+                self.__dict__.setdefault('rec_report', {})[name] = (rec_before, rec_after)
+                logging.info('{}: reconstruction loss on its first {} images {:.6g} -> {:.6g} after {} iterations'.format(
+                    name, n_eval, rec_before, rec_after, iters))
         del block.raw_input, block.raw_out
         return loss_func
 
     def _trained_tensors(self, block, quant_act):
-        """What a block's reconstruction trains (block_recon.py:97-108), in named_modules() order."""
-        out = []
-        for _, module in block.named_modules():
-            if hasattr(module, 'mode'):
-                if isinstance(module, (MinMaxQuantLinear, MinMaxQuantConv2d)):
-                    out.append(module.w_quantizer.alpha)
-                    if quant_act:
-                        out.append(module.a_quantizer.scale)
-                elif isinstance(module, MinMaxQuantMatMul) and quant_act:
-                    out += [module.A_quantizer.scale, module.B_quantizer.scale]
-        return out
+        """What a block's reconstruction trains, module by module in named_modules() order (the order of the result broadcast)."""
+        return [t for w, a in _trained_by_module(block, quant_act) for t in w + a]
 
     def _reconstruct_blocks_parallel(self, device, quant_act, keep_gpu, iters, drop_prob=1.0):
         """Block-parallel BRECQ over the ranks.  A block's inputs AND targets come from the FP model (block_recon.py:62-82), so
@@ -550,19 +611,15 @@ class BlockReconstructor(QuantCalibrator):
                 del mine, gin, gout
                 with parallel.solo():
                     self.reconstruct_single_block(name, block, device, quant_act=quant_act, iters=iters, drop_prob=drop_prob)
-            # the ranks meet here once per round: a wait is at most one block's training (the process group's timeout -- 
+            # the ranks meet here once per round: a wait is at most one block's training (the process group's timeout --
             # ADALOG_DIST_TIMEOUT_MIN, default 120 -- is what bounds it, not the library's 10 minutes)
             parallel.barrier()
         for name in names:                                   # results from their owners
             block = self.blocks[name]
             for t in self._trained_tensors(block, quant_act):
                 parallel.broadcast(t.data, src=owner[name])
-            if owner[name] != rk:                            # the state reconstruct_single_block leaves behind
-                for _, module in block.named_modules():
-                    if hasattr(module, 'w_quantizer'):
-                        module.w_quantizer.soft_targets = False
-                    if hasattr(module, 'mode'):
-                        module.mode = 'raw'
+            if owner[name] != rk:
+                finish_block(block, end_training=False)
 
     @staticmethod
     def _block_cost(block, shard_input):
@@ -590,9 +647,7 @@ class BlockReconstructor(QuantCalibrator):
             for q_ in _drop.activation_quantizers(self.model):
                 q_.drop_prob = float(drop_prob)
         drop_prob = 1.0                                      # (the quantisers carry it from here on)
-        for _, module in self.model.named_modules():
-            if hasattr(module, 'mode'):
-                module.mode = 'raw'
+        self.set_block_mode(self.model, 'raw')
         self.dp_mode = 'single'
         if parallel.world_size() > 1 and os.environ.get("ADALOG_BRECQ_DP", "block") != "batch":
             self.dp_mode = 'block'
@@ -605,13 +660,11 @@ class BlockReconstructor(QuantCalibrator):
                 logging.info('reconstructing {} ...'.format(name))
                 self.init_block_raw_data(block, full_block, name, device, keep_gpu=keep_gpu)
                 self.reconstruct_single_block(name, block, device, quant_act=quant_act, iters=iters, drop_prob=drop_prob)
-        for _, module in self.model.named_modules():
-            if hasattr(module, 'mode'):
-                module.mode = 'quant_forward'
-            if hasattr(module, 'w_quantizer') and isinstance(module.w_quantizer, AdaRoundQuantizer):
-                module.weight.data.copy_(module.w_quantizer.get_hard_value(module.weight.data))
-                del module.w_quantizer.alpha
-                module.w_quantizer.round_mode = "nearest"
+        self.set_block_mode(self.model, 'quant_forward')
+        for module in adaround_modules(self.model):          # commit the hard rounding
+            module.weight.data.copy_(module.w_quantizer.get_hard_value(module.weight.data))
+            del module.w_quantizer.alpha
+            module.w_quantizer.round_mode = "nearest"
 
 
 class _RecLossFn(torch.autograd.Function):
@@ -710,14 +763,12 @@ class LossFunction:
     def round_sum(self, b, gate=None):
         """weight * sum over the block's AdaRound quantisers of sum(1 - |2h-1|^b); b: float or one-element device tensor;
         gate: optional one-element device tensor multiplied in (captured iterations: 0 during the warm-up, then 1)."""
-        alphas = [module.w_quantizer.alpha for _, module in self.block.named_modules()
-                  if hasattr(module, 'w_quantizer') and isinstance(module.w_quantizer, AdaRoundQuantizer)]
-        if 1 <= len(alphas) <= 16 and all(a.dtype == torch.float32 for a in alphas):
-            return _RoundLossAllFn.apply(b, float(self.weight), gate, *alphas)
+        qs = [module.w_quantizer for module in adaround_modules(self.block)]
+        if 1 <= len(qs) <= 16 and all(q_.alpha.dtype == torch.float32 for q_ in qs):
+            return _RoundLossAllFn.apply(b, float(self.weight), gate, *[q_.alpha for q_ in qs])
         round_loss = 0
-        for _, module in self.block.named_modules():
-            if hasattr(module, 'w_quantizer') and isinstance(module.w_quantizer, AdaRoundQuantizer):
-                round_loss = round_loss + self.weight * module.w_quantizer.round_loss(b)
+        for q_ in qs:
+            round_loss = round_loss + self.weight * q_.round_loss(b)
         return round_loss if gate is None else (round_loss * gate).sum()
 
     def round_term(self):
