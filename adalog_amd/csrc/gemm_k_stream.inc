@@ -22,6 +22,39 @@ constexpr int BK3 = 64;
 #define STREAM_DMA(rsrc, dst, voff, soff) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (las_ptr)(dst), 16, voff, soff, 0, 0)
 #endif
 #define STREAM_DMA4(rsrc, dst, voff) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (las_ptr)(dst), 4, (int)(voff), 0, 0, 0)
+// tools/lab/stream_mx_lab.hip: timing-only ablations of the MX main loop (profiles/stream_mx_ablation.txt).  Each takes one part out
+// and leaves the rest as shipped; the scores are wrong with any of them, and none is ever defined for the library.
+//   GEMM_LAB_NO_MFMA        the MFMAs (their operands are still read and converted)
+//   GEMM_LAB_MX_NO_CVT      the fp8 -> bf16 conversions (the raw dwords feed the MFMA)
+//   GEMM_LAB_MX_NO_AREAD    the A-fragment reads (a register stands in)
+//   GEMM_LAB_MX_NO_BREAD    the B-fragment reads
+//   GEMM_LAB_NO_BARRIER     the per-step s_barrier (the counted vmcnt stays)
+//   GEMM_LAB_MX_BRANCHY     (not an ablation: same scores) the DMA requests of a step behind wave-uniform branches, as before the wave
+//                           index was masked -- the form the table's "parent" rows were measured on
+#if defined(GEMM_LAB_NO_MFMA)
+#define STREAM_MX_MMA(FIRST_, a, b, c)                                                                            \
+    do {                                                                                                          \
+        if (FIRST_) { _Pragma("unroll") for (int r_ = 0; r_ < 16; ++r_) (c)[r_] = 0; }                            \
+        asm volatile("" :: "v"((a).x), "v"((a).y), "v"((a).z), "v"((a).w), "v"((b).x), "v"((b).y), "v"((b).z), "v"((b).w)); \
+    } while (0)
+#else
+#define STREAM_MX_MMA(FIRST_, a, b, c) do { if (FIRST_) (c) = mma0<1>((a), (b)); else mma<1>((a), (b), (c)); } while (0)
+#endif
+#if defined(GEMM_LAB_MX_NO_CVT)
+#define STREAM_MX_CVT(w0, w1) make_uint4((w0), (w0), (w1), (w1))
+#else
+#define STREAM_MX_CVT(w0, w1) make_uint4(fp8x2_bf16((w0), false), fp8x2_bf16((w0), true), fp8x2_bf16((w1), false), fp8x2_bf16((w1), true))
+#endif
+#if defined(GEMM_LAB_MX_NO_AREAD)   // (the reads in front of it lose their only use and are dropped)
+#define STREAM_MX_LAB_A(arr) do { _Pragma("unroll") for (int i_ = 0; i_ < RI; ++i_) (arr)[i_] = lab_frag; } while (0)
+#else
+#define STREAM_MX_LAB_A(arr) do { } while (0)
+#endif
+#if defined(GEMM_LAB_MX_NO_BREAD)
+#define STREAM_MX_LAB_B(b0, b1) do { _Pragma("unroll") for (int j_ = 0; j_ < CJ; ++j_) { (b0)[j_] = lab_frag; (b1)[j_] = lab_frag; } } while (0)
+#else
+#define STREAM_MX_LAB_B(b0, b1) do { } while (0)
+#endif
 typedef float v2f __attribute__((ext_vector_type(2)));
 // One fp32 fma as ONE VALU instruction.  Measured (tools/lab/pair_probe): packed fp32 math (v_pk_fma_f32, v_pk_mul_f32,
 // v_pk_add_f32) does not issue while the SIMD's other wave has MFMAs in flight -- a packed epilogue serialises with the
@@ -89,6 +122,19 @@ __global__ __launch_bounds__(64 * NW, (NS == 3 && !MX) ? (NW == 8 ? 4 : 2) : 1) 
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = w / (NW / 2), wc = w % (NW / 2);
+    // Owner index of the DMA requests.  MX: masked to 0 .. NW - 1 (which it is), so that whether request w + q * NW of a step reads A or
+    // B rows is a compile-time fact.  The wave-uniform branches that decided it at run time cut every K-step into a dozen basic blocks,
+    // and no fragment read or conversion could be scheduled across them: each sub-step's ds_reads sat right in front of the MFMAs
+    // that consume them (profiles/stream_mx_ablation.txt: 0.65 -> 0.60 ms per fc2 launch with the K-step in one block).
+#if defined(GEMM_LAB_MX_BRANCHY)
+    const int wq = w;
+#else
+    const int wq = MX ? (w & (NW - 1)) : w;
+#endif
+#if defined(GEMM_LAB_MX_NO_AREAD) || defined(GEMM_LAB_MX_NO_BREAD)
+    uint4 lab_frag = make_uint4(lane, lane, lane, lane);
+    asm volatile("" : "+v"(lab_frag.x), "+v"(lab_frag.y), "+v"(lab_frag.z), "+v"(lab_frag.w));
+#endif
     const int frow = lane & 31, fkg = lane >> 5;
     const int arow = wr * (BM3 / 2) + frow, brow = wc * WCOLS + frow;
 
@@ -136,7 +182,7 @@ __global__ __launch_bounds__(64 * NW, (NS == 3 && !MX) ? (NW == 8 ? 4 : 2) : 1) 
         rb = __builtin_amdgcn_make_buffer_rsrc((void*)(p.B + (int64_t)t.g * p.sBg + (int64_t)n0 * Kb), 0, 0x7ffffffe, 0x00020000);
 #pragma unroll
         for (int q = 0; q < MAXQ; ++q) {
-            const int r = w + q * NW;                       // wave-uniform
+            const int r = wq + q * NW;                      // wave-uniform
             const bool isA = r < AP;
             int row = (isA ? (MX ? r % APL : r) : r - AP) * 16 + lrow;
             row = min(row, isA ? p.M - 1 - m0 : p.N - 1 - n0);   // edge rows: re-read the last valid row (masked in the epilogue)
@@ -150,7 +196,7 @@ __global__ __launch_bounds__(64 * NW, (NS == 3 && !MX) ? (NW == 8 ? 4 : 2) : 1) 
         }
     };
     auto issue_slot = [&](int q, uint8_t* st, int ko) {
-        const int r = w + q * NW;
+        const int r = wq + q * NW;
         if (PT % NW == 0 || q + 1 < MAXQ || r < PT) {
             if (r < AP) STREAM_DMA(ra, st + r * 1024, vo[q], MX ? 2 * ko : ko);
             else STREAM_DMA(rb, st + r * 1024, vo[q], ko);
@@ -189,20 +235,19 @@ __global__ __launch_bounds__(64 * NW, (NS == 3 && !MX) ? (NW == 8 ? 4 : 2) : 1) 
         _Pragma("unroll") for (int j = 0; j < CJ; ++j) {                                                   \
             q0[j] = lds_frag(Bx_, swz3(brow + j * 32, fkg)); q1[j] = lds_frag(Bx_, swz3(brow + j * 32, 2 + fkg)); \
         }                                                                                                  \
+        STREAM_MX_LAB_B(q0, q1);                                                                           \
         _Pragma("unroll") for (int m = 0; m < 4; ++m) {                                                    \
             const uint8_t* Ap_ = (cur) + (m >> 1) * (BM3 * BK3);                                           \
             uint4 am[RI], bm[CJ];                                                                          \
             _Pragma("unroll") for (int i = 0; i < RI; ++i) am[i] = lds_frag(Ap_, swz3(arow + i * 32, 2 * fkg + (m & 1))); \
+            STREAM_MX_LAB_A(am);                                                                           \
             _Pragma("unroll") for (int j = 0; j < CJ; ++j) {                                               \
                 const uint4 s_ = (m >> 1) ? q1[j] : q0[j];                                                 \
                 const uint32_t w0_ = (m & 1) ? s_.z : s_.x, w1_ = (m & 1) ? s_.w : s_.y;                   \
-                bm[j] = make_uint4(fp8x2_bf16(w0_, false), fp8x2_bf16(w0_, true), fp8x2_bf16(w1_, false), fp8x2_bf16(w1_, true)); \
+                bm[j] = STREAM_MX_CVT(w0_, w1_);                                                           \
             }                                                                                              \
             _Pragma("unroll") for (int j = 0; j < CJ; ++j) {                                               \
-                _Pragma("unroll") for (int i = 0; i < RI; ++i) {                                           \
-                    if (FIRST && m == 0) acc[i][j] = mma0<1>(am[i], bm[j]);                                \
-                    else mma<1>(am[i], bm[j], acc[i][j]);                                                  \
-                }                                                                                          \
+                _Pragma("unroll") for (int i = 0; i < RI; ++i) STREAM_MX_MMA(FIRST && m == 0, am[i], bm[j], acc[i][j]); \
                 _Pragma("unroll") for (int q = m * CJ + j; q < MAXQ; q += 4 * CJ) issue_slot(q, (nxt), (ko)); \
             }                                                                                              \
         }                                                                                                  \
@@ -258,7 +303,9 @@ __global__ __launch_bounds__(64 * NW, (NS == 3 && !MX) ? (NW == 8 ? 4 : 2) : 1) 
                 else if ((NS - 2) * MAXQ == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
                 else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             }
+#if !defined(GEMM_LAB_NO_BARRIER)
             __builtin_amdgcn_s_barrier();
+#endif
             asm volatile("" ::: "memory");
             const int stn = st == 0 ? NS - 1 : st - 1;       // (st + NS - 1) % NS: the slot read in the previous step
             const int ko = i_k * BK3;
